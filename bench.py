@@ -28,11 +28,14 @@ Steady state: after an idle gap the part's power management slows launches ~3-40
 series by up to 35 % (tools/probes/transient.py), so PRE_ROLL untimed iterations run before the first
 timed leg, on top of --warmup; the timed region is exactly K iterations (`config.pre_roll_steps`).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--points P]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--points P] [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...     (one process per GPU, RCCL)
   python bench.py --gpus N          (no launcher: one process, N member threads of the library's device group, sums by RCCL)
-The main leg is repeated (K timed iterations each time, every repeat bracketed by the barrier + synchronize pair) until the
-timed regions add up to MIN_TIMED_S; `value` / `ms_per_step` are the MEDIAN repeat, min and max beside them (`repeats`).
+The main leg times exactly K iterations, bracketed by the barrier + synchronize pair: `ms_per_step` is that region over K.
+With --min-timed S it is repeated (K timed iterations each time) until the timed regions add up to S seconds; `value` /
+`ms_per_step` are then the MEDIAN repeat, min and max beside them (`repeats`).
+--dump-outputs DIR: after the main leg, what its last timed fit returned to the caller -- the fitted parameters and the
+final chi2 and lambda -- as float64 DIR/<name>.npy (the inputs are seeded, so two builds can be compared output for output).
 """
 import argparse
 import json
@@ -50,7 +53,7 @@ FIT_ITERS = 10                 # LM iterations per gfh_fit call in the timed reg
 # (tools/probes/transient.py: 0.49 ms -> 0.68 ms -> 0.49 ms from launch ~40 on).  The timed legs measure the steady
 # state: this many untimed iterations run first, on top of --warmup.
 PRE_ROLL = 64
-MIN_TIMED_S = 2.0              # the main leg repeats its K timed iterations until the timed regions add up to this
+MIN_TIMED_S = 0.0              # --min-timed default: one repeat, so --steps K times exactly K iterations
 SWEEP_BYTES_PER_POINT = 24 + 8 + 8 * P_ACTIVE     # read x,y,w; write res and 32 Jacobian entries
 GRAM_BYTES_PER_POINT = 8 * P_ACTIVE + 8
 CHI2_BYTES_PER_POINT = 24 + 8
@@ -199,6 +202,8 @@ def main():
                     "strong_leg, host_sum_ms_per_step): 'auto' = whenever more than one rank runs; 'on' also with one rank behind a communicator (rehearsal)")
     ap.add_argument('--only-config', type=int, default=None, help="with --legs configs: 2, 3 or 4 (one configuration per kernel trace)")
     ap.add_argument('--dry', action='store_true', help='print the schema of the multi-GPU line from a device group of compile-only members (no GPU needed)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed fit of the main leg returned (parameters, chi2, '
+                    'lambda) as float64 DIR/<name>.npy')
     args = ap.parse_args()
     if args.dry:
         return dry_line(args)
@@ -290,13 +295,14 @@ def main():
         done = 0
         while done < k:
             n = min(FIT_ITERS, k - done)
-            _, r = (on or ctx).fit(start, active, is_global, lambda_=1.0, max_iter=n, **extra)
+            p, r = (on or ctx).fit(start, active, is_global, lambda_=1.0, max_iter=n, **extra)
             if r.iterations != n and (strict or r.iterations < 1):
                 raise RuntimeError('fit stopped after %d of %d iterations (exit %d)' % (r.iterations, n, r.exit_reason))
             # (not strict -- the legs on other data than the headline's: a fit that ends a trial early, at a rejected step, counts its own iterations)
             last['iterations'] = last.get('iterations', 0) + r.iterations
             done += n
             last['r'] = r
+            last['pars'] = p
             for key in ('n_sweeps', 'n_chi2', 'n_lookahead'):
                 last[key] = last.get(key, 0) + getattr(r, key)
 
@@ -373,6 +379,12 @@ def main():
     order = sorted(range(len(reps)), key=lambda k: reps[k][0])
     dt, tm, counts, spread = reps[order[len(order) // 2]]
     rep_ms = [1e3 * r[0] / args.steps for r in reps]
+    if args.dump_outputs and rank == 0:
+        # the caller's view of the last timed step: the parameters and result of the main leg's last fit (every rank holds the same)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        r_last = reps[-1][2]['r']
+        for name, a in (('parameters', reps[-1][2]['pars']), ('chi2', [r_last.chi2]), ('lambda', [r_last.lambda_])):
+            np.save(os.path.join(args.dump_outputs, name + '.npy'), np.asarray(a, dtype=np.float64))
     n_allreduce_main = ctx.comm_info()[1]
     state_chi2 = counts['r'].chi2
     extra = args.legs == 'all'

@@ -2,7 +2,7 @@
 ! shape of the reference's example 4, fortran/examples/4_multiple_curves.F90: amplitudes and background per curve, decay times
 ! shared), timing gadf_init ... gadf_set and the first / a later gadf_fit on the host clock.
 ! usage: bench_global [curves] [points per curve] [max_iter] [files]      (defaults 64, 100000, 10; a 4th argument "files": the
-! curves are first written to text files under /tmp and handed to gadf_add_dataset by path)
+! curves are first written to text files in the working directory and handed to gadf_add_dataset by path)
 module decay3_model
   use ad
   use fitfunction
@@ -57,7 +57,7 @@ program bench_global
   end do
   if (files) then
      do c = 1, nc
-        write(path, '(a, i0, a)') '/tmp/gadfit_bench_global_', c, '.txt'
+        write(path, '(a, i0, a)') 'gadfit_bench_global_', c, '.txt'
         open(newunit=u, file=trim(path), action='write', status='replace')
         write(u, '(a)') '# x y'
         do i = 1, n
@@ -70,7 +70,7 @@ program bench_global
   call gadf_init(f, nc)
   do c = 1, nc
      if (files) then
-        write(path, '(a, i0, a)') '/tmp/gadfit_bench_global_', c, '.txt'
+        write(path, '(a, i0, a)') 'gadfit_bench_global_', c, '.txt'
         call gadf_add_dataset(trim(path))
      else
         call gadf_add_dataset(x(:, c), y(:, c))
@@ -96,7 +96,7 @@ program bench_global
   call gadf_close()
   if (files) then
      do c = 1, nc
-        write(path, '(a, i0, a)') '/tmp/gadfit_bench_global_', c, '.txt'
+        write(path, '(a, i0, a)') 'gadfit_bench_global_', c, '.txt'
         open(newunit=u, file=trim(path), status='old'); close(u, status='delete')
      end do
   end if

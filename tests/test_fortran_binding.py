@@ -138,7 +138,7 @@ def test_fortran_env_communicator_single_rank(tmp_path):
 @needs_flang
 @pytest.mark.gpu
 @pytest.mark.parametrize('images', [1, 3])
-def test_fortran_eval_with_plain_real_arithmetic_on_x(images):
+def test_fortran_eval_with_plain_real_arithmetic_on_x(tmp_path, images):
     """eval() computes x**2 and sin(0.05*x) in real(kp) arithmetic: the recorder tabulates them as auxiliary
     per-point columns (gfh_set_aux).  The Fortran fit equals the Python-API fit of the same model, where the
     arithmetic on the symbolic x is recorded and evaluated on the device.  images = 3: the same program on a
@@ -149,14 +149,14 @@ def test_fortran_eval_with_plain_real_arithmetic_on_x(images):
     _build()
     path = os.path.join(GOLD, 'gaussian_xy.txt')
     env = dict(os.environ) if images == 1 else dict(os.environ, GADFIT_HIP_DEVICES=str(images), GADFIT_HIP_GROUP_WRAP='1')
-    p = subprocess.run([os.path.join(BUILD, 'fit_real_x_functions'), path], capture_output=True, text=True, timeout=600, env=env)
+    p = subprocess.run([os.path.join(BUILD, 'fit_real_x_functions'), path], capture_output=True, text=True, timeout=600, env=env, cwd=str(tmp_path))
     assert p.returncode == 0 and 'DONE' in p.stdout, p.stdout + p.stderr
     got = np.array([float(l.split('=')[1]) for l in p.stdout.splitlines() if l.startswith('par ')])
     assert 'iterations = 4' in p.stdout and got.size == 6
     # gadf_print after the fit: curve on 11 points over the data range, parameter table, log with the device timings
-    curve = np.loadtxt('/tmp/gadfit_real_x_print')
+    curve = np.loadtxt(str(tmp_path / 'gadfit_real_x_print'))
     assert curve.shape == (11, 2) and curve[0, 0] == -100.0 and curve[-1, 0] == 100.0
-    assert 'fmax' in open('/tmp/gadfit_real_x_print_parameters').read() and 'Jacobian' in open('/tmp/gadfit_real_x_print_log').read()
+    assert 'fmax' in open(str(tmp_path / 'gadfit_real_x_print_parameters')).read() and 'Jacobian' in open(str(tmp_path / 'gadfit_real_x_print_log')).read()
 
     def model(q, x):
         return q[0] * exp(-((x - q[1]) / q[2]) ** 2) + q[3] + q[4] * (x ** 2 * 1.0e-4) + q[5] * sin(0.05 * x)
@@ -669,13 +669,14 @@ def test_fortran_a_constant_of_eval_changed_between_two_fits_takes_effect():
 
 @needs_flang
 @pytest.mark.gpu
-def test_fortran_global_fit_of_many_curves():
+def test_fortran_global_fit_of_many_curves(tmp_path):
     """tests/fortran/bench_global.F90 (BASELINE config 3's shape: amplitudes and background per curve, three decay times shared) at a
     small size: the datasets are laid side by side on several threads, the global fit finds the shared decay times"""
     _build()
     out = []
     for extra in ([], ['files']):                      # from arrays; from text files handed over by path (read side by side)
-        p = subprocess.run([os.path.join(BUILD, 'bench_global'), '8', '3000', '30'] + extra, capture_output=True, text=True, timeout=600)
+        p = subprocess.run([os.path.join(BUILD, 'bench_global'), '8', '3000', '30'] + extra, capture_output=True, text=True, timeout=600,
+                           cwd=str(tmp_path))          # ('files': the program writes its data files into its working directory)
         assert p.returncode == 0 and 'DONE' in p.stdout, p.stdout + p.stderr
         out.append([l for l in p.stdout.splitlines() if l.startswith('tau')][0])
     assert out[0] == out[1]

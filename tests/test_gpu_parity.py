@@ -434,6 +434,34 @@ def test_bench_distributed_path_on_one_gpu():
     assert d['host_sum_ms_per_step'] > 0 and d['host_sum_leg']['rccl_nranks'] == 0, d['host_sum_leg']
 
 
+def test_bench_steps_and_dumped_outputs(tmp_path):
+    """bench.py --steps K times exactly K iterations, and --dump-outputs writes what the last timed fit returned: with K = 13 the
+    timed region is a 10- and a 3-iteration fit from the start values, so the dumped parameters, chi2 and lambda are those of a
+    3-iteration fit of the same seeded points."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n = 200000
+    out = str(tmp_path / 'dump')
+    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '13', '--warmup', '1', '--pre-roll', '0',
+                        '--points', str(n), '--cpu-sample', '0', '--legs', 'main', '--dump-outputs', out],
+                       capture_output=True, text=True, timeout=900, cwd=root)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
+    d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith('{')][-1])
+    assert d['steps'] == 13 and d['repeats']['n'] == 1 and d['passes_in_timed_region']['iterations'] == 13 and d['ms_per_step'] > 0
+    got = {k: np.load(os.path.join(out, k + '.npy')) for k in ('parameters', 'chi2', 'lambda')}
+    assert sorted(os.listdir(out)) == ['chi2.npy', 'lambda.npy', 'parameters.npy']
+    assert all(a.dtype == np.float64 for a in got.values()) and got['parameters'].shape == (1, 32)
+    truth = M.gauss8_truth()
+    x, y, s = M.make_single_slice(M.gauss8_numpy, truth, n, 0, n, 0.0, 100.0)
+    c = _lib.Context(0)
+    c.set_model(trace_model(M.model_gauss8, 32)); c.set_data(x, y, s, [0, n]); c.init_weights(4)
+    c.set_lookahead(True); c.set_placement_after(0)
+    pars, r = c.fit(M.start_values(truth).reshape(1, 32), list(range(32)), [0] * 32, lambda_=1.0, max_iter=3)
+    c.close()
+    assert r.iterations == 3
+    assert rel(got['parameters'], pars) < TOL_FIT and rel(got['chi2'], [r.chi2]) < TOL_FIT and rel(got['lambda'], [r.lambda_]) < TOL_LAMBDA
+
+
 def test_cfg1_two_exponential_200_points(ctx):
     """BASELINE config 1: 2-exponential decay, 200 points, 4 active parameters; full fit vs the oracle
     with the reference's defaults plus acceleration, run to the iteration limit."""

@@ -118,8 +118,11 @@ def test_reference_example_runs_unchanged_on_the_device(tmp_path):
     from gadfit_amd.ad import trace_model
     from oracle import binding as orc
     from tests.golden import goldens as G
-    exe = os.path.join(REF_BIN, 'example')
-    assert os.path.exists(exe), 'oracle/_ref/example was not built (oracle/build_ref_programs.py in the build container; the directory travels with the snapshot)'
+    exe = os.path.join(REF_BIN, 'example_cwd_data')
+    assert os.path.exists(exe), 'oracle/_ref/example_cwd_data was not built (oracle/build_ref_programs.py in the build container; the directory travels with the snapshot)'
+    # (built with DATA_DIR = '.': the two data files are the committed fixtures, under the names the program opens in its working directory)
+    for k in (1, 2):
+        shutil.copyfile(os.path.join(ROOT, 'tests', 'golden', 'curve%d_xy.txt' % k), os.path.join(str(tmp_path), 'example_data%d' % k))
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout + r.stderr
     got = np.zeros((2, 3))
