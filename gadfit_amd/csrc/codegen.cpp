@@ -1353,18 +1353,18 @@ int mesh_sites(const Model& m) {
 //   GFH_CLOAD_W(B, U)  fragment reads of k-step U into buffer B: one per DISTINCT tile of the run + the residual row
 //   GFH_CMMA_W(B)      one v_mfma_f64_16x16x4_f64 per pair; J^T r of tile t with the owner of pair (t, t)
 //   GFH_CPUT_W         the wave's accumulators into the workgroup's image
-static std::string coop_defines(int NA, const GenConfig& cfg) {
+static std::string coop_defines(int NA) {
   std::ostringstream o;
-  const bool on = fused_coop(NA, cfg);
+  const bool on = fused_coop(NA);
   o << "\n#define GFH_COOP " << (on ? 1 : 0);
   if (!on) return o.str();
-  const int T = (NA + 15) / 16, npair = T * (T + 1) / 2, fw = fused_waves_for(NA, cfg);
+  const int T = (NA + 15) / 16, npair = T * (T + 1) / 2, fw = fused_waves_for(NA);
   std::vector<std::pair<int, int>> pairs;
   for (int ti = 0; ti < T; ti++) for (int tj = ti; tj < T; tj++) pairs.push_back({ti, tj});
   int cnd = 0;
   std::ostringstream body;
-  for (int w = 0, p0 = 0; w < 4; w++) {
-    const int nk = w < fw ? npair / fw + (w < npair % fw ? 1 : 0) : 0;
+  for (int w = 0, p0 = 0; w < fw; w++) {
+    const int nk = npair / fw + (w < npair % fw ? 1 : 0);
     std::vector<int> tiles;                                   // distinct tiles of this wave's run, in order of first use
     auto slot = [&](int t) { for (size_t d = 0; d < tiles.size(); d++) if (tiles[d] == t) return (int)d; tiles.push_back(t); return (int)tiles.size() - 1; };
     std::ostringstream mma0, mma, put;
@@ -1401,9 +1401,9 @@ bool generate_source(const Model& m, const std::vector<int32_t>& active, const G
   std::ostringstream s;
   s << "// generated by libgadfit_hip codegen -- model with " << st.nodes.size() << " tape nodes, "
     << NP << " parameters, " << NA << " active\n";
-  s << "#define GFH_OMEGA_JT " << (cfg.omega_jt ? 1 : 0) << "\n#define GFH_FW " << fused_waves_for(NA, cfg) << "\n#define GFH_HALF " << (fused_half_stage(NA, cfg) ? 1 : 0) << "\n#define GFH_FUSED_WPE " << cfg.fused_wpe << "\n#define GFH_FRAG_LATE " << cfg.frag_late << "\n#define GFH_RED1 " << (fused_single_image(NA, cfg) ? 1 : 0) << "\n#define GFH_FUSED_MAX " << fused_max_active(cfg) << coop_defines(NA, cfg) << "\n#define GFH_FAST_DIV " << (cfg.fast_div ? 1 : 0)
+  s << "#define GFH_OMEGA_JT " << (cfg.omega_jt ? 1 : 0) << "\n#define GFH_FW " << fused_waves_for(NA) << "\n#define GFH_HALF " << (fused_half_stage(NA) ? 1 : 0) << "\n#define GFH_RED1 " << (fused_single_image(NA) ? 1 : 0) << "\n#define GFH_FUSED_MAX " << kFusedMaxActive << coop_defines(NA) << "\n#define GFH_FAST_DIV " << (cfg.fast_div ? 1 : 0)
     << "\n#define GFH_STORE_J " << (cfg.store_j ? 1 : 0) << "\n#define GFH_STORE_RES " << (cfg.store_res ? 1 : 0) << "\n#define GFH_LOSS " << cfg.loss << "\n#define GFH_BLOCK " << cfg.block << "\n#define GFH_NP " << NP
-    << "\n#define GFH_NA " << (NA > 0 ? NA : 1) << "\n#define GFH_VALU_GRAM_MAX " << kValuGramMax << "\n#define GFH_VAHEAD " << valu_ahead_for(NA, cfg) << "\n#define GFH_AHEAD " << std::max(1, std::min(2, cfg.frag_ahead)) << "\n#define GFH_ABLATE " << cfg.ablate << "\n#define GFH_MATRIX_PRIO " << (cfg.store_j ? 0 : cfg.matrix_prio) << "\n";
+    << "\n#define GFH_NA " << (NA > 0 ? NA : 1) << "\n#define GFH_VALU_GRAM_MAX " << kValuGramMax << "\n#define GFH_AD_PRIO " << (cfg.store_j ? 0 : 1) << "\n";
   s << "#define GFH_PARG " << cfg.kernarg_pars << "\n";
   s << R"(
 // exp(x): the operations of the device library's exp (ROCm device-libs, __ocml_exp_f64: n = rint(x log2 e), two-step
@@ -1862,11 +1862,6 @@ static __device__ __forceinline__ double gfh_wave_sum(double t) {
 #define GFH_NH 1
 #define GFH_KS 16
 #endif
-#if GFH_FUSED_WPE > 0
-#define GFH_FOCC __attribute__((amdgpu_waves_per_eu(GFH_FUSED_WPE)))
-#else
-#define GFH_FOCC
-#endif
 // Descriptor of the fused kernel's tail (filled by the host, context.cpp TailDesc).
 struct gfh_tail {
   const int* ds_first_gb;          // [nd+1] first workgroup of each dataset
@@ -1891,7 +1886,7 @@ struct gfh_tail {
 #else
 #define GFH_K_SWEEP_GRAM gfh_k_sweep_gram_nostore
 #endif
-extern "C" __global__ __launch_bounds__(GFH_FTHREADS) GFH_FOCC
+extern "C" __global__ __launch_bounds__(GFH_FTHREADS)
 void GFH_K_SWEEP_GRAM(const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ w,
                       GFH_PARS_DECL, const i64* __restrict__ gb_start,
                       const int* __restrict__ gb_slots, const int* __restrict__ gb_ds,
@@ -1916,8 +1911,6 @@ void GFH_K_SWEEP_GRAM(const double* __restrict__ x, const double* __restrict__ y
   for (int k = 0; k < NACC; k++) av[k] = 0.0;
   i64 iw = s0 + 64 * __builtin_amdgcn_readfirstlane(wv);
   double Xc = (x + iw)[lane], Yc = (y + iw)[lane], Wc = (w + iw)[lane];
-  // GFH_VAHEAD == 2 (GADFIT_HIP_VALU_AHEAD=2, an experiment of round 6 that changed nothing: model.h, valu_ahead_for): the inputs are
-  // loaded TWO passes ahead through three rotating register sets; the default loads one pass ahead.
   auto body = [&](const double XC, const double YC, const double WC) __attribute__((always_inline)) {
     double* __restrict__ Jw = J + iw;
     double F, G[GFH_NA];
@@ -1942,27 +1935,6 @@ void GFH_K_SWEEP_GRAM(const double* __restrict__ x, const double* __restrict__ y
     for (int a = 0; a < GFH_NA; a++) av[NP_ + a] += G[a] * R;          // gadfit.F90:698
     av[NP_ + GFH_NA] += R * R;
   };
-#if GFH_VAHEAD >= 2
-  const i64 i1 = iw + GFH_FTHREADS < e ? iw + GFH_FTHREADS : iw;
-  double Xn = (x + i1)[lane], Yn = (y + i1)[lane], Wn = (w + i1)[lane];
-  double Xf = 0.0, Yf = 0.0, Wf = 0.0;                      // (the third register set: free at entry)
-  asm volatile("" :: "v"(Xc), "v"(Yc), "v"(Wc), "v"(Xn), "v"(Yn), "v"(Wn));      // (see the matrix path: keeps the per-pass wait a counted one)
-  // One pass: the loads of the pass after next go out into the free register set (XL ...), then the pass on (XC ...).  Three passes per
-  // trip with the roles of the sets rotating, so that no register move has to wait for a load on its way.
-  auto pass = [&](const double XC, const double YC, const double WC, double& XL, double& YL, double& WL) __attribute__((always_inline)) {
-    const i64 in = iw + 2 * GFH_FTHREADS < e ? iw + 2 * GFH_FTHREADS : iw;
-    XL = (x + in)[lane]; YL = (y + in)[lane]; WL = (w + in)[lane];
-    body(XC, YC, WC);
-    iw += GFH_FTHREADS;
-  };
-  while (iw < e) {
-    pass(Xc, Yc, Wc, Xf, Yf, Wf);
-    if (iw >= e) break;
-    pass(Xn, Yn, Wn, Xc, Yc, Wc);
-    if (iw >= e) break;
-    pass(Xf, Yf, Wf, Xn, Yn, Wn);
-  }
-#else
   asm volatile("" :: "v"(Xc), "v"(Yc), "v"(Wc));             // (see the matrix path: keeps the per-pass wait a counted one)
   for (; iw < e; iw += GFH_FTHREADS) {
     const i64 in = iw + GFH_FTHREADS < e ? iw + GFH_FTHREADS : iw;
@@ -1970,7 +1942,6 @@ void GFH_K_SWEEP_GRAM(const double* __restrict__ x, const double* __restrict__ y
     body(Xc, Yc, Wc);
     Xc = Xn; Yc = Yn; Wc = Wn;
   }
-#endif
   // wave tree of the NACC sums: t_l += t_(l+32), += t_(l+16) through the LDS crossbar (ds_bpermute, what __shfl_down compiles to), then
   // += t_(l+8), (l+4), (l+2), (l+1) as DPP row shifts inside the 16 lanes of row 0 -- the additions __shfl_down's tree makes, the same
   // bits, with a third of the crossbar operations: 45 sums x 6 levels x 2 halves = 540 ds_bpermute per wave, all waves of the chip
@@ -2016,6 +1987,7 @@ void GFH_K_SWEEP_GRAM(const double* __restrict__ x, const double* __restrict__ y
   constexpr int STAGE = ROWS * GFH_S;
   constexpr int IMG = GFH_NPAIR * 256 + 16 * GFH_T + 1;      // the workgroup's sums (partial image)
   constexpr int EPI = GFH_T * 64 + 8 + IMG;                  // epilogue: J^T r fragments per tile | wave sums of r^2 | the image, laid over the stages
+  static_assert(GFH_FW == 4, "the cooperative form is written for one wave per SIMD: GFH_CSTAGES / GFH_CPUT dispatch, coop_defines");
   __shared__ double lds[GFH_FW * STAGE > EPI ? GFH_FW * STAGE : EPI];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int r = lane & 15, q = lane >> 4;
@@ -2043,13 +2015,7 @@ void GFH_K_SWEEP_GRAM(const double* __restrict__ x, const double* __restrict__ y
     const i64 in = iw + GFH_FTHREADS < e ? iw + GFH_FTHREADS : iw;
     const double Xn = (x + in)[lane], Yn = (y + in)[lane], Wn = (w + in)[lane];
     double F, G[GFH_NA];
-#if GFH_ABLATE & 8
-    F = Xc * 0.5;
-#pragma unroll
-    for (int a = 0; a < GFH_NA; a++) G[a] = Xc + (double)a;
-#else
     gfh_point_grad(Xc, P, F, G, status, aux + iw + lane, lda GFH_MESH_NONE GFH_SLOT(iw + lane));
-#endif
     double R = (Yc - F) * Wc;                               // gadfit.F90:682-683
     double Wl = Wc;
     GFH_ROBUST(R, Wl)
@@ -2089,19 +2055,11 @@ void GFH_K_SWEEP_GRAM(const double* __restrict__ x, const double* __restrict__ y
           __builtin_amdgcn_sched_barrier(0);                                                                        \
         }                                                                                                           \
       }
-#if GFH_ABLATE & 4
-#define GFH_MFMA(A_, B_, C_) asm volatile("" :: "v"(A_), "v"(B_))
-#else
 #define GFH_MFMA(A_, B_, C_) C_ = __builtin_amdgcn_mfma_f64_16x16x4f64(A_, B_, C_, 0, 0, 0)
-#endif
       if (wvu == 0) { GFH_CSTAGES(0) }
-#if GFH_FW > 1
       else if (wvu == 1) { GFH_CSTAGES(1) }
-#endif
-#if GFH_FW > 2
       else if (wvu == 2) { GFH_CSTAGES(2) }
       else { GFH_CSTAGES(3) }
-#endif
       __syncthreads();
     }
     Xc = Xn; Yc = Yn; Wc = Wn;
@@ -2118,13 +2076,9 @@ void GFH_K_SWEEP_GRAM(const double* __restrict__ x, const double* __restrict__ y
     tail_img[idx] = acc[K_][j]; }
 #define GFH_CPUTR(K_, T_) vecs[(T_) * 64 + lane] = accr[K_];
   if (wvu == 0) { GFH_CPUT_0 }
-#if GFH_FW > 1
   else if (wvu == 1) { GFH_CPUT_1 }
-#endif
-#if GFH_FW > 2
   else if (wvu == 2) { GFH_CPUT_2 }
   else { GFH_CPUT_3 }
-#endif
   {
     const double t = gfh_wave_sum(accc);                     // wave tree, then the waves in order: gfh_k_chi2's order
     if (lane == 0) wsum[wv] = t;
@@ -2149,7 +2103,7 @@ void GFH_K_SWEEP_GRAM(const double* __restrict__ x, const double* __restrict__ y
   constexpr int RED = GFH_NPAIR * 256 + GFH_T * 64 + 4;      // cross-wave reduction image (as k_gram)
   constexpr int IMG = GFH_NPAIR * 256 + 16 * GFH_T + 1;      // the workgroup's own sums (partial image), kept for the single-workgroup tail
 #if GFH_RED1
-  // 5 and 6 tiles: ONE pair image that the waves add into in order + the waves' J^T r / r^T r vectors + the workgroup's sums,
+  // 5 tiles: ONE pair image that the waves add into in order + the waves' J^T r / r^T r vectors + the workgroup's sums,
   // laid over the stages once the pass loop is done (model.h, fused_lds_bytes_for)
   constexpr int VEC = GFH_T * 64 + 4;
   constexpr int RED1 = GFH_NPAIR * 256 + GFH_FW * VEC + IMG;
@@ -2202,8 +2156,8 @@ void GFH_K_SWEEP_GRAM(const double* __restrict__ x, const double* __restrict__ y
   // the store queue at the top of every pass.  With a clean entry state the wait inside the loop
   // is the counted one (the 3 prefetch loads are OLDER than the pass's stores).
   asm volatile("" :: "v"(Xc), "v"(Yc), "v"(Wc));
-#if GFH_MATRIX_PRIO < 0
-  __builtin_amdgcn_s_setprio(-(GFH_MATRIX_PRIO));            // (the AD phase of the first pass; GenConfig::matrix_prio)
+#if GFH_AD_PRIO
+  __builtin_amdgcn_s_setprio(3);                             // (the AD phase of the first pass; GenConfig::store_j)
 #endif
   for (; iw < e; iw += GFH_FTHREADS) {
     // prefetch the next pass's inputs before the long compute phase (the last pass re-reads its
@@ -2212,28 +2166,20 @@ void GFH_K_SWEEP_GRAM(const double* __restrict__ x, const double* __restrict__ y
     const double Xn = (x + in)[lane], Yn = (y + in)[lane], Wn = (w + in)[lane];
     double* __restrict__ Jw = J + iw;
     double F, G[GFH_NA];
-#if GFH_ABLATE & 8
-    F = Xc * 0.5;
-#pragma unroll
-    for (int a = 0; a < GFH_NA; a++) G[a] = Xc + (double)a;
-#else
     gfh_point_grad(Xc, P, F, G, status, aux + iw + lane, lda GFH_MESH_NONE GFH_SLOT(iw + lane));
-#endif
     double R = (Yc - F) * Wc;                               // gadfit.F90:682-683
     double Wl = Wc;
     GFH_ROBUST(R, Wl)
     gfh_store64(res + iw, lane * 8, R);
     accc += R * R;                                          // every lane sums its own points pass by pass: the order gfh_k_chi2 uses
-#if !(GFH_ABLATE & 1) && !GFH_HALF
+#if !GFH_HALF
     st[16 * GFH_T * GFH_S + lane] = R;
 #endif
 #pragma unroll
     for (int a = 0; a < GFH_NA; a++) {
       G[a] = G[a] * Wl;                                     // gadfit.F90:689-690
-#if !(GFH_ABLATE & 1) && !GFH_HALF
+#if !GFH_HALF
       st[a * GFH_S + lane] = G[a];
-#elif GFH_ABLATE & 1
-      asm volatile("" :: "v"(G[a]));
 #endif
     }
 #if GFH_STORE_J
@@ -2242,42 +2188,26 @@ void GFH_K_SWEEP_GRAM(const double* __restrict__ x, const double* __restrict__ y
     // barrier is idle time (0.352 against 0.334 ms)
     __syncthreads();
 #endif
-    // k-steps: the fragment reads of step s+1 are issued before the MFMAs of step s so the
-    // LDS latency hides under the 64-cycle matrix instructions (sched_barrier pins the order)
-    // GFH_AHEAD sets of fragments in flight: the reads of step s + GFH_AHEAD go out before the matrix instructions of step s
-    double fn[GFH_AHEAD][GFH_T], f4n[GFH_AHEAD][GFH_T], man[GFH_AHEAD][NMIX + 1], mbn[GFH_AHEAD][NMIX + 1], rn[GFH_AHEAD];
-#if GFH_ABLATE & 2
+    // k-steps: the fragment reads of step s+1 are issued while the matrix instructions of step s run, so the
+    // LDS latency hides under them (sched_barrier pins the order)
+    double fn[GFH_T], f4n[GFH_T], man[NMIX + 1], mbn[NMIX + 1], rn;
 #define GFH_FRAGS(S_)                                                                                            \
     _Pragma("unroll") for (int t = 0; t < GFH_T; t++) {                                                          \
-      fn[(S_) % GFH_AHEAD][t] = G[(2 * (S_) + t) % GFH_NA];                                                      \
-      f4n[(S_) % GFH_AHEAD][t] = G[(2 * (S_) + t + 5) % GFH_NA];                                                 \
-    }                                                                                                            \
-    _Pragma("unroll") for (int m = 0; m <= NMIX; m++) {                                                          \
-      man[(S_) % GFH_AHEAD][m] = G[(2 * (S_) + m + 9) % GFH_NA];                                                 \
-      mbn[(S_) % GFH_AHEAD][m] = G[(2 * (S_) + m + 13) % GFH_NA];                                                \
-    }                                                                                                            \
-    rn[(S_) % GFH_AHEAD] = G[(S_) % GFH_NA];
-#else
-#define GFH_FRAGS(S_)                                                                                            \
-    _Pragma("unroll") for (int t = 0; t < GFH_T; t++) {                                                          \
-      fn[(S_) % GFH_AHEAD][t] = st[(16 * t + r) * GFH_S + 4 * (S_) + q];                                         \
-      f4n[(S_) % GFH_AHEAD][t] = st[(16 * t + r4) * GFH_S + 4 * (S_) + q];                                       \
+      fn[t] = st[(16 * t + r) * GFH_S + 4 * (S_) + q];                                                           \
+      f4n[t] = st[(16 * t + r4) * GFH_S + 4 * (S_) + q];                                                         \
     }                                                                                                            \
     _Pragma("unroll") for (int m = 0; m < NMIX; m++) {                                                           \
-      man[(S_) % GFH_AHEAD][m] = st[(16 * (2 * m + hi) + r) * GFH_S + 4 * (S_) + q];                             \
-      mbn[(S_) % GFH_AHEAD][m] = st[(16 * (2 * m + hi) + r8) * GFH_S + 4 * (S_) + q];                            \
+      man[m] = st[(16 * (2 * m + hi) + r) * GFH_S + 4 * (S_) + q];                                               \
+      mbn[m] = st[(16 * (2 * m + hi) + r8) * GFH_S + 4 * (S_) + q];                                              \
     }                                                                                                            \
-    if (GFH_T & 1) mbn[(S_) % GFH_AHEAD][NMIX] = st[(16 * (GFH_T - 1) + r8) * GFH_S + 4 * (S_) + q];             \
-    rn[(S_) % GFH_AHEAD] = st[16 * GFH_T * GFH_S + 4 * (S_) + q];
-#endif
-#if GFH_MATRIX_PRIO > 0
-    __builtin_amdgcn_s_setprio(GFH_MATRIX_PRIO);
-#elif GFH_MATRIX_PRIO < 0
+    if (GFH_T & 1) mbn[NMIX] = st[(16 * (GFH_T - 1) + r8) * GFH_S + 4 * (S_) + q];                               \
+    rn = st[16 * GFH_T * GFH_S + 4 * (S_) + q];
+#if GFH_AD_PRIO
     __builtin_amdgcn_s_setprio(0);
 #endif
 #pragma unroll
     for (int h = 0; h < GFH_NH; h++) {
-#if GFH_HALF && !(GFH_ABLATE & 1)
+#if GFH_HALF
       // this half's 32 points into the stage (the fragment reads of the half before are older LDS operations of this wave:
       // the LDS executes a wave's operations in order)
       if ((lane >> 5) == h) {
@@ -2286,39 +2216,30 @@ void GFH_K_SWEEP_GRAM(const double* __restrict__ x, const double* __restrict__ y
         for (int a = 0; a < GFH_NA; a++) st[a * GFH_S + (lane & 31)] = G[a];
       }
 #endif
+      // (the first k-step's reads stay a one-trip loop: written out straight they compile to another instruction order)
 #pragma unroll
-      for (int s = 0; s < GFH_AHEAD; s++) { GFH_FRAGS(s) }
+      for (int s = 0; s < 1; s++) { GFH_FRAGS(s) }
 #pragma unroll
       for (int s = 0; s < GFH_KS; s++) {
         double fa[GFH_T], f4[GFH_T], ma[NMIX + 1], mb[NMIX + 1];
 #pragma unroll
-        for (int t = 0; t < GFH_T; t++) { fa[t] = fn[s % GFH_AHEAD][t]; f4[t] = f4n[s % GFH_AHEAD][t]; }
+        for (int t = 0; t < GFH_T; t++) { fa[t] = fn[t]; f4[t] = f4n[t]; }
 #pragma unroll
-        for (int m = 0; m <= NMIX; m++) { ma[m] = man[s % GFH_AHEAD][m]; mb[m] = mbn[s % GFH_AHEAD][m]; }
-        const double rr = rn[s % GFH_AHEAD];
-#if !GFH_FRAG_LATE
-        if (s + GFH_AHEAD < GFH_KS) { GFH_FRAGS(s + GFH_AHEAD) }
-#endif
+        for (int m = 0; m <= NMIX; m++) { ma[m] = man[m]; mb[m] = mbn[m]; }
+        const double rr = rn;
         __builtin_amdgcn_sched_barrier(0);
         int p = 0;
-#if GFH_ABLATE & 4
-#pragma unroll
-        for (int t = 0; t < GFH_T; t++) asm volatile("" :: "v"(fa[t]), "v"(f4[t]));
-#pragma unroll
-        for (int m = 0; m <= NMIX; m++) asm volatile("" :: "v"(ma[m]), "v"(mb[m]));
-#else
 #pragma unroll
         for (int ti = 0; ti < GFH_T; ti++)
 #pragma unroll
           for (int tj = ti; tj < GFH_T; tj++, p++)
             if (tj > ti) acc[p] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[ti], fa[tj], acc[p], 0, 0, 0);
-#if GFH_FRAG_LATE
         // the next step's fragment reads go out BEHIND this step's 64-cycle matrix instructions (issued, they run by themselves):
-        // the wave's LDS instructions then cost the shared FP64 pipe no idle issue slots
+        // the wave's LDS instructions then cost the shared FP64 pipe no idle issue slots (round 5: no-store 0.3135 -> 0.299 ms,
+        // stored 0.209 -> 0.178 ms at N = 4e6, against the reads in front of them)
         __builtin_amdgcn_sched_barrier(0);
-        if (s + GFH_AHEAD < GFH_KS) { GFH_FRAGS(s + GFH_AHEAD) }
+        if (s + 1 < GFH_KS) { GFH_FRAGS(s + 1) }
         __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
         for (int t = 0; t < GFH_T; t++) {
           dga[t] = __builtin_amdgcn_mfma_f64_4x4x4f64(fa[t], fa[t], dga[t], 0, 0, 0);
@@ -2327,7 +2248,6 @@ void GFH_K_SWEEP_GRAM(const double* __restrict__ x, const double* __restrict__ y
 #pragma unroll
         for (int m = 0; m < NMIX; m++) dgm[m] = __builtin_amdgcn_mfma_f64_4x4x4f64(ma[m], mb[m], dgm[m], 0, 0, 0);
         if (GFH_T & 1) dgm[NMIX] = __builtin_amdgcn_mfma_f64_4x4x4f64(fa[GFH_T - 1], mb[NMIX], dgm[NMIX], 0, 0, 0);
-#endif
 #pragma unroll
         for (int t = 0; t < GFH_T; t++) accr[t] += fa[t] * rr;
 #if GFH_STORE_J
@@ -2340,10 +2260,8 @@ void GFH_K_SWEEP_GRAM(const double* __restrict__ x, const double* __restrict__ y
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-#if GFH_MATRIX_PRIO > 0
-    __builtin_amdgcn_s_setprio(0);
-#elif GFH_MATRIX_PRIO < 0
-    __builtin_amdgcn_s_setprio(-(GFH_MATRIX_PRIO));
+#if GFH_AD_PRIO
+    __builtin_amdgcn_s_setprio(3);
 #endif
 #if GFH_STORE_J
     __syncthreads();
@@ -2351,11 +2269,11 @@ void GFH_K_SWEEP_GRAM(const double* __restrict__ x, const double* __restrict__ y
     Xc = Xn; Yc = Yn; Wc = Wn;
   }
 
-#if GFH_MATRIX_PRIO
+#if GFH_AD_PRIO
   __builtin_amdgcn_s_setprio(0);
 #endif
 #if GFH_RED1
-  // cross-wave reduction, 5 and 6 tiles: the waves add their accumulators into ONE image in wave order -- ((w0 + w1) + w2) + w3,
+  // cross-wave reduction, 5 tiles: the waves add their accumulators into ONE image in wave order -- ((w0 + w1) + w2) + w3,
   // the order in which the per-wave images of the smaller kernels are added -- then J^T r and r^T r from per-wave vectors as there
   __syncthreads();                                           // (every wave is done with its stage: the image lies over them)
   double* img1 = lds;

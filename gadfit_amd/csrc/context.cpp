@@ -132,7 +132,6 @@ Range::~Range() { if (on_) roctx().pop(); }
 
 int join_pending(gfh_ctx* c) {
   if (!c->pending.joinable()) return 0;
-  c->stop_warm.store(true);
   c->pending.join();
   c->creating = false;
   const int rc = c->pending_rc;
@@ -268,16 +267,8 @@ int gfh_create(int device, gfh_ctx** out) {
   if (const char* e = getenv("GADFIT_HIP_KEEP_J")) { int v = atoi(e); if (v >= 0 && v <= 2) { c->keep_jacobian = v; c->gen.store_j = v != 0; } }
   if (const char* e = getenv("GADFIT_HIP_MESH")) c->mesh_on = atoi(e) != 0;
   if (const char* e = getenv("GADFIT_HIP_ORDER")) c->order_on = atoi(e) != 0;
-  if (const char* e = getenv("GADFIT_HIP_KEEP_WARM")) c->keep_warm = atoi(e) != 0;
   if (const char* e = getenv("GADFIT_HIP_PLACEMENT_AFTER")) { int v = atoi(e); if (v >= 0) c->placement_after = v; }
   if (const char* e = getenv("GADFIT_HIP_WS_FAST")) { int v = atoi(e); if (v >= 0) c->ws_fast = v; }
-  if (const char* e = getenv("GADFIT_HIP_HALF_STAGE")) { int v = atoi(e); if (v >= -1 && v <= 1) c->gen.half_stage = v; }
-  if (const char* e = getenv("GADFIT_HIP_FUSED_WAVES")) { int v = atoi(e); if (v == 1 || v == 2 || v == 4 || v == 8) c->gen.fused_waves = v; }
-  if (const char* e = getenv("GADFIT_HIP_SINGLE_IMAGE")) c->gen.single_image = atoi(e) != 0;
-  if (const char* e = getenv("GADFIT_HIP_FRAG_LATE")) c->gen.frag_late = atoi(e) != 0;
-  if (const char* e = getenv("GADFIT_HIP_FUSED_WPE")) { int v = atoi(e); if (v >= 0 && v <= 8) c->gen.fused_wpe = v; }
-  if (const char* e = getenv("GADFIT_HIP_COOP")) { int v = atoi(e); if (v >= 0 && v <= 2) c->gen.coop = v; }
-  if (const char* e = getenv("GADFIT_HIP_VALU_AHEAD")) { int v = atoi(e); if (v >= 0 && v <= 2) c->gen.valu_ahead = v; }
   if (const char* e = getenv("GADFIT_HIP_TIMERS")) { int v = atoi(e); if (v >= 0 && v <= 2) c->timer_detail = v; }
   if (device >= 0 && init_device(c)) { delete c; return 1; }
   *out = c;
@@ -573,7 +564,6 @@ constexpr int kPassGranule = 512;      // slots one pass of an 8-wave workgroup 
 // (4-wave workgroups on 768 blocks for the VALU form of the fused kernel were measured: cfg 2 0.174 against 0.166 ms, and
 // gfh_k_chi2 on the same partition 0.077 against 0.064 ms.)
 static int gb_target_for(const gfh_ctx* c) {
-  if (const char* e = getenv("GADFIT_HIP_GB_TARGET")) { const int v = atoi(e); if (v > 0) return v; }      // (experiments)
   return c->has_model && c->model.has_integrals() ? kGramTargetFine : kGramTarget;
 }
 
@@ -795,7 +785,6 @@ int gfh_set_data_begin(gfh_ctx* c, int64_t n_total, const double* x, const doubl
   c->hx.clear(); c->hy.clear(); c->hw.clear();
   const int64_t b = c->begin;
   if (!creation.joinable()) c->pending_rc = 0;
-  c->stop_warm.store(false);
   // (the creation thread, still running, travels into the upload thread inside `prev`.  Should that thread not start -- std::thread
   // throws on EAGAIN -- `prev` must be joined HERE: unwinding would destroy a joinable std::thread, which is std::terminate
   // before any handler runs, and bail() only knows `creation`, moved from by then: round-5 advisor)
@@ -808,19 +797,6 @@ int gfh_set_data_begin(gfh_ctx* c, int64_t n_total, const double* x, const doubl
       if (!rc) rc = hipSetDevice(c->device) == hipSuccess ? 0 : fail(c, "hipSetDevice failed");
       if (!rc) rc = upload_tables(c);
       if (!rc) rc = upload_points(c, x + b, y + b, w + b);
-      // The caller is still busy on the host (that is why it asked for an upload in the background), and its first passes are
-      // about to come: the part is kept busy until the caller is back (join_pending), so those passes do not start in the clock
-      // ramp that follows an idle gap (20-35 % slower launches, tools/probes/transient.py).  At most 200 ms.
-      c->warm_ms = 0;
-      if (!rc && c->keep_warm && c->n_slots > 0) {
-        const auto t0 = std::chrono::steady_clock::now();
-        while (!c->stop_warm.load()) {
-          if (launch_keep_warm(c->stream, c->x.as<double>(), c->n_slots, 8, c->res.as<double>()) != hipSuccess) { (void)hipGetLastError(); break; }
-          if (hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipGetLastError(); break; }
-          c->warm_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-          if (c->warm_ms > 200.0) break;
-        }
-      }
       c->pending_rc = rc;
     });
   } catch (const std::exception& e) {
@@ -993,17 +969,11 @@ int gfh_set_model_variants(gfh_ctx* c, int n, const gfh_tape* const* t, int hint
   // (a model handed over by a recovery's handler keeps the grown state: the pass that is about to be repeated has needed it)
   c->ws_grown = c->ws_grown && c->in_recovery;
   apply_ws_plan(c);
-  {
-    // Models with integrate(): the plain kernels are bound by VALU issue and their bodies take 135-150 VGPRs as the compiler
-    // allocates them (3 waves per SIMD; gfh_k_chi2's 8-wave workgroups then fit once per CU = 2 waves per SIMD).  Capped at 128
-    // registers (4 waves) a handful of values spill and chi2 runs 20 % faster, the sweep 4 %; at 96 (5 waves) the spills cost
-    // more than the waves bring (profiles/r03_cfg4.md).  GADFIT_HIP_WAVES_PER_EU overrides (0: the compiler's choice).
-    const char* e = getenv("GADFIT_HIP_WAVES_PER_EU");
-    c->gen.waves_per_eu = e ? atoi(e) : (c->model.has_integrals() ? 4 : 0);
-    if (const char* pr = getenv("GADFIT_HIP_MATRIX_PRIO")) c->gen.matrix_prio = std::max(-3, std::min(3, atoi(pr)));
-    if (const char* ab = getenv("GADFIT_HIP_ABLATE")) c->gen.ablate = atoi(ab);
-    if (const char* fa = getenv("GADFIT_HIP_FRAG_AHEAD")) c->gen.frag_ahead = std::max(1, std::min(2, atoi(fa)));
-  }
+  // Models with integrate(): the plain kernels are bound by VALU issue and their bodies take 135-150 VGPRs as the compiler
+  // allocates them (3 waves per SIMD; gfh_k_chi2's 8-wave workgroups then fit once per CU = 2 waves per SIMD).  Capped at 128
+  // registers (4 waves) a handful of values spill and chi2 runs 20 % faster, the sweep 4 %; at 96 (5 waves) the spills cost
+  // more than the waves bring (profiles/r03_cfg4.md).
+  c->gen.waves_per_eu = c->model.has_integrals() ? 4 : 0;
   return 0;
 } catch (const std::exception& e) { return fail(c, std::string("gfh_set_model: ") + e.what()); }
 
@@ -1159,7 +1129,7 @@ int gfh_model_prepare(gfh_ctx* c, int n_act, const int32_t* active) {
   int rc = get_kernels(c, a, false);
   const bool combos[2][2] = {{false, false}, {true, false}};
   for (int k = 0; k < 2 && !rc; k++) {
-    c->gen.store_j = combos[k][0] || !c->fused || c->model.has_integrals() || n_act > fused_max_active(c->gen); c->gen.store_res = combos[k][1];
+    c->gen.store_j = combos[k][0] || !c->fused || c->model.has_integrals() || n_act > kFusedMaxActive; c->gen.store_res = combos[k][1];
     rc = get_kernels(c, a, false);
   }
   c->gen.store_j = sj; c->gen.store_res = sr;
@@ -1203,7 +1173,7 @@ static int upload_pars(gfh_ctx* c, const double* pars) {
 // sweep's small workgroups (cfg 4: 2.39 ms fused against 1.77 + 0.02 ms).
 static bool fusable_model(const gfh_ctx* c) { return !(c->has_model && c->model.has_integrals()); }
 static bool use_fused(const gfh_ctx* c) {
-  return c->fused && fusable_model(c) && (int)c->cur_active.size() <= fused_max_active(c->gen) && c->cur && c->cur->sweep_gram;
+  return c->fused && fusable_model(c) && (int)c->cur_active.size() <= kFusedMaxActive && c->cur && c->cur->sweep_gram;
 }
 
 extern "C++" { namespace gfh {
@@ -1216,7 +1186,7 @@ bool uses_fused_kernel(const gfh_ctx* c) { return use_fused(c); }
 // sums like the value-only pass).  Pinned by test_chi2_is_bitwise_the_sweeps_sum_of_squares*.
 bool sweep_chi2_is_bitwise(const gfh_ctx* c) {
   if (use_fused(c)) return true;
-  return c->cur && c->cur_active.size() <= 8 && fused_waves_for((int)c->cur_active.size(), c->gen) == 8 && !c->gen.finite_diff;
+  return c->cur && c->cur_active.size() <= 8 && fused_waves_for((int)c->cur_active.size()) == 8 && !c->gen.finite_diff;
 }
 } }
 
@@ -1338,7 +1308,7 @@ static int launch_model_sweep_gram(gfh_ctx* c, int tail_mode = 0, unsigned long 
   int ps = gram_partial_stride(c->cur_T); void* stp = c->status.p; void* tl = c->tail_dev.p;
   void* ax = c->aux.p; long long lda = c->n_slots;
   void* args[] = {&x, &y, &w, parg, &gs, &gn, &gd, &res, &J, &ldj, &part, &ps, &stp, &ax, &lda, &tl, &seq, &tail_mode};
-  const int fw = fused_waves_for((int)c->cur_active.size(), c->gen);
+  const int fw = fused_waves_for((int)c->cur_active.size());
   HIPCHK(c, hipModuleLaunchKernel(c->cur->sweep_gram, c->n_gb, 1, 1, 64 * fw, 1, 1, lds_pad, c->stream, args, nullptr));
   return 0;
 }
@@ -1347,9 +1317,9 @@ static int launch_model_sweep_gram(gfh_ctx* c, int tail_mode = 0, unsigned long 
 // visibility, table).  Up to 16 active parameters two workgroups of the fused kernel fit a CU's LDS (and the kernel wants
 // them: padding it down to one costs 15 % at cfg 2); those models keep the three-launch chain.
 static long fused_lds_bytes(const gfh_ctx* c) {
-  const int na = (int)c->cur_active.size(), fw = fused_waves_for(na, c->gen);
+  const int na = (int)c->cur_active.size(), fw = fused_waves_for(na);
   if (na <= kValuGramMax) return (fw + 1) * (na * (na + 1) / 2 + na + 1) * 8 + 273 * 8 + 64;      // the VALU path: the cross-wave reduction and the image
-  return fused_lds_bytes_for(na, fw, c->gen);
+  return fused_lds_bytes_for(na, fw);
 }
 static bool tail_one_workgroup_per_cu(const gfh_ctx* c) { return fused_lds_bytes(c) > 80 * 1024; }
 // Grids of at most 256 workgroups (one per CU at most) may take the tail with <= 16 parameters too: a dynamic LDS pad makes
@@ -1408,7 +1378,7 @@ static int launch_model_chi2(gfh_ctx* c, int tail_mode, unsigned long long seq, 
   void* out = c->vec.p; void* hout = c->h_pinned; void* hflag = c->h_flag; void* cnt = c->status.as<char>() + 24;
   void* mesh = c->mesh.p;
   void* ord = c->order_on && c->order_ready && !c->gen.finite_diff && mesh_sites(c->model) > 0 ? c->gb_order.p : nullptr; void* cst = nullptr;
-  const int cw = c->cur->n_active <= fused_max_active(c->gen) ? fused_waves_for(c->cur->n_active, c->gen) : 8;     // GFH_CW of the generated source
+  const int cw = c->cur->n_active <= kFusedMaxActive ? fused_waves_for(c->cur->n_active) : 8;     // GFH_CW of the generated source
   int grid; if (wsg_grid(c, c->cur->chi2, 64 * cw, c->n_gb, &grid)) return 1;
   void* pool = c->wsg.p;
   std::vector<void*> args{&x, &y, &w, parg, &gs, &gn, &gd, &res, &part, &stp, &ax, &lda, &dfg, &nd, &out, &hout, &hflag, &cnt, &seq, &tail_mode};
@@ -1527,7 +1497,7 @@ static int ensure_mesh(gfh_ctx* c) {
 static int prepare_active(gfh_ctx* c, const int32_t* active, int na, const int32_t* jac, int dim) {
   if (na < 1) return fail(c, "There are no active parameters.");
   if (check_aux(c) || ensure_gb_partition(c)) return 1;
-  if ((na > fused_max_active(c->gen) || (c->has_model && c->model.has_integrals())) && !c->gen.store_j)
+  if ((na > kFusedMaxActive || (c->has_model && c->model.has_integrals())) && !c->gen.store_j)
     set_store_j(c, true);   // beyond 4 tiles, and for quadrature models, STEP 2 is a separate pass over the stored Jacobian
   // fast path of the LM loop: the same active set, column map and kernels as in the previous call
   if (c->cur && c->prepared && c->cur == c->prepared_cur && dim == c->cur_dim && (int)c->cur_active.size() == na && c->prepared_store_j == c->gen.store_j &&

@@ -713,20 +713,6 @@ __global__ void k_status_slot(const int* __restrict__ status, double* __restrict
   dst[0] = st == 0 ? 0.0 : st == 1 ? 1.0 : st == 2 ? 4096.0 : 16777216.0;
 }
 
-// Keeps the part busy between an upload and the first pass of a fit (context.cpp, gfh_set_data_begin): after an idle gap the
-// first ~40 launches of a series run 20-35 % slower (clock ramp, tools/probes/transient.py), and any kernel work ends that.  FP64
-// arithmetic on registers for `rounds` x 256 FMAs per lane, one load per lane; the result leaves only if it is a NaN's NaN.
-__global__ __launch_bounds__(256) void k_keep_warm(const double* __restrict__ x, i64 n, int rounds, double* __restrict__ sink) {
-  const i64 i = ((i64)blockIdx.x * 256 + threadIdx.x) % (n > 0 ? n : 1);
-  double a = x[i], b = 1.0 + 1e-9 * a;
-  for (int r = 0; r < rounds; r++) {
-#pragma unroll 16
-    for (int k = 0; k < 256; k++) a = __builtin_fma(a, b, 1e-30);
-    b = 2.0 - b;
-  }
-  if (a != a && b != b) sink[0] = a;
-}
-
 // Pad slots of the device layout (every dataset's range is padded to whole tiles): a real abscissa of the same dataset (so f stays
 // finite), y = 0, w = 0, is_pad = 1.  One workgroup per dataset; seg[d] = {first slot, number of real points, end slot}.
 __global__ __launch_bounds__(256) void k_fill_pads(const i64* __restrict__ seg, double* __restrict__ x, double* __restrict__ y,
@@ -855,11 +841,6 @@ hipError_t launch_publish(hipStream_t st, const double* src, int n, const int* s
 
 hipError_t launch_status_slot(hipStream_t st, const int* status, double* dst) {
   hipLaunchKernelGGL(k_status_slot, dim3(1), dim3(1), 0, st, status, dst);
-  return hipGetLastError();
-}
-
-hipError_t launch_keep_warm(hipStream_t st, const double* x, i64 n, int rounds, double* sink) {
-  hipLaunchKernelGGL(k_keep_warm, dim3(256 * 8), dim3(256), 0, st, x, n, rounds, sink);
   return hipGetLastError();
 }
 
