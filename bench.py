@@ -11,24 +11,32 @@ One "step" = one LM iteration of gfh_fit, the library's gadf_fit main loop (gadf
   chi2 at the trial parameters (+ its all-reduce) -> accept/reject and lambda update.
 The timed region runs whole fits of FIT_ITERS iterations each (max_iter exit, no other
 convergence test), every fit from the same 5 %-off start values, so the K timed iterations are
-iterations of a fit in progress (accepted steps) and not of a converged one.  Two schedules
-are timed back to back, K iterations each:
-  * look-ahead (library default, `value`): the trial chi2 is the sum r^2 the fused sweep returns
-    at the trial point, and an accepted step hands that sweep to the next iteration -- one
-    N-sized pass per accepted iteration (gadfit_hip.h, gfh_set_lookahead);
-  * reference schedule (`reference_schedule`): chi2() kernel at the trial point, then the sweep
-    of the same point in the next iteration, exactly the reference's sequence of passes.
-Further legs, reported beside `value` and never as `value`: the look-ahead schedule without the
-Jacobian store (`jacobian_not_kept`), with geodesic acceleration (`accelerated_fit`), the first iterations after
-an idle gap (`cold_start`), and `setup`: host-clock milliseconds of every step from a fresh context to the end of a
-first fit, and of the first `gadf_fit` of the same workload through the Fortran API with its phases.
+iterations of a fit in progress (accepted steps) and not of a converged one.  The main leg, the one
+`value` is taken from, runs the look-ahead schedule (library default): the trial chi2 is the sum r^2
+the fused sweep returns at the trial point, and an accepted step hands that sweep to the next
+iteration -- one N-sized pass per accepted iteration (gadfit_hip.h, gfh_set_lookahead).
 Inputs are resident in HBM before the timed region.  `value` = data points x LM iterations
 per second over the whole job; `lm_iters_per_s` is the same thing per iteration.
 Steady state: after an idle gap the part's power management slows launches ~3-40 of a back-to-back
 series by up to 35 % (tools/probes/transient.py), so PRE_ROLL untimed iterations run before the first
 timed leg, on top of --warmup; the timed region is exactly K iterations (`config.pre_roll_steps`).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--points P] [--dump-outputs DIR]
+A plain run does only what `value` needs: set-up, warm-up, the pre-roll, the main leg, --dump-outputs, the line.  The
+pre-roll starts after a 0.5 s idle gap, and a 1 GiB device-to-device copy runs right before the main leg; `value` is
+measured in the state they leave, so every run makes them and reports what they measure (`cold_start`,
+`roofline.copy_GBps_before_main_leg`).
+--full adds everything else, reported beside `value` and never as `value`:
+  * the same K iterations on the reference schedule (`reference_schedule`): chi2() kernel at the trial point, then the
+    sweep of the same point in the next iteration, exactly the reference's sequence of passes;
+  * the look-ahead schedule without the Jacobian store (`jacobian_not_kept`), with geodesic acceleration
+    (`accelerated_fit`), a fit that rejects trial steps (`rejecting_fit`), an untimed leg with events around every stage
+    (the gram / reduce / all-reduce times of `kernels_ms`), the copy rate after all legs (`roofline.copy_GBps_measured_on_this_box`);
+  * one GPU: `setup` (host-clock milliseconds of every step from a fresh context to the end of a first fit, and of the
+    first `gadf_fit` of the same workload through the Fortran API with its phases), BASELINE configs 2-4 (`configs`), and
+    the CPU baselines (`cpu_baseline*`, --cpu-sample);
+  * N > 1 ranks: the self-check legs (`multi_gpu_parity`, `allreduce_us`, `strong_leg`, `host_sum_leg`; --multi).
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--points P] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...     (one process per GPU, RCCL)
   python bench.py --gpus N          (no launcher: one process, N member threads of the library's device group, sums by RCCL)
 The main leg times exactly K iterations, bracketed by the barrier + synchronize pair: `ms_per_step` is that region over K.
@@ -194,17 +202,23 @@ def main():
     ap.add_argument('--pre-roll', type=int, default=PRE_ROLL, help='untimed iterations before the first timed leg (power-state settle)')
     ap.add_argument('--points', type=int, default=10_000_000, help='data points per GPU')
     ap.add_argument('--strong', action='store_true', help='strong scaling: --points is the TOTAL over all GPUs (default: per GPU, weak)')
-    ap.add_argument('--legs', choices=['all', 'main', 'configs'], default='all', help="'main': only the look-ahead leg that `value` is taken from "
-                    "(profiling: the kernel trace then holds warm-up + pre-roll + exactly K timed iterations)")
-    ap.add_argument('--cpu-sample', type=int, default=1_000_000, help='points of the cpu_baseline sample (0 = skip)')
+    ap.add_argument('--full', action='store_true', help='also run every leg beside `value`: other schedules and store modes, setup, BASELINE '
+                    'configs 2-4, CPU baselines, the self-checks of an N > 1 line (see the docstring); off: the main leg alone')
+    ap.add_argument('--legs', choices=['all', 'main', 'configs'], default='all', help="with --full: 'main' = without the other schedules and "
+                    "store modes, the stage-timing and rejecting-fit legs, setup and configs; 'configs' = only BASELINE configs 2-4")
+    ap.add_argument('--cpu-sample', type=int, default=1_000_000, help='with --full: points of the cpu_baseline sample (0 = skip)')
     ap.add_argument('--min-timed', type=float, default=MIN_TIMED_S, help='repeat the main leg until this many seconds are timed (0: one repeat)')
-    ap.add_argument('--multi', choices=['auto', 'on', 'off'], default='auto', help="the self-check legs of an N > 1 line (multi_gpu_parity, allreduce_us, "
-                    "strong_leg, host_sum_ms_per_step): 'auto' = whenever more than one rank runs; 'on' also with one rank behind a communicator (rehearsal)")
-    ap.add_argument('--only-config', type=int, default=None, help="with --legs configs: 2, 3 or 4 (one configuration per kernel trace)")
-    ap.add_argument('--dry', action='store_true', help='print the schema of the multi-GPU line from a device group of compile-only members (no GPU needed)')
+    ap.add_argument('--multi', choices=['auto', 'on', 'off'], default='auto', help="with --full: the self-check legs of an N > 1 line (multi_gpu_parity, "
+                    "allreduce_us, strong_leg, host_sum_ms_per_step): 'auto' = whenever more than one rank runs; 'on' also with one rank behind a "
+                    "communicator (rehearsal)")
+    ap.add_argument('--only-config', type=int, default=None, help="with --full --legs configs: 2, 3 or 4 (one configuration per kernel trace)")
+    ap.add_argument('--dry', action='store_true', help='print the schema of the multi-GPU --full line from a device group of compile-only members '
+                    '(no GPU needed)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed fit of the main leg returned (parameters, chi2, '
                     'lambda) as float64 DIR/<name>.npy')
     args = ap.parse_args()
+    if not args.full and (args.legs == 'configs' or args.multi == 'on'):
+        ap.error('--legs configs and --multi on ask for legs that only --full runs')
     if args.dry:
         return dry_line(args)
 
@@ -366,7 +380,8 @@ def main():
             steps(args.pre_roll - n_cold)
     # how fast the fused kernel's store stream runs depends on the card and on the pages behind the Jacobian buffer (DESIGN.md
     # section 3, placement); a plain
-    # device-to-device copy right before the timed leg is reported beside the roofline line as a second reference
+    # device-to-device copy right before the timed leg is reported beside the roofline line as a second reference.  Every run makes
+    # this copy, --full or not: `value` is measured in the state it leaves (without it the first launches of the timed leg run faster)
     copy_before = copy_rate(20) if rank == 0 else None
     # main leg: K timed iterations per repeat; `value` is the median repeat
     reps = []
@@ -387,7 +402,7 @@ def main():
             np.save(os.path.join(args.dump_outputs, name + '.npy'), np.asarray(a, dtype=np.float64))
     n_allreduce_main = ctx.comm_info()[1]
     state_chi2 = counts['r'].chi2
-    extra = args.legs == 'all'
+    extra = args.full and args.legs == 'all'
     dt_ref = dt_nj = dt_acc = float('nan'); tm_ref = tm_nj = tm_detail = tm; counts_ref = counts_nj = counts_acc = counts; ctx_source_sha1 = None
     if extra:
         # the reference's schedule of passes, same K iterations, for comparison (not `value`)
@@ -441,11 +456,11 @@ def main():
     # tm: HIP-event device times accumulated over the timed steps, this rank's stream
 
 
-    # ---- N > 1: the line proves itself.  The first run on several cards is also the first execution of RCCL over
+    # ---- N > 1: the --full line proves itself.  The first run on several cards is also the first execution of RCCL over
     # more than one rank, so every such line carries: (a) the all-reduced sums against the rank-ordered host sum of the ranks' own
     # partials and a 10-iteration fit against a one-rank fit of the same points; (b) the measured latency of the all-reduce itself;
     # (c) the same iterations with the device group's ordered host sum; (d) a strong-scaling leg at --points in total.
-    do_multi = args.multi == 'on' or (args.multi == 'auto' and world > 1)
+    do_multi = args.full and (args.multi == 'on' or (args.multi == 'auto' and world > 1))
     mg = None
     placement_ms = ctx.placement(); placement_copy_GBps = ctx.placement_copy_GBps()      # (of the main leg's Jacobian buffer: the legs below change the data)
     if do_multi:
@@ -742,7 +757,7 @@ def main():
     # oracle/ref_cxx_driver.cpp, whose per-point loop is lm_solver.cpp:286-346, 513-529) -- kind "reference" -- wherever that file
     # travelled with the snapshot; the oracle (C restatement of the Fortran side, kind "port") is timed beside it on the same
     # sample, and the build container's calibration of the two (tools/calibrate_cpu_baseline.py) is read from the committed file.
-    if rank == 0 and world == 1 and args.cpu_sample > 0:      # N = 1 only: the scaling runs do not re-time the host
+    if rank == 0 and world == 1 and args.full and args.cpu_sample > 0:      # N = 1 only: the scaling runs do not re-time the host
         from oracle import binding as orc
         from oracle import refcxx
         ns = args.cpu_sample
@@ -799,7 +814,7 @@ def main():
             out['cpu_baseline'] = port
     # all host cores: one process per core, each an "image" with its contiguous share of a bounded
     # sample (the reference's own parallel model, gadfit.F90:977-1002); started together, timed to the last finisher
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if rank == 0 and world == 1 and args.full and args.cpu_sample > 0:
         import subprocess
         cores = max(1, min(_cpu_share(), 128))
         per = max(50_000, args.cpu_sample // 4)

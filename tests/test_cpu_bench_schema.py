@@ -1,4 +1,4 @@
-"""The N > 1 bench line must prove itself (cross-rank parity, measured all-reduce latency, host-sum leg, strong leg): its schema
+"""The N > 1 `bench.py --full` line must prove itself (cross-rank parity, measured all-reduce latency, host-sum leg, strong leg): its schema
 is pinned here on a device group of compile-only members, which runs without a GPU (`bench.py --dry`).  The GPU tests
 (test_gpu_device_group.py, test_gpu_parity.py) fill the same keys with measured values on one card."""
 import json
@@ -37,6 +37,14 @@ def test_dry_line_has_every_key_of_the_multi_gpu_line():
     # the dry members' sum went through the group's real host sum: bitwise the rank-ordered sum
     assert mp['cross_rank_sum_path'] == 'host' and mp['ok'] and max(mp['sums_vs_ordered_host_sum']['max_dev'].values()) == 0.0
     assert d['value'] is None and d['strong_leg'] is None and d['host_sum_ms_per_step'] is None      # nothing that needs a kernel is made up
+
+
+def test_legs_of_the_full_run_need_full():
+    """a plain run is the main leg alone: asking for a leg that only --full runs fails before anything starts"""
+    for extra in (['--legs', 'configs'], ['--legs', 'configs', '--only-config', '2'], ['--multi', 'on']):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1'] + extra, capture_output=True, text=True,
+                           timeout=300, cwd=ROOT)
+        assert p.returncode == 2 and 'only --full runs' in p.stderr, (extra, p.stdout[-2000:] + p.stderr[-3000:])
 
 
 def test_parity_verdict_follows_the_tolerances():

@@ -181,7 +181,7 @@ def test_bench_launcherless_multi_gpu_path_on_one_card():
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     args = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '1', '--pre-roll', '0',
-            '--points', '150000', '--cpu-sample', '0', '--min-timed', '0', '--legs', 'main']
+            '--points', '150000', '--cpu-sample', '0', '--min-timed', '0', '--legs', 'main', '--full']
     env = dict(os.environ)
     for k in ('WORLD_SIZE', 'RANK', 'GADFIT_HIP_GROUP_WRAP', 'GADFIT_HIP_GROUP_REDUCE'):
         env.pop(k, None)
@@ -305,7 +305,7 @@ def test_large_workspaces_from_several_contexts_of_one_card():
 
 
 def test_bench_multi_gpu_line_proves_itself_on_one_card():
-    """Eight members on the one card (GADFIT_HIP_GROUP_WRAP, ordered host sum): the N > 1 line carries its own cross-rank checks --
+    """Eight members on the one card (GADFIT_HIP_GROUP_WRAP, ordered host sum): the N > 1 --full line carries its own cross-rank checks --
     the summed [JTJ | JTres | chi2] against the rank-ordered sum of the members' partials, a 10-iteration fit against a one-rank
     fit, the measured latency of one sum, a strong-scaling leg -- and the run fails when they fail (tests/test_cpu_bench_schema.py
     pins the schema on dry members)."""
@@ -313,7 +313,7 @@ def test_bench_multi_gpu_line_proves_itself_on_one_card():
     from tests.test_cpu_bench_schema import check_multi_block
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     args = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '8', '--steps', '4', '--warmup', '1', '--pre-roll', '0',
-            '--points', '120000', '--cpu-sample', '0', '--min-timed', '0', '--legs', 'main']
+            '--points', '120000', '--cpu-sample', '0', '--min-timed', '0', '--legs', 'main', '--full']
     env = dict(os.environ, GADFIT_HIP_GROUP_WRAP='1', GADFIT_HIP_GROUP_REDUCE='host')
     for k in ('WORLD_SIZE', 'RANK'):
         env.pop(k, None)

@@ -417,7 +417,8 @@ def test_bench_distributed_path_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     p = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1',
                         '--master-addr', '127.0.0.1', '--master-port', '29533', os.path.join(root, 'bench.py'),
-                        '--gpus', '1', '--steps', '3', '--warmup', '1', '--points', '200000', '--cpu-sample', '0', '--min-timed', '0.05', '--multi', 'on'],
+                        '--gpus', '1', '--steps', '3', '--warmup', '1', '--points', '200000', '--cpu-sample', '0', '--min-timed', '0.05', '--multi', 'on',
+                        '--full'],
                        capture_output=True, text=True, timeout=900, cwd=root)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     line = [ln for ln in p.stdout.splitlines() if ln.startswith('{')][-1]
@@ -437,17 +438,19 @@ def test_bench_distributed_path_on_one_gpu():
 def test_bench_steps_and_dumped_outputs(tmp_path):
     """bench.py --steps K times exactly K iterations, and --dump-outputs writes what the last timed fit returned: with K = 13 the
     timed region is a 10- and a 3-iteration fit from the start values, so the dumped parameters, chi2 and lambda are those of a
-    3-iteration fit of the same seeded points."""
+    3-iteration fit of the same seeded points.  Without --full the run has no leg beside the main one."""
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     n = 200000
     out = str(tmp_path / 'dump')
     p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '13', '--warmup', '1', '--pre-roll', '0',
-                        '--points', str(n), '--cpu-sample', '0', '--legs', 'main', '--dump-outputs', out],
+                        '--points', str(n), '--dump-outputs', out],
                        capture_output=True, text=True, timeout=900, cwd=root)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith('{')][-1])
     assert d['steps'] == 13 and d['repeats']['n'] == 1 and d['passes_in_timed_region']['iterations'] == 13 and d['ms_per_step'] > 0
+    assert all(d[k] is None for k in ('reference_schedule', 'jacobian_not_kept', 'accelerated_fit', 'rejecting_fit'))
+    assert d['roofline']['copy_GBps_measured_on_this_box'] is None and not {'setup', 'configs', 'cpu_baseline', 'multi_gpu_parity'} & set(d)
     got = {k: np.load(os.path.join(out, k + '.npy')) for k in ('parameters', 'chi2', 'lambda')}
     assert sorted(os.listdir(out)) == ['chi2.npy', 'lambda.npy', 'parameters.npy']
     assert all(a.dtype == np.float64 for a in got.values()) and got['parameters'].shape == (1, 32)
