@@ -1,0 +1,354 @@
+// active.cpp -- model, kernels and active set: the model a context fits (gfh_set_model*), the generated kernels of an active set
+// (get_kernels: generate, compile, load, cache), the layout of the packed image the ranks sum (PackedLayout), and prepare_active, which
+// sizes every buffer a pass of that active set needs.  It launches nothing and owns no timing; buffers come from devmem.cpp.
+#include "context_internal.h"
+#include "group.h"
+#include <algorithm>
+#include <cstring>
+#include <exception>
+
+using namespace gfh;
+
+// ------------------------------------------------------------------------- model
+// The quadrature workspaces the next kernels carry (model.h, plan_workspaces): the fast form in scratch, or the user's sizes -- in
+// scratch while they fit the budget, else in the context's global pool.
+void gfh::apply_ws_plan(gfh_ctx* c) {
+  const gfh::WsPlan p = gfh::plan_workspaces(c->model, c->ws.fast, c->ws.grown);
+  c->gen.ws_size = p.ws_size; c->gen.ws_size_inner = p.ws_size_inner; c->gen.ws_global = p.global;
+  const int64_t wave = p.global ? gfh::wsg_wave_doubles(c->model, p.ws_size, p.ws_size_inner) : 0;
+  if (wave != c->ws.wave_doubles) {          // (another slot size: the pool is cut anew at the next launch that needs it)
+    if (c->ws.wsg.p && c->device >= 0) { hipSetDevice(c->device); if (c->stream) hipStreamSynchronize(c->stream); dev_free(c->ws.wsg); }
+    c->ws.waves = 0; c->ws.tried = 0; c->ws.wave_doubles = wave;
+  }
+}
+
+constexpr int kMaxKernargPars = 480;   // doubles; the kernel-argument segment holds 4 KiB
+
+static int get_kernels_variant(gfh_ctx* c, const std::vector<int32_t>& active, bool load, int kernarg_pars) {
+  // loaded kernels are keyed by the active set and the generator options that can change per context
+  std::vector<int32_t> key = active;
+  key.push_back(-1 - c->gen.loss - 4 * (c->gen.finite_diff ? 1 : 0) - 8 * (c->gen.store_j ? 0 : 1) - 16 * (c->gen.store_res ? 0 : 1) - 32 * kernarg_pars);
+  key.push_back(-1 - c->gen.ws_size); key.push_back(-1 - c->gen.ws_size_inner); key.push_back(c->gen.ws_global ? -2 : -1);
+  key.push_back(c->gen.finite_diff && c->gen.fd_col_sets ? -2 : -1);
+  auto it = c->kernel_cache.find(key);
+  if (it != c->kernel_cache.end()) { c->cur = &it->second; return 0; }
+  std::string src, err;
+  GenConfig cfg = c->gen; cfg.kernarg_pars = kernarg_pars;
+  if (!generate_source(c->model, active, cfg, &src, &err)) return fail(c, err);
+  ModelKernels mk;
+  const uint64_t skey = load ? source_key(src) : 0;
+  if (!(load && acquire_loaded(c->device, skey, &mk))) {       // (a code object this process already has loaded on this card: rtc.h)
+    std::vector<char> code; bool cached = false;
+    if (!compile_to_code_object(src, &code, &err, &cached)) return fail(c, err);
+    if (!load) return 0;
+    if (!load_kernels(code, &mk, &err)) return fail(c, err);
+    publish_loaded(c->device, skey, mk);
+  }
+  mk.kernarg_pars = kernarg_pars; mk.n_active = (int)active.size();
+  c->cur = &c->kernel_cache.emplace(key, mk).first->second;
+  return 0;
+}
+
+int gfh::get_kernels(gfh_ctx* c, const std::vector<int32_t>& active, bool load) {
+  if (!c->has_model) return fail(c, "no model set (gfh_set_model)");
+  const int np = c->model.n_pars;
+  const bool can = c->kernarg && np >= 1 && np <= kMaxKernargPars;
+  if (c->device < 0 && !c->nd) {          // compile-only context without data: the one-dataset and the pointer form go to the cache
+    if (can && get_kernels_variant(c, active, load, np)) return 1;
+    return get_kernels_variant(c, active, load, 0);
+  }
+  // the whole [n_datasets][n_pars] block by value while it fits the kernel-argument segment
+  const bool fits = can && c->nd >= 1 && (int64_t)c->nd * np <= kMaxKernargPars;
+  return get_kernels_variant(c, active, load, fits ? c->nd * np : 0);
+}
+
+int gfh::check_aux(gfh_ctx* c) {
+  if (c->has_model && c->model.n_aux > c->n_aux)
+    return fail(c, "the model reads " + std::to_string(c->model.n_aux) + " auxiliary per-point column(s); call gfh_set_aux after gfh_set_data");
+  return 0;
+}
+
+// What the ranks all-reduce after a sweep is the image `packed`: [JTJ (dim*dim, column-major) | JTres | chi2], or for global
+// fits beyond the in-kernel tail's reach the pattern-only [nnz values | JTres | chi2].  ncclAllReduce needs the same length
+// and the same meaning of every element on every rank, so the layout may depend only on what all ranks share -- the column
+// map, dim, the number of datasets -- never on which points (or whether any) THIS rank holds.  Host-only: also what
+// gfh_debug_packed_layout reports for compile-only contexts (CPU tests of the multi-rank bookkeeping).
+struct PackedLayout {
+  std::vector<int> inv, owner, nz_row, nz_col;
+  bool sparse = false;         // the pattern is a quarter of the dense image or less
+  bool small = false;          // dim*dim*n_datasets <= 65536: dense image, assembled by the fused kernel's tail where it applies
+  int nnz = 0;
+  bool transfer_sparse() const { return sparse && !small; }
+  size_t packed_n(int dim) const { return transfer_sparse() ? (size_t)nnz + dim + 1 : (size_t)dim * dim + dim + 1; }
+};
+
+static int compute_layout(gfh_ctx* c, int nd, int na, const int32_t* jac, int dim, bool sparse_ok, PackedLayout* L) {
+  L->inv.assign((size_t)nd * dim, -1);
+  for (int d = 0; d < nd; d++)
+    for (int k = 0; k < na; k++) {
+      const int col = jac[d * na + k];
+      if (col < 0 || col >= dim) return fail(c, "Jacobian index out of range");
+      L->inv[(size_t)d * dim + col] = k;
+    }
+  // owner[col]: the single dataset that uses column col (local parameter) or -1 (several: global parameter)
+  L->owner.assign(dim, -1);
+  std::vector<int> users(dim, 0);
+  for (int d = 0; d < nd; d++) for (int k = 0; k < na; k++) { const int col = jac[d * na + k]; if (users[col]++ == 0) L->owner[col] = d; }
+  for (int col = 0; col < dim; col++) if (users[col] != 1) L->owner[col] = -1;
+  if (nd == 1) std::fill(L->owner.begin(), L->owner.end(), 0);
+  // pattern of the normal equations: (row <= col) pairs of columns that share a dataset, column-major order
+  L->sparse = false; L->nnz = 0; L->nz_row.clear(); L->nz_col.clear();
+  L->small = (int64_t)dim * dim * nd <= 65536;
+  if (sparse_ok && nd > 1) {
+    // the (row <= col) pairs some dataset couples, in column-major order (sorted keys: a dim x dim map costs 16 MB and 8e6 tests
+    // per call at the 4003 columns of a 1000-curve fit)
+    std::vector<int64_t> keys;
+    keys.reserve((size_t)nd * na * (na + 1) / 2);
+    for (int d = 0; d < nd; d++)
+      for (int k = 0; k < na; k++) for (int m = 0; m < na; m++) {
+        const int r_ = jac[d * na + k], c_ = jac[d * na + m];
+        if (r_ <= c_) keys.push_back((int64_t)c_ * dim + r_);
+      }
+    std::sort(keys.begin(), keys.end());
+    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+    for (const int64_t key : keys) { L->nz_row.push_back((int)(key % dim)); L->nz_col.push_back((int)(key / dim)); }
+    L->nnz = (int)L->nz_row.size();
+    L->sparse = 4 * ((int64_t)L->nnz + dim + 1) < (int64_t)dim * dim + dim + 1;      // worth it when the pattern is a quarter or less
+  }
+  return 0;
+}
+
+// the buffer of the quadrature meshes (context.h): one record per slot and outermost integrate() call site of the model
+int gfh::ensure_mesh(gfh_ctx* c) {
+  const int sites = (c->has_model && c->disp.mesh_on && c->gen.fast_div && !c->gen.finite_diff) ? mesh_sites(c->model) : 0;
+  const int stride = sites * kMeshRecord;
+  if (stride != c->disp.mesh_stride) { c->disp.mesh_stride = stride; c->disp.mesh_valid = false; }
+  if (stride) {
+    const size_t need = (size_t)stride * (size_t)std::max<int64_t>(1, c->n_slots);
+    if (c->disp.mesh.bytes < need) { c->disp.mesh_valid = false; if (dev_alloc(c, c->disp.mesh, need)) return 1; }
+  } else dev_free(c->disp.mesh);
+  return 0;
+}
+
+int gfh::prepare_active(gfh_ctx* c, const int32_t* active, int na, const int32_t* jac, int dim) {
+  if (na < 1) return fail(c, "There are no active parameters.");
+  if (check_aux(c) || ensure_gb_partition(c)) return 1;
+  if ((na > kFusedMaxActive || (c->has_model && c->model.has_integrals())) && !c->gen.store_j)
+    set_store_j(c, true);   // beyond 4 tiles, and for quadrature models, STEP 2 is a separate pass over the stored Jacobian
+  // fast path of the LM loop: the same active set, column map and kernels as in the previous call
+  if (c->cur && c->prepared && c->cur == c->prepared_cur && dim == c->cur_dim && (int)c->cur_active.size() == na && c->prepared_store_j == c->gen.store_j &&
+      std::equal(active, active + na, c->cur_active.begin()) && c->cur_jac.size() == (size_t)c->nd * na &&
+      std::equal(jac, jac + (size_t)c->nd * na, c->cur_jac.begin()))
+    return 0;
+  c->prepared = false;
+  std::vector<int32_t> a(active, active + na);
+  if (get_kernels(c, a, true)) return 1;
+  if (ensure_tile_table(c)) return 1;
+  std::vector<int32_t> j(jac, jac + (size_t)c->nd * na);
+  const bool same = (a == c->cur_active) && (j == c->cur_jac) && dim == c->cur_dim;
+  c->cur_T = (na + 15) / 16;
+  if (!same) {
+    PackedLayout L;
+    if (compute_layout(c, c->nd, na, jac, dim, c->sparse_ok, &L)) return 1;
+    const std::vector<int>& inv = L.inv;
+    if (dev_alloc(c, c->inv, sizeof(int) * inv.size())) return 1;
+    HIPCHK(c, hipMemcpy(c->inv.p, inv.data(), sizeof(int) * inv.size(), hipMemcpyHostToDevice));
+    if (dev_alloc(c, c->owner, sizeof(int) * (size_t)dim)) return 1;
+    HIPCHK(c, hipMemcpy(c->owner.p, L.owner.data(), sizeof(int) * (size_t)dim, hipMemcpyHostToDevice));
+    c->sparse = L.sparse; c->nnz = L.nnz; c->h_nz_row = L.nz_row; c->h_nz_col = L.nz_col;
+    if (c->sparse) {
+      if (dev_alloc(c, c->nz_row, sizeof(int) * (size_t)c->nnz) || dev_alloc(c, c->nz_col, sizeof(int) * (size_t)c->nnz)) return 1;
+      HIPCHK(c, hipMemcpy(c->nz_row.p, c->h_nz_row.data(), sizeof(int) * (size_t)c->nnz, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(c->nz_col.p, c->h_nz_col.data(), sizeof(int) * (size_t)c->nnz, hipMemcpyHostToDevice));
+    }
+    // source lists for k_gather_sum: where in G (the per-dataset Gram images, [nd][gw]) the terms of every element of the packed
+    // image sit, in dataset order -- what k_assemble / k_assemble_sparse find through owner/inv at run time.  Built for the layout
+    // the launch chain will use: pattern-only [nnz values | JTres | chi2] or dense [JTJ column-major | JTres | chi2].
+    {
+      const int T = c->cur_T, gw = gram_partial_stride(T), npair = T * (T + 1) / 2;
+      const bool lay_sparse = L.transfer_sparse();
+      const int64_t n_img = (int64_t)L.packed_n(dim);
+      dev_free(c->gs_meta); c->gs_n = 0; c->gs_sparse = lay_sparse;
+      if ((int64_t)c->nd * gw < (int64_t(1) << 31) && n_img <= (int64_t(1) << 18)) {
+        std::vector<int> meta((size_t)n_img), list, terms;
+        auto put = [&](size_t idx) {
+          if (terms.empty()) meta[idx] = (int)0x80000000;
+          else if (terms.size() == 1) meta[idx] = terms[0];
+          else { meta[idx] = -((int)list.size() + 1); list.push_back((int)terms.size()); list.insert(list.end(), terms.begin(), terms.end()); }
+        };
+        auto entry = [&](int row, int col) {
+          terms.clear();
+          for (int d = 0; d < c->nd; d++) {
+            int a_ = inv[(size_t)d * dim + row], b_ = inv[(size_t)d * dim + col];
+            if (a_ < 0 || b_ < 0) continue;
+            if (a_ > b_) std::swap(a_, b_);                 // upper triangle of tile pairs is stored
+            const int ti = a_ >> 4, tj = b_ >> 4, p = ti * T - ti * (ti - 1) / 2 + (tj - ti);
+            terms.push_back(d * gw + p * 256 + (a_ & 15) * 16 + (b_ & 15));
+          }
+        };
+        const size_t nn = lay_sparse ? (size_t)c->nnz : (size_t)dim * dim;
+        if (lay_sparse) for (int k = 0; k < c->nnz; k++) { entry(c->h_nz_row[k], c->h_nz_col[k]); put((size_t)k); }
+        else for (int col = 0; col < dim; col++) for (int row = 0; row < dim; row++) { entry(row, col); put((size_t)col * dim + row); }
+        for (int row = 0; row < dim; row++) {
+          terms.clear();
+          for (int d = 0; d < c->nd; d++) { const int a_ = inv[(size_t)d * dim + row]; if (a_ >= 0) terms.push_back(d * gw + npair * 256 + a_); }
+          put(nn + row);
+        }
+        terms.clear();
+        for (int d = 0; d < c->nd; d++) terms.push_back(d * gw + npair * 256 + 16 * T);
+        put(nn + dim);
+        if (list.empty()) list.push_back(0);
+        if (dev_alloc(c, c->gs_meta, sizeof(int) * meta.size()) || dev_alloc(c, c->gs_list, sizeof(int) * list.size())) return 1;
+        HIPCHK(c, hipMemcpy(c->gs_meta.p, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->gs_list.p, list.data(), sizeof(int) * list.size(), hipMemcpyHostToDevice));
+        c->gs_n = (int)n_img;
+      }
+    }
+    c->cur_active = a; c->cur_jac = j; c->cur_dim = dim; c->have_sweep = false;
+  }
+  if (ensure_mesh(c)) return 1;
+  const int ps = gram_partial_stride(c->cur_T);
+  const size_t packed_n = (size_t)dim * dim + dim + 2;       // (+ the status slot that travels with a cross-rank sum)
+  if ((c->gen.store_j && place_jacobian(c, na)) ||
+      dev_alloc(c, c->partial, sizeof(double) * (size_t)std::max(1, c->n_gb) * ps) ||
+      dev_alloc(c, c->G, sizeof(double) * (size_t)c->nd * ps) ||
+      dev_alloc(c, c->packed, sizeof(double) * packed_n) ||
+      dev_alloc(c, c->chi2_partial, sizeof(double) * (size_t)std::max(1, c->n_gb)) ||
+      dev_alloc(c, c->vec, sizeof(double) * (size_t)(dim + 8)) ||
+      pinned_reserve(c, sizeof(double) * std::max<size_t>(packed_n + 1, 4096))) return 1;
+  c->prepared = true; c->prepared_store_j = c->gen.store_j; c->prepared_cur = c->cur;
+  return 0;
+}
+
+extern "C" {
+
+int gfh_set_model_variants(gfh_ctx* c, int n, const gfh_tape* const* t, int hint_aux) try {
+  if (!c) return 1;
+  GROUP(c, gfh_set_model_variants(k, n, t, hint_aux));
+  std::string err;
+  Model m;
+  // (per-tape hint columns left by gfh_set_variant_hint_columns for exactly this hand-over)
+  const std::vector<int32_t> cols = std::move(c->up.pending_hint_cols);
+  c->up.pending_hint_cols.clear();
+  if (!m.load_variants(n, t, hint_aux, &err, (int)cols.size() == n ? &cols : nullptr)) return fail(c, "gfh_set_model: " + err);
+  if (gfh::join_pending(c)) return 1;
+  if (c->device >= 0) { hipSetDevice(c->device); if (c->stream) hipStreamSynchronize(c->stream); for (auto& kv : c->kernel_cache) release_loaded(c->device, &kv.second); }
+  c->kernel_cache.clear(); c->cur = nullptr; c->cur_active.clear(); c->have_sweep = false; c->prepared = false;
+  c->model = std::move(m); c->has_model = true; c->model_serial++; c->disp.mesh_valid = false;
+  c->disp.order_ready = false; c->disp.order_want = true;
+  // the kernels first carry small quadrature workspaces (fast: 3.2 KB of scratch per lane and level); a pass that exhausts them is
+  // repeated with the user's sizes (grow_workspace)
+  // (a model handed over by a recovery's handler keeps the grown state: the pass that is about to be repeated has needed it)
+  c->ws.grown = c->ws.grown && c->in_recovery;
+  apply_ws_plan(c);
+  // Models with integrate(): the plain kernels are bound by VALU issue and their bodies take 135-150 VGPRs as the compiler
+  // allocates them (3 waves per SIMD; gfh_k_chi2's 8-wave workgroups then fit once per CU = 2 waves per SIMD).  Capped at 128
+  // registers (4 waves) a handful of values spill and chi2 runs 20 % faster, the sweep 4 %; at 96 (5 waves) the spills cost
+  // more than the waves bring (profiles/r03_cfg4.md).
+  c->gen.waves_per_eu = c->model.has_integrals() ? 4 : 0;
+  return 0;
+} catch (const std::exception& e) { return fail(c, std::string("gfh_set_model: ") + e.what()); }
+
+int gfh_set_model(gfh_ctx* c, const gfh_tape* t) { return gfh_set_model_variants(c, 1, &t, -1); }
+
+int gfh_set_variant_hint_columns(gfh_ctx* c, int n_tapes, const int32_t* cols) {
+  if (!c) return 1;
+  GROUP(c, gfh_set_variant_hint_columns(k, n_tapes, cols));
+  if (n_tapes < 0 || (n_tapes > 0 && !cols)) return fail(c, "gfh_set_variant_hint_columns: bad arguments");
+  c->up.pending_hint_cols.assign(cols, cols + n_tapes);
+  return 0;
+}
+
+int gfh_model_needs_hint(gfh_ctx* c) {
+  if (!c) return -1;
+  if (c->grp) return gfh_model_needs_hint(gfh::group_member(c, 0));
+  if (!c->has_model) return -1;
+  try { return c->model.needs_hint() ? 1 : 0; } catch (const std::exception&) { return -1; }
+}
+int gfh_model_n_variants(gfh_ctx* c) {
+  if (!c) return 0;
+  if (c->grp) return gfh_model_n_variants(gfh::group_member(c, 0));
+  return c->has_model ? c->model.n_variants() : 0;
+}
+int gfh_model_n_tapes(gfh_ctx* c) {
+  if (!c) return 0;
+  if (c->grp) return gfh_model_n_tapes(gfh::group_member(c, 0));
+  return c->has_model ? c->model.n_tapes : 0;
+}
+int64_t gfh_model_source(gfh_ctx* c, int n_act, const int32_t* active, char* buf, int64_t cap) {
+  if (c && c->grp) {
+    gfh_ctx* k0 = gfh::group_member(c, 0);
+    const int64_t n = gfh_model_source(k0, n_act, active, buf, cap);
+    if (n < 0) fail(c, k0->err);
+    return n;
+  }
+  if (!c || !c->has_model) { fail(c, "no model set"); return -1; }
+  std::string src, err;
+  std::vector<int32_t> a(active, active + n_act);
+  GenConfig cfg = c->gen;
+  const int np = c->model.n_pars;
+  if (c->kernarg && np >= 1 && (int64_t)std::max(1, c->nd) * np <= kMaxKernargPars) cfg.kernarg_pars = std::max(1, c->nd) * np;
+  if (!generate_source(c->model, a, cfg, &src, &err)) { fail(c, err); return -1; }
+  if (buf && cap > 0) { size_t n = std::min<size_t>((size_t)cap - 1, src.size()); memcpy(buf, src.data(), n); buf[n] = 0; }
+  return (int64_t)src.size() + 1;
+}
+
+int gfh_model_prepare(gfh_ctx* c, int n_act, const int32_t* active) {
+  if (!c) return 1;
+  GROUP(c, gfh_model_prepare(k, n_act, active));      // compiled once: rtc.cpp serialises, the other members load the cached code object
+  std::vector<int32_t> a(active, active + n_act);
+  if (c->device >= 0) return get_kernels(c, a, false);
+  // compile-only context (build time): also the forms gfh_fit switches to under keep_jacobian mode 2 -- without the Jacobian
+  // store (plain fits) and without the residual store -- so that a GPU box finds them in the cache
+  const bool sj = c->gen.store_j, sr = c->gen.store_res;
+  int rc = get_kernels(c, a, false);
+  const bool combos[2][2] = {{false, false}, {true, false}};
+  for (int k = 0; k < 2 && !rc; k++) {
+    c->gen.store_j = combos[k][0] || !c->fused || c->model.has_integrals() || n_act > kFusedMaxActive; c->gen.store_res = combos[k][1];
+    rc = get_kernels(c, a, false);
+  }
+  c->gen.store_j = sj; c->gen.store_res = sr;
+  return rc;
+}
+
+// Test hook (no GPU needed): the geometry and the layout of the all-reduced image as rank `rank` of `nranks` derives them.
+// out[0] = length of the packed image, out[1] = pattern-only transfer (0/1), out[2] = nnz, out[3] = FNV-1a hash of the
+// pattern lists and of inv/owner, out[4] = first global point of this rank, out[5] = its point count, out[6] = number
+// of datasets it holds points of, out[7] = its number of gram workgroups.  Every rank must report the same out[0..3].
+int gfh_debug_packed_layout(int nranks, int rank, int64_t n_total, int nd, const int64_t* dp, int na, const int32_t* jac, int dim,
+                            int sparse_ok, int64_t* out, int32_t* nz_row, int32_t* nz_col, int nz_cap) {
+  if (nranks < 1 || rank < 0 || rank >= nranks || !dp || !jac || !out || na < 1 || nd < 1) { set_global_error("gfh_debug_packed_layout: bad arguments"); return 1; }
+  gfh_ctx c;
+  c.nranks = nranks; c.rank = rank;
+  if (set_geometry(&c, n_total, nd, dp)) { set_global_error(c.err); return 1; }
+  PackedLayout L;
+  if (compute_layout(&c, nd, na, jac, dim, sparse_ok != 0, &L)) { set_global_error(c.err); return 1; }
+  uint64_t h = 1469598103934665603ull;
+  auto mix = [&](const std::vector<int>& v) { for (int x : v) { h ^= (uint32_t)x; h *= 1099511628211ull; } h ^= 0xffu; h *= 1099511628211ull; };
+  mix(L.nz_row); mix(L.nz_col); mix(L.inv); mix(L.owner);
+  int held = 0;
+  for (int d = 0; d < nd; d++) if (c.lb[d + 1] > c.lb[d]) held++;
+  out[0] = (int64_t)L.packed_n(dim); out[1] = L.transfer_sparse() ? 1 : 0; out[2] = L.nnz; out[3] = (int64_t)(h >> 1);
+  out[4] = c.begin; out[5] = c.count; out[6] = held; out[7] = c.n_gb;
+  for (int k = 0; k < L.nnz && k < nz_cap; k++) { if (nz_row) nz_row[k] = L.nz_row[k]; if (nz_col) nz_col[k] = L.nz_col[k]; }
+  return 0;
+}
+
+int gfh_set_active(gfh_ctx* c, const int32_t* active, int na, const int32_t* jac, int dim) {
+  GROUP(c, gfh_set_active(k, active, na, jac, dim));
+  NEED_GPU(c);
+  if (!c->nd) return fail(c, "no data set (gfh_set_data)");
+  return prepare_active(c, active, na, jac, dim);
+}
+
+int gfh_jacobian_indices(int nd, int na, const int32_t* active, const int32_t* is_global, int32_t* jac) {
+  int shift = 0;   // gadfit.F90:618-628
+  for (int i = 0; i < nd; i++)
+    for (int j = 0; j < na; j++) {
+      if (is_global[active[j]]) { jac[i * na + j] = j; if (i > 0) shift++; }
+      else jac[i * na + j] = j + i * na - shift;
+    }
+  return nd * na - shift;
+}
+
+}  // extern "C"

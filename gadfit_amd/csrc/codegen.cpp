@@ -761,7 +761,7 @@ struct Gen {
 // The per-lane interval workspace lives in scratch: GFH_WS1 intervals for outer, GFH_WS2 for inner integrals.  The reference's
 // workspaces are user-sized, default 1000 (NI:40, 114-135); typical use is << 100, so the kernels are first compiled with
 // min(100, the user's size) and a pass that exhausts that (STATUS = 1) is repeated by the host with kernels compiled at the
-// user's size before the reference's error is raised (NI:282-283; context.cpp, grow_workspace).
+// user's size before the reference's error is raised (NI:282-283; passes.cpp, grow_workspace).
 void emit_integrand_functions(const Model& m, int S, const GenConfig& cfg, std::ostringstream& s) {
   const SubTape& st = m.sub[S];
   int nip = 0;
@@ -1020,7 +1020,7 @@ void emit_integral_site(const Model& m, int I, const GenConfig& cfg, std::ostrin
 // only (every parameter passive, the reference's expression shapes: comparisons look at val alone); it returns the variant
 // whose body the lane then runs, or -1 where the point takes a turn no recording has taken yet -- the lane then reports
 // its slot and the outcomes so far (gfh_report_unseen), the host records eval() at that point along those outcomes, adds
-// the variant and repeats the pass (context.cpp, recover_unseen).
+// the variant and repeats the pass (passes.cpp, recover_unseen).
 // Where two variants part ways WITHOUT a guard (a Fortran eval() that branches on the plain real x: invisible to the
 // recorder), only the host can tell which points go where: a per-point column (Model::hint_aux) names the variant each
 // point took when the columns were tabulated, and the walk follows it at such a fork.
@@ -1617,7 +1617,7 @@ struct gfh_parg { double v[GFH_PARG]; };
          "#define GFH_MESH_NONE , (unsigned char*)nullptr, 0\n#define GFH_MESH_KPARAMS , unsigned char* __restrict__ mesh, const int mesh_mode\n";
   else
     s << "#define GFH_MESH_DECL\n#define GFH_MESH_PASS\n#define GFH_MESH_AT(i)\n#define GFH_MESH_NONE\n#define GFH_MESH_KPARAMS\n";
-  // Order of dispatch (context.cpp, build_orders): the cost of a point of a model with integrate() is the number of its bisections,
+  // Order of dispatch (launch.cpp, build_orders): the cost of a point of a model with integrate() is the number of its bisections,
   // workgroups are dispatched in index order, and x-sorted data put the expensive tiles last -- they would run alone at the end.  The
   // plain kernels of such models take the tile / block a workgroup works on from a table sorted by measured cost, expensive first;
   // the sweep measures (shader clock per tile).  Which workgroup does a tile changes no result: every sum is defined on the fixed
@@ -1838,7 +1838,7 @@ static __device__ __forceinline__ double gfh_wave_sum(double t) {
 }
 
 // (the fused kernels exist for up to 128 active parameters = 8 tiles, model.h kFusedMaxActive / fused_max_active; beyond that STEP 1 and STEP 2 run as
-// gfh_k_sweep + k_gram_block launches; models whose quadrature workspaces are the global pool never run them: context.cpp, fusable_model)
+// gfh_k_sweep + k_gram_block launches; models whose quadrature workspaces are the global pool never run them: launch.cpp, fusable_model)
 #if GFH_NA <= GFH_FUSED_MAX && !GFH_WSG
 // Fused STEP 1 + STEP 2 (gadfit.F90:675-699): the sweep above plus J^T J / J^T r / sum r^2 of
 // the same points on the FP64 matrix cores, so J is written once and never re-read.
@@ -1862,7 +1862,7 @@ static __device__ __forceinline__ double gfh_wave_sum(double t) {
 #define GFH_NH 1
 #define GFH_KS 16
 #endif
-// Descriptor of the fused kernel's tail (filled by the host, context.cpp TailDesc).
+// Descriptor of the fused kernel's tail (filled by the host, launch.cpp TailDesc).
 struct gfh_tail {
   const int* ds_first_gb;          // [nd+1] first workgroup of each dataset
   const int* inv;                  // [nd][dim] inverse of Jacobian_indices
@@ -2463,7 +2463,7 @@ void GFH_K_SWEEP_GRAM(const double* __restrict__ x, const double* __restrict__ y
     }
     if (tail_mode != 2) {
       // (one process per GPU: element `total` of the packed buffer is the status slot of the cross-rank sum that follows --
-      // 0, 1, 4096, 2^24 by code, so the sum over the ranks still tells which codes occurred: context.cpp, allreduce_sum)
+      // 0, 1, 4096, 2^24 by code, so the sum over the ranks still tells which codes occurred: comm.cpp, allreduce_sum)
       if (threadIdx.x == 0) packed[total] = GFH_STATUS_SLOT(GFH_LD_DEV(status));
       return;
     }
@@ -2700,7 +2700,7 @@ typedef const double __attribute__((address_space(4))) * gfh_cptr;
 // omega kernel (STEP 3, forward mode): a workgroup owns a CONTIGUOUS chunk of tiles.  When the whole chunk
 // lies in one dataset (always, unless a dataset boundary falls inside it) the parameter block is
 // fixed for the loop, so everything that depends on parameters only leaves the per-point code.  The host sizes
-// the grid to what is resident at once (context.cpp, resident_grid), so no workgroup waits for a second round.
+// the grid to what is resident at once (launch.cpp, resident_grid), so no workgroup waits for a second round.
 extern "C" __global__ __launch_bounds__(GFH_BLOCK) GFH_OCC
 void gfh_k_omega(const double* __restrict__ x, const double* __restrict__ w,
                  GFH_PARS_DECL, GFH_DPARS_DECL,

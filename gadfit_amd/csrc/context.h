@@ -25,8 +25,9 @@ struct UnseenEntry { long long slot; unsigned long long path; int n_guards; int 
 
 struct Group;                       // group.h: single-process device group
 
+// a device block (devmem.cpp allocates and frees them, nobody else): `bytes` as asked for, `cap` as really allocated
 struct DevBuf {
-  void* p = nullptr; size_t bytes = 0;
+  void* p = nullptr; size_t bytes = 0, cap = 0;
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
@@ -44,11 +45,13 @@ struct gfh_ctx {
   gfh::Group* member_of = nullptr;  // this context is member `rank` of that group: results are summed over the members on the host
 
   // adaptive parallelism (load_balancing of gadf_fit, gadfit.F90:672-673, 935-983): image weights of the current
-  // partition, and a host copy of the whole point array (every image of the reference holds it) to cut new ranges from
-  bool load_balancing = false;
-  std::vector<double> part_w;       // empty = 1/nranks each
-  std::vector<double> hx, hy, hw, haux; int h_n_aux = 0; int weights_type = -1;
-  double lb_t_prev = 0.0; long lb_moves = 0;
+  // partition, and a host copy of the whole point array (every image of the reference holds it) to cut new ranges from (data.cpp)
+  struct LoadBalance {
+    bool on = false;
+    std::vector<double> part_w;     // empty = 1/nranks each
+    std::vector<double> hx, hy, hw, haux; int h_n_aux = 0; int weights_type = -1;
+    double t_prev = 0.0; long moves = 0;
+  } bal;
   // data partition
   int64_t n_total = 0, begin = 0, count = 0;
   int nd = 0;
@@ -70,13 +73,15 @@ struct gfh_ctx {
   gfh::DevBuf aux; int n_aux = 0;   // auxiliary per-point columns [n_aux][n_slots] (gfh_set_aux)
   // Mesh hand-over of quadrature models (codegen.cpp, mesh_build): per slot and outermost integrate() call site the record of the
   // bisections the last recording pass made, and the parameter block it made them at.  A pass at exactly those parameters replays
-  // them instead of bisecting again: the sweep of an accepted step after the trial chi2() there, STEP 3 after the sweep.
-  gfh::DevBuf tile_cost, tile_order, gb_order;   // models with integrate(): measured cost per tile, tiles / gram blocks expensive first (build_orders)
+  // them instead of bisecting again: the sweep of an accepted step after the trial chi2() there, STEP 3 after the sweep.  (launch.cpp)
+  struct Dispatch {
+    gfh::DevBuf tile_cost, tile_order, gb_order;   // models with integrate(): measured cost per tile, tiles / gram blocks expensive first (build_orders)
+    bool order_on = true, order_ready = false, order_want = false, order_measured = false; int order_age = 0;
+    gfh::DevBuf mesh; int mesh_stride = 0;
+    std::vector<double> mesh_pars; bool mesh_valid = false, mesh_on = true;   // GADFIT_HIP_MESH (0: every pass bisects)
+    long n_mesh_replays = 0;
+  } disp;
   int n_integrand_rounds = 0;          // passes repeated in a row because an integrand met an unrecorded path (recover_integrand_path)
-  bool order_on = true, order_ready = false, order_want = false, order_measured = false; int order_age = 0;
-  gfh::DevBuf mesh; int mesh_stride = 0;
-  std::vector<double> mesh_pars; bool mesh_valid = false, mesh_on = true;   // GADFIT_HIP_MESH (0: every pass bisects)
-  long n_mesh_replays = 0;
   gfh::DevBuf partial, G, chi2_partial, packed, pars, dpars, inv, dl, vec, status;
   int* h_status = nullptr;          // pinned, host-coherent 64 B: the result mailbox's flag lives at byte 8
   unsigned long long* h_flag = nullptr;   // sequence number of the last published result (k_publish)
@@ -95,18 +100,24 @@ struct gfh_ctx {
   // Quadrature workspaces beyond the scratch budget (GenConfig::ws_global): the context's pool in global memory, one slot of
   // wsg_wave_doubles per wave of a launch; the launchers cap their grids at the slots there are.  Allocated at the first launch that
   // needs it (hipMalloc: a failure is an error code, not the runtime's abort), freed by gfh_destroy / when the model changes its sizes.
-  gfh::DevBuf wsg; int64_t wsg_waves = 0, wsg_wave_doubles = 0;
-  int64_t wsg_tried = 0;             // the largest number of slots the pool was last ASKED for (the card may have granted fewer: wsg_waves): not asked again until more are wanted
-  bool ws_grown = false;            // a pass has exhausted the fast workspaces: the kernels carry the user's sizes (kept through a recovery's new model)
-  bool in_recovery = false;         // the unseen-branch handler is running (gfh_set_model_variants then keeps ws_grown)
-  int ws_fast = 100;                // quadrature workspace the kernels carry first (GADFIT_HIP_WS_FAST; 0: the user's size from the start)
-  std::thread pending;              // gfh_set_data_begin: the upload in flight (joined by the next call on this context)
-  std::vector<int32_t> pending_hint_cols;   // gfh_set_variant_hint_columns: consumed by the next gfh_set_model_variants
-  bool creating = false;      // `pending` is the device part of gfh_create_begin (not an upload): gfh_set_data_begin chains its upload behind it
-  bool create_failed = false; std::string create_err;      // ... and it failed: every call that needs the device fails with its message
-  int pending_rc = 0;
-  void* hc_dst = nullptr; const void* hc_src = nullptr; size_t hc_bytes = 0;   // gfh_queue_host_copy: a host-side copy made beside the next upload
-  std::thread host_copy;               // ... on a thread of its own (gfh_wait_host_copy joins it)
+  // (cut by launch.cpp, wsg_grid; sized by active.cpp, apply_ws_plan)
+  struct WsPool {
+    gfh::DevBuf wsg; int64_t waves = 0, wave_doubles = 0;
+    int64_t tried = 0;              // the largest number of slots the pool was last ASKED for (the card may have granted fewer: waves): not asked again until more are wanted
+    bool grown = false;             // a pass has exhausted the fast workspaces: the kernels carry the user's sizes (kept through a recovery's new model)
+    int fast = 100;                 // quadrature workspace the kernels carry first (GADFIT_HIP_WS_FAST; 0: the user's size from the start)
+  } ws;
+  bool in_recovery = false;         // the unseen-branch handler is running (gfh_set_model_variants then keeps ws.grown)
+  // what is in flight beside the caller: the device part of a creation, an upload, a host-side copy (context.cpp, data.cpp)
+  struct Upload {
+    std::thread pending;            // gfh_set_data_begin: the upload in flight (joined by the next call on this context)
+    std::vector<int32_t> pending_hint_cols;   // gfh_set_variant_hint_columns: consumed by the next gfh_set_model_variants
+    bool creating = false;    // `pending` is the device part of gfh_create_begin (not an upload): gfh_set_data_begin chains its upload behind it
+    bool create_failed = false; std::string create_err;      // ... and it failed: every call that needs the device fails with its message
+    int pending_rc = 0;
+    void* hc_dst = nullptr; const void* hc_src = nullptr; size_t hc_bytes = 0;   // gfh_queue_host_copy: a host-side copy made beside the next upload
+    std::thread host_copy;             // ... on a thread of its own (gfh_wait_host_copy joins it)
+  } up;
   long n_unseen_rounds = 0;         // passes repeated because a point left the recorded decision tree (since the model was set)
   gfh::GenConfig gen;
   std::map<std::vector<int32_t>, gfh::ModelKernels> kernel_cache;
@@ -126,22 +137,27 @@ struct gfh_ctx {
   gfh::DevBuf slice, counters, tail_dev; std::vector<char> tail_host;
   bool fused = true;                // STEP 1+2 in one kernel (GADFIT_HIP_FUSED=0: separate sweep and Gram kernels)
 
-  // timers (seconds) + counters
-  double t_sweep = 0, t_gram = 0, t_reduce = 0, t_allreduce = 0, t_chi2 = 0, t_omega = 0;
-  long n_sweep = 0, n_chi2 = 0, n_allreduce = 0;
-  double t_sweep_min = 0, t_sweep_max = 0, t_sweep_last = 0; long n_sweep_timed = 0, n_chi2_timed = 0, n_omega = 0, n_omega_timed = 0, n_chain_timed = 0;
-  // 0: no events; 1: events around every 8th launch of each model kernel (an event record costs ~4 us of stream time: two per
-  // launch were 8 us of a 35 us small-fit iteration), the sums scaled to all launches; 2: every launch, also reduce/all-reduce
-  int timer_detail = 1;
-  int ev_pending = 0;               // timer level of a sweep whose events have not been read yet
-  int placement_tries = 16;         // candidate allocations of a large Jacobian buffer that are timed (gfh_set_placement_tries; 1: take the first)
-  double placement_ms[8] = {0};     // the candidates' store-stream times of the last placement, [0] = the one kept
-  int placement_n = 0;
-  int placement_data_n = 0; double placement_data_ms = 0.0;   // round 6: re-placements of {x, y, w, res} tried behind the Jacobian's, the kernel's time on the set kept
-  int placement_after = 48;         // sweeps that must have written the buffer before candidates are timed (gfh_set_placement_after)
-  int64_t sweeps_on_J = 0;          // ... counted since the buffer was (re)allocated
-  double placement_copy_rate = 0;   // B/s of a device-to-device copy inside the first candidate (the measure the placement's thresholds scale with)
-  bool placement_pending = false;   // the Jacobian buffer was (re)allocated and is large: the next sweep that writes it times candidates first
+  // timers (seconds) + counters (inspect.cpp; the passes count and bracket their launches)
+  struct Timers {
+    double t_sweep = 0, t_gram = 0, t_reduce = 0, t_allreduce = 0, t_chi2 = 0, t_omega = 0;
+    long n_sweep = 0, n_chi2 = 0, n_allreduce = 0;
+    double t_sweep_min = 0, t_sweep_max = 0, t_sweep_last = 0; long n_sweep_timed = 0, n_chi2_timed = 0, n_omega = 0, n_omega_timed = 0, n_chain_timed = 0;
+    // 0: no events; 1: events around every 8th launch of each model kernel (an event record costs ~4 us of stream time: two per
+    // launch were 8 us of a 35 us small-fit iteration), the sums scaled to all launches; 2: every launch, also reduce/all-reduce
+    int detail = 1;
+    int ev_pending = 0;             // timer level of a sweep whose events have not been read yet
+  } timers;
+  // the placement search (placement.cpp)
+  struct Placement {
+    int tries = 16;                 // candidate allocations of a large Jacobian buffer that are timed (gfh_set_placement_tries; 1: take the first)
+    double ms[8] = {0};             // the candidates' store-stream times of the last placement, [0] = the one kept
+    int n = 0;
+    int data_n = 0; double data_ms = 0.0;   // round 6: re-placements of {x, y, w, res} tried behind the Jacobian's, the kernel's time on the set kept
+    int after = 48;                 // sweeps that must have written the buffer before candidates are timed (gfh_set_placement_after)
+    int64_t sweeps_on_J = 0;        // ... counted since the buffer was (re)allocated
+    double copy_rate = 0;           // B/s of a device-to-device copy inside the first candidate (the measure the placement's thresholds scale with)
+    bool pending = false;           // the Jacobian buffer was (re)allocated and is large: the next sweep that writes it times candidates first
+  } place;
   hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 };
 

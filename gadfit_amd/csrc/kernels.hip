@@ -503,7 +503,7 @@ __global__ __launch_bounds__(256) void k_assemble_sparse(const double* __restric
   }
 }
 
-// The same packed image from host-built source lists (context.cpp, prepare_active): k_assemble_sparse reaches a value through four
+// The same packed image from host-built source lists (active.cpp, prepare_active): k_assemble_sparse reaches a value through four
 // dependent loads (pattern entry -> owner -> inv -> G), each ~2 us on an idle chip, which made it 24 us at config 3.  Here
 // meta[idx] >= 0 is the offset of the single term in G; meta[idx] < 0 (and not INT_MIN = no term) points at [count, offsets...]
 // in `list`, the terms of an entry that walks the datasets, in dataset order.  Same terms, same order of additions as k_assemble.

@@ -411,7 +411,7 @@ extern "C" int gfh_fit(gfh_ctx* c, double* pars, int na, const int32_t* active, 
   // while the previous first trial was accepted.  Off when the convergence tests read the device
   // J/res pair the reference has at that point (old J, new res: gadfit.F90:849-850, 865-873).
   // adaptive parallelism (load_balancing, gadfit.F90:672-673): the ranges may be re-cut before an iteration, so no sweep is handed over
-  const bool balancing = c->load_balancing && c->nranks > 1;
+  const bool balancing = c->bal.on && c->nranks > 1;
   // ... and only where the sweep's sum r^2 is bitwise what chi2() returns at the same parameters: the fused kernel (same
   // partition and order of additions as gfh_k_chi2) with shared reciprocals (GADFIT_HIP_FAST_DIV=0 keeps the reference's
   // two division forms, whose values differ by rounding between the active and the passive evaluation)

@@ -549,7 +549,7 @@ def test_device_against_the_reference_cxx_directly(ctx, which):
 
 
 def test_placement_of_the_jacobian_and_of_the_data_arrays_changes_no_bit(monkeypatch):
-    """The placement search (context.cpp, place_jacobian_now; round 6: also x, y, w, res as a set) swaps the buffers under a context:
+    """The placement search (placement.cpp, place_jacobian_now; round 6: also x, y, w, res as a set) swaps the buffers under a context:
     the Jacobian buffer for the fastest of several allocations, the four data arrays for copies in other pages.  The sums of a sweep,
     the residuals, the weights and the abscissas behind the swap are bitwise those before it (1.1e6 points x 32 parameters: the
     smallest Jacobian the search is made for)."""
@@ -577,6 +577,53 @@ def test_placement_of_the_jacobian_and_of_the_data_arrays_changes_no_bit(monkeyp
         assert c.chi2(start) == chi0
     finally:
         c.close()
+
+
+def test_blocks_the_data_search_replaced_enter_the_pool_at_their_real_size():
+    """The pool's invariant (devmem.cpp: a pooled block of class k is 1 << k bytes long) behind a placement search.  A context with
+    96 active parameters of the K = 32 gaussK model and 350 000 points -- x, y, w, res of 2.8 MB each, pool class 4 MB; a Jacobian of
+    269 MB, above the 256 MB from which the search runs -- lets the search run at once, sweeps twice and closes: whatever set of
+    {x, y, w, res} the data search left in place goes to the pool through dev_release.  A context of the same process with 500 000
+    points (4.0 MB per array, the same class) then takes its arrays from that pool.  Its sweep sums, residuals, weights and abscissas
+    are bitwise those of the same sweep by a context created BEFORE the first one, whose arrays no search has touched.
+    (The C ABI does not report whether the data search swapped a set -- placement() gives the kernel's times only -- so the test
+    cannot assert that it did; where it did not, the pool holds the first context's own class-size blocks and the test passes trivially.)"""
+    K, na = 32, 96
+    truth = M.gaussK_truth(K)
+    t = trace_model(M.make_model_gaussK(K), 4 * K)
+    act = list(range(na)); start = M.start_values(truth).reshape(1, 4 * K)
+    n_small, n_large = 350_000, 500_000
+    xs, ys, ss = M.make_single(M.gaussK_numpy(K), truth, n_small, 0.0, 100.0)
+    xl, yl, sl = M.make_single(M.gaussK_numpy(K), truth, n_large, 0.0, 100.0)
+
+    def sweep_of(c, x, y, s, n):
+        c.set_model(t); c.set_data(x, y, s, [0, n]); c.init_weights(4)
+        jac, dim = c.jacobian_indices(act, [0] * (4 * K))
+        JTJ, JTr, chi = c.sweep(start, act, jac, dim)
+        return JTJ, JTr, chi, jac, dim
+
+    before = _lib.Context(0)
+    try:
+        JTJ0, JTr0, chi0, _, _ = sweep_of(before, xl, yl, sl, n_large)
+        res0 = before.residuals().copy(); w0 = before.weights().copy(); x0 = before.abscissas().copy()
+        c = _lib.Context(0)
+        try:
+            c.set_placement_after(0)
+            _, _, chi_a, jac, dim = sweep_of(c, xs, ys, ss, n_small)          # the search runs at this sweep
+            pl = c.placement()
+            assert len(pl) >= 1 and pl[0] > 0.0, pl
+            assert c.sweep(start, act, jac, dim)[2] == chi_a
+        finally:
+            c.close()
+        after = _lib.Context(0)
+        try:
+            JTJ1, JTr1, chi1, _, _ = sweep_of(after, xl, yl, sl, n_large)
+            assert np.array_equal(JTJ1, JTJ0) and np.array_equal(JTr1, JTr0) and chi1 == chi0
+            assert np.array_equal(after.residuals(), res0) and np.array_equal(after.weights(), w0) and np.array_equal(after.abscissas(), x0)
+        finally:
+            after.close()
+    finally:
+        before.close()
 
 
 def test_device_meshes_hold_the_oracles_interval_counts(ctx):
@@ -1689,7 +1736,7 @@ def test_upload_in_the_background_with_a_host_copy_beside_it(ctx):
 @pytest.mark.gpu
 def test_contexts_created_one_after_the_other_share_nothing_but_memory():
     """A destroyed context leaves its stream, events, pinned buffers and small device blocks to the next context of the device
-    (context.cpp, BaseRes / dev_release).  Fits of different models and sizes through a row of short-lived contexts give bitwise
+    (devmem.cpp, BaseRes / dev_release).  Fits of different models and sizes through a row of short-lived contexts give bitwise
     what each gives in a process-fresh order: nothing of a previous context's state or data may show."""
     from gadfit_amd.ad import exp
     rng = np.random.default_rng(5)

@@ -12,7 +12,7 @@ cp oracle/libgadfit_oracle.so $T/oracle.bak; cp $T/oracle.so oracle/libgadfit_or
 ASAN_OPTIONS=detect_leaks=0 LD_PRELOAD=$(gcc -print-file-name=libasan.so) python -m pytest tests/test_oracle_goldens.py tests/test_cpu_branching.py -x -q || RC=1
 cp $T/oracle.bak oracle/libgadfit_oracle.so
 RT=$(dirname $(find /opt/rocm/lib/llvm -name "libclang_rt.asan-x86_64.so" | head -1))
-for f in codegen rtc context group lm reader; do
+for src in gadfit_amd/csrc/*.cpp; do f=$(basename $src .cpp)
   /opt/rocm/bin/hipcc -O1 -g -std=c++17 -fPIC --offload-arch=gfx950 -fvisibility=hidden -fsanitize=address -shared-libasan -fno-omit-frame-pointer -w -c gadfit_amd/csrc/$f.cpp -o $T/$f.o
 done
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -fvisibility=hidden --offload-arch=gfx950 -w -c gadfit_amd/csrc/kernels.hip -o $T/kernels.o
