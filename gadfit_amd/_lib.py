@@ -31,10 +31,18 @@ class FitOptions(C.Structure):
                  ('verbosity', C.c_int), ('umnigh_a', C.c_double)])
 
 
+_FIT_OPTION_FIELDS = frozenset(n for n, _ in FitOptions._fields_)
+
+
 class FitResult(C.Structure):
     _fields_ = [('iterations', C.c_int), ('dim', C.c_int), ('dof', C.c_int), ('exit_reason', C.c_int),
                 ('lambda_', C.c_double), ('chi2', C.c_double), ('n_sweeps', C.c_int), ('n_chi2', C.c_int),
                 ('n_omega', C.c_int), ('n_lookahead', C.c_int), ('seconds', C.c_double)]
+
+
+class BatchResult(C.Structure):
+    _fields_ = [('iterations', C.c_int), ('exit_reason', C.c_int), ('n_sweeps', C.c_int), ('n_chi2', C.c_int),
+                ('n_omega', C.c_int), ('dof', C.c_int), ('lambda_', C.c_double), ('chi2', C.c_double)]
 
 
 # every symbol include/gadfit_hip.h declares: name -> (restype, argtypes)
@@ -89,6 +97,11 @@ SYMBOLS = {
     'gfh_omega': (_i, [_vp, _dp, _dp, _dp]),
     'gfh_aux': (_i, [_vp, _i, _dp, _dp]),
     'gfh_fit': (_i, [_vp, _dp, _i, _ip, _ip, C.POINTER(FitOptions), C.POINTER(FitResult)]),
+    'gfh_set_batch_data': (_i, [_vp, _i64, C.POINTER(_i64), _dp, _dp, _dp]),
+    'gfh_fit_batch': (_i, [_vp, _dp, _i, _ip, C.POINTER(FitOptions), C.POINTER(BatchResult), _dp]),
+    'gfh_batch_pass': (_i, [_vp, _dp, _i, _ip, _dp, _dp, _dp]),
+    'gfh_batch_source': (_i64, [_vp, _i, _ip, C.c_char_p, _i64]),
+    'gfh_batch_prepare': (_i, [_vp, _i, _ip]),
     'gfh_set_lookahead': (_i, [_vp, _i]),
     'gfh_set_keep_jacobian': (_i, [_vp, _i]),
     'gfh_set_use_ad': (_i, [_vp, _i]),
@@ -123,6 +136,12 @@ SYMBOLS = {
     'gfh_local_count': (_i64, [_vp]),
     'gfh_local_begin': (_i64, [_vp]),
 }
+
+
+# gfh_batch_result as a numpy record (Context.fit_batch returns an array of them)
+BATCH_RESULT_DTYPE = np.dtype([(n, np.int32) for n in ('iterations', 'exit_reason', 'n_sweeps', 'n_chi2', 'n_omega', 'dof')] +
+                              [('lambda_', np.float64), ('chi2', np.float64)], align=True)
+assert BATCH_RESULT_DTYPE.itemsize == C.sizeof(BatchResult) == 40
 
 
 def lib():
@@ -433,6 +452,83 @@ class Context:
         self._chk(lib().gfh_fit(self._h, dp(p), a.size, ip(a), ip(g), C.byref(o), C.byref(r)))
         self.umnigh_a = o.umnigh_a
         return p.reshape(np.shape(pars)), r
+
+    # --- batched independent fits (gfh_set_batch_data, gfh_fit_batch, gfh_batch_pass)
+    def set_batch_data(self, offsets, x, y, w):
+        """the spectra of a batch back to back: fit f owns points [offsets[f], offsets[f + 1]); w are the weights of (y - f) * w"""
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        x = np.ascontiguousarray(x, dtype=np.float64); y = np.ascontiguousarray(y, dtype=np.float64)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if off.ndim != 1 or off.size < 2:
+            raise GadfitHipError('set_batch_data: offsets must hold n_fits + 1 >= 2 values')
+        if not (x.size == y.size == w.size == off[-1]):
+            raise GadfitHipError('set_batch_data: x, y and w must hold offsets[-1] = %d values each, got %d, %d, %d'
+                                 % (off[-1], x.size, y.size, w.size))
+        self.n_fits = 0
+        try:
+            self._chk(lib().gfh_set_batch_data(self._h, off.size - 1, off.ctypes.data_as(C.POINTER(_i64)), dp(x), dp(y), dp(w)))
+        except GadfitHipError as e:
+            if 'no GPU bound' in str(e):       # (a compile-only context: the library has checked the geometry and keeps it, so does this object)
+                self.n_fits = off.size - 1
+            raise
+        self.n_fits = off.size - 1
+
+    def _batch_args(self, who, pars, active):
+        p = np.ascontiguousarray(pars, dtype=np.float64).copy()
+        a = np.ascontiguousarray(active, dtype=np.int32)
+        n = getattr(self, 'n_fits', 0)
+        if n < 1:
+            raise GadfitHipError(who + ': no batch data (set_batch_data)')
+        if p.size != n * self.n_pars:
+            raise GadfitHipError('%s: pars must hold n_fits x n_pars = %d x %d values, got %d' % (who, n, self.n_pars, p.size))
+        if a.size < 1 or a.min() < 0 or a.max() >= self.n_pars:
+            raise GadfitHipError('%s: active parameter indices must lie in [0, %d)' % (who, self.n_pars))
+        return p.reshape(n, self.n_pars), a, n
+
+    def fit_batch(self, pars, active, DTD_min=None, **kw):
+        """every spectrum of the batch fitted in one launch.  pars [n_fits][n_pars]; keyword arguments as fit().  Returns the fitted
+        parameters, a numpy record array of BatchResult [n_fits] and the device time of the launch in seconds."""
+        p, a, n = self._batch_args('fit_batch', pars, active)
+        o = FitOptions()
+        for k, v in kw.items():
+            if v is None:
+                continue
+            name = 'lambda' if k in ('lambda_', 'lam', 'lambda') else k
+            if 'has_' + name not in _FIT_OPTION_FIELDS:
+                raise GadfitHipError('fit_batch: unknown fit argument %r' % k)
+            setattr(o, 'lambda_' if name == 'lambda' else name, v)
+            setattr(o, 'has_' + name, 1)
+        o.umnigh_a = 0.5
+        if DTD_min is not None:
+            dm = np.ascontiguousarray(DTD_min, dtype=np.float64)
+            if dm.size != a.size:
+                raise GadfitHipError('fit_batch: DTD_min must hold one value per active parameter (%d), got %d' % (a.size, dm.size))
+            o.DTD_min = dp(dm)
+        res = np.zeros(n, dtype=BATCH_RESULT_DTYPE)
+        sec = C.c_double()
+        self._chk(lib().gfh_fit_batch(self._h, dp(p), a.size, ip(a), C.byref(o), res.ctypes.data_as(C.POINTER(BatchResult)),
+                                      C.cast(C.byref(sec), _dp)))
+        return p, res.view(np.recarray), sec.value
+
+    def batch_pass(self, pars, active):
+        """(JTJ [n_fits][na][na], JTres [n_fits][na], chi2 [n_fits]) of every spectrum at pars [n_fits][n_pars] -- gfh_batch_pass"""
+        p, a, n = self._batch_args('batch_pass', pars, active)
+        JTJ = np.zeros((n, a.size, a.size)); JTr = np.zeros((n, a.size)); chi2 = np.zeros(n)
+        self._chk(lib().gfh_batch_pass(self._h, dp(p), a.size, ip(a), dp(JTJ), dp(JTr), dp(chi2)))
+        return JTJ, JTr, chi2
+
+    def batch_source(self, active):
+        a = np.ascontiguousarray(active, dtype=np.int32)
+        n = lib().gfh_batch_source(self._h, a.size, ip(a), None, 0)
+        if n < 0:
+            self._chk(1)
+        buf = C.create_string_buffer(n)
+        lib().gfh_batch_source(self._h, a.size, ip(a), buf, n)
+        return buf.value.decode()
+
+    def batch_prepare(self, active):
+        a = np.ascontiguousarray(active, dtype=np.int32)
+        self._chk(lib().gfh_batch_prepare(self._h, a.size, ip(a)))
 
     def lm_iterate(self, pars, active, is_global, n_iter, state3, DTD):
         """n_iter LM iterations without convergence exits; pars, state3, DTD are updated in place."""

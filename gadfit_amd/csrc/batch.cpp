@@ -1,0 +1,228 @@
+// batch.cpp -- batched independent fits: many Levenberg-Marquardt fits of ONE model in ONE kernel launch, each with its own data,
+// start parameters, lambda history and exit (gfh_set_batch_data, gfh_fit_batch, gfh_batch_pass, gfh_batch_source, gfh_batch_prepare).
+// This file validates, uploads, compiles / loads and launches; the loop itself (gadfit.F90:670-915) is the generated kernel
+// gfh_k_fit_batch (codegen.cpp, emit_batch_kernels), a wave per fit.  One stream, one launch and one device-to-host copy per call.
+// Everything the kernels do not carry is refused here with its own message, before anything touches the device.
+#include "context_internal.h"
+#include <algorithm>
+#include <cstring>
+#include <exception>
+
+using namespace gfh;
+
+namespace {
+
+// layouts shared with the generated source (codegen.cpp: gfh_batch_opts, gfh_batch_rec)
+struct BatchOpts {
+  double lambda, lam_up, lam_down, accth, chi2_abs, chi2_rel, rel_error;
+  double dtd_min[kValuGramMax];
+  int lam_incs, max_iter, has_max_iter, use_accth, has_chi2_abs, has_chi2_rel, has_rel_error, damp_plain;
+};
+static_assert(sizeof(gfh_batch_result) == 40 && sizeof(BatchOpts) == 7 * 8 + 8 * kValuGramMax + 8 * 4, "layout shared with the generated kernels");
+
+// what a batch cannot be: refused on any context, with or without a GPU
+int check_context(gfh_ctx* c, const char* who) {
+  if (!c) return 1;
+  const std::string w(who);
+  if (c->grp) return fail(c, w + " is not available on a device-group handle (the fits are independent: split the batch over the members' contexts)");
+  if (c->nranks > 1) return fail(c, w + " is not available on a context with a communicator of more than one rank (the fits are independent: split the batch)");
+  return 0;
+}
+int check_model(gfh_ctx* c, const char* who, int na, const int32_t* active) {
+  const std::string w(who);
+  if (!c->has_model) return fail(c, w + ": no model set (gfh_set_model)");
+  if (c->model.has_integrals()) return fail(c, w + ": models with integrate() are not carried by the batch kernels");
+  if (c->model.branching()) return fail(c, w + ": models recorded as variant tapes (a branching eval()) are not carried by the batch kernels");
+  if (c->model.n_aux > 0) return fail(c, w + ": models with auxiliary per-point columns are not carried by the batch kernels");
+  if (c->pars_fn) return fail(c, w + ": a pars hook (gfh_set_pars_hook) cannot run inside a device-resident loop");
+  if (c->gen.loss != 0) return fail(c, w + ": a robust loss (gfh_set_loss) is not carried by the batch kernels");
+  if (c->gen.finite_diff) return fail(c, w + ": use_ad = 0 (finite differences) is not carried by the batch kernels");
+  if (na < 1) return fail(c, "There are no active parameters.");                                       // gadfit.F90:602-603
+  if (na > kValuGramMax) return fail(c, w + ": more than " + std::to_string(kValuGramMax) + " active parameters per fit");
+  if (!active) return fail(c, w + ": null argument");
+  if (na > c->model.n_pars) return fail(c, w + ": more active parameters than the model has");
+  for (int j = 0; j < na; j++) {
+    if (active[j] < 0 || active[j] >= c->model.n_pars) return fail(c, w + ": active parameter index out of range");
+    for (int k = 0; k < j; k++) if (active[k] == active[j]) return fail(c, w + ": an active parameter is listed twice");
+  }
+  return 0;
+}
+int check_geometry(gfh_ctx* c, const char* who, int na) {
+  const std::string w(who);
+  if (c->batch.n_fits < 1) return fail(c, w + ": no batch data (gfh_set_batch_data)");
+  if (c->batch.min_points < na) return fail(c, "More independent fitting parameters than data points (a fit of the batch has " +
+                                              std::to_string((long long)c->batch.min_points) + " points).");      // gadfit.F90:648-657, per fit
+  return 0;
+}
+
+// the translation unit of an active set with the two batch kernels: generated, compiled and (load) loaded once per context, kept
+// in the context's kernel cache under a key no plain active set has, so that a new model or gfh_destroy releases it with the rest
+GenConfig batch_config(const gfh_ctx* c) {
+  GenConfig cfg;                    // the defaults, not the context's current switches: one form per (model, active set)
+  cfg.fast_div = c->gen.fast_div;
+  cfg.batch = true;
+  return cfg;
+}
+int batch_kernels(gfh_ctx* c, const std::vector<int32_t>& active, bool load, ModelKernels** out) {
+  std::vector<int32_t> key = active;
+  key.push_back(-(1 << 30));
+  auto it = c->kernel_cache.find(key);
+  if (it != c->kernel_cache.end()) { if (out) *out = &it->second; return 0; }
+  std::string src, err;
+  if (!generate_source(c->model, active, batch_config(c), &src, &err)) return fail(c, err);
+  ModelKernels mk;
+  const uint64_t skey = load ? source_key(src) : 0;
+  if (!(load && acquire_loaded(c->device, skey, &mk))) {
+    std::vector<char> code; bool cached = false;
+    if (!compile_to_code_object(src, &code, &err, &cached)) return fail(c, err);
+    if (!load) return 0;
+    if (!load_kernels(code, &mk, &err)) return fail(c, err);
+    publish_loaded(c->device, skey, mk);
+  }
+  if (!mk.fit_batch || !mk.batch_pass) { release_loaded(c->device, &mk); return fail(c, "the batch kernels are missing from their code object"); }
+  mk.n_active = (int)active.size();
+  ModelKernels* p = &c->kernel_cache.emplace(key, mk).first->second;
+  if (out) *out = p;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+// The spectra of a batch, back to back: fit f owns points [offsets[f], offsets[f + 1]) of x, y, w (w: the weights as used in
+// (y - f) * w, gadfit.F90:682-683).  Replaces the batch the context held.  The geometry is checked and kept before the device is
+// asked for, so a compile-only context ends in "no GPU" with the geometry known to the argument checks of the launches.
+int gfh_set_batch_data(gfh_ctx* c, int64_t n_fits, const int64_t* offsets, const double* x, const double* y, const double* w) try {
+  if (check_context(c, "gfh_set_batch_data")) return 1;
+  if (n_fits < 1) return fail(c, "gfh_set_batch_data: a batch holds at least one fit");
+  if (n_fits > ((int64_t)1 << 31) - 4) return fail(c, "gfh_set_batch_data: more fits than one launch takes (2^31 - 4)");
+  if (!offsets || !x || !y || !w) return fail(c, "gfh_set_batch_data: null argument");
+  if (offsets[0] != 0) return fail(c, "gfh_set_batch_data: offsets must begin at 0");
+  int64_t shortest = offsets[1] - offsets[0];
+  for (int64_t f = 0; f < n_fits; f++) {
+    if (offsets[f + 1] < offsets[f]) return fail(c, "gfh_set_batch_data: offsets must ascend (fit " + std::to_string((long long)f) + " ends before it begins)");
+    shortest = std::min(shortest, offsets[f + 1] - offsets[f]);
+  }
+  if (join_pending(c)) return 1;
+  if (c->device >= 0 && c->batch.on_device) { hipSetDevice(c->device); if (c->stream) hipStreamSynchronize(c->stream); }
+  batch_free(c);
+  c->batch.n_fits = n_fits; c->batch.off.assign(offsets, offsets + n_fits + 1); c->batch.min_points = shortest;
+  NEED_GPU(c);
+  const size_t n = (size_t)offsets[n_fits], nb = sizeof(double) * std::max<size_t>(n, 1);
+  if (dev_alloc(c, c->batch.x, nb) || dev_alloc(c, c->batch.y, nb) || dev_alloc(c, c->batch.w, nb) ||
+      dev_alloc(c, c->batch.off_d, sizeof(int64_t) * (size_t)(n_fits + 1))) return 1;
+  copy_path_ready();
+  if (n) {
+    HIPCHK(c, hipMemcpyAsync(c->batch.x.p, x, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->batch.y.p, y, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->batch.w.p, w, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+  }
+  HIPCHK(c, hipMemcpyAsync(c->batch.off_d.p, offsets, sizeof(int64_t) * (size_t)(n_fits + 1), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->batch.on_device = true;
+  return 0;
+} catch (const std::exception& e) { return fail(c, std::string("gfh_set_batch_data: ") + e.what()); }
+
+// gadf_fit (gadfit.F90:502-1035) for every spectrum of the batch at once: STEP 1+2, the damped solve (potr_f08,
+// gadfit_linalg.F90:36-57), STEP 3 under accth, STEP 4 with its retrials and STEP 5 run on the device, a wave per fit.
+int gfh_fit_batch(gfh_ctx* c, double* pars, int na, const int32_t* active, const gfh_fit_options* o, gfh_batch_result* results,
+                  double* seconds) try {
+  if (check_context(c, "gfh_fit_batch") || check_model(c, "gfh_fit_batch", na, active)) return 1;
+  if (!pars || !results) return fail(c, "gfh_fit_batch: null argument");
+  gfh_fit_options defaults; memset(&defaults, 0, sizeof defaults);
+  if (!o) o = &defaults;
+  // the options of gadf_fit a device-resident loop does not carry
+  if (o->has_uphill && o->uphill != 0) return fail(c, "gfh_fit_batch: uphill != 0 is not carried by the batch kernel");
+  if (o->has_nielsen && o->nielsen) return fail(c, "gfh_fit_batch: the nielsen lambda strategy is not carried by the batch kernel");
+  if (o->has_umnigh && o->umnigh) return fail(c, "gfh_fit_batch: the umnigh lambda strategy is not carried by the batch kernel");
+  if (o->has_grad_chi2) return fail(c, "gfh_fit_batch: the grad_chi2 test is not carried by the batch kernel");
+  if (o->has_cos_phi) return fail(c, "gfh_fit_batch: the cos_phi test is not carried by the batch kernel");
+  if (o->has_rel_error_global) return fail(c, "gfh_fit_batch: rel_error_global has no meaning for independent fits");
+  if (o->has_lam_incs && o->lam_incs < 1) return fail(c, "Input parameter lam_incs must be at least 1.");      // gadfit.F90:575-578
+  if (!o->has_max_iter || o->max_iter < 0) return fail(c, "gfh_fit_batch: max_iter is required (a loop that runs on the device must be bounded)");
+  if (check_geometry(c, "gfh_fit_batch", na)) return 1;
+  BatchOpts bo; memset(&bo, 0, sizeof bo);
+  bo.lambda = o->has_lambda ? o->lambda : 1.0;                                                          // gadfit.F90:568-584
+  bo.lam_up = o->has_lam_up ? o->lam_up : 10.0; bo.lam_down = o->has_lam_down ? o->lam_down : 10.0;
+  bo.lam_incs = o->has_lam_incs ? o->lam_incs : 2;
+  bo.use_accth = o->has_accth && o->accth > 1.17549435e-38; bo.accth = o->accth;
+  bo.has_chi2_abs = o->has_chi2_abs != 0; bo.chi2_abs = o->chi2_abs;
+  bo.has_chi2_rel = o->has_chi2_rel != 0; bo.chi2_rel = o->chi2_rel;
+  bo.has_rel_error = o->has_rel_error != 0; bo.rel_error = o->rel_error;
+  bo.has_max_iter = 1; bo.max_iter = o->max_iter;
+  bo.damp_plain = o->has_damp_max && !o->damp_max;
+  if (o->DTD_min) for (int j = 0; j < na; j++) bo.dtd_min[j] = o->DTD_min[j];                            // gadfit.F90:641-646 (the same for every fit)
+  NEED_GPU(c);
+  if (!c->batch.on_device) return fail(c, "gfh_fit_batch: no batch data on the device (gfh_set_batch_data)");
+  gfh::Range range("gadfit gfh_fit_batch");
+  ModelKernels* mk = nullptr;
+  if (batch_kernels(c, std::vector<int32_t>(active, active + na), true, &mk)) return 1;
+  const int64_t nf = c->batch.n_fits; const int np = c->model.n_pars;
+  const size_t pb = sizeof(double) * (size_t)nf * (size_t)np, rb = sizeof(gfh_batch_result) * (size_t)nf;
+  if (dev_alloc(c, c->batch.io, pb + rb)) return 1;
+  c->batch.host.resize(pb + rb);
+  harvest_events(c);
+  HIPCHK(c, hipMemcpyAsync(c->batch.io.p, pars, pb, hipMemcpyHostToDevice, c->stream));
+  void* x = c->batch.x.p; void* y = c->batch.y.p; void* w = c->batch.w.p; void* off = c->batch.off_d.p;
+  void* dp = c->batch.io.p; void* recs = c->batch.io.as<char>() + pb; long long n = nf; void* stp = c->status.p;
+  void* args[] = {&x, &y, &w, &off, &dp, &bo, &recs, &n, &stp};
+  HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+  HIPCHK(c, hipModuleLaunchKernel(mk->fit_batch, (unsigned)((nf + 3) / 4), 1, 1, 256, 1, 1, 0, c->stream, args, nullptr));
+  HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->batch.host.data(), c->batch.io.p, pb + rb, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  memcpy(pars, c->batch.host.data(), pb);
+  memcpy(results, c->batch.host.data() + pb, rb);
+  if (seconds) *seconds = 1e-3 * ev_ms(c->ev[0], c->ev[1]);
+  return 0;
+} catch (const std::exception& e) { return fail(c, std::string("gfh_fit_batch: ") + e.what()); }
+
+// STEP 1 + 2 (gadfit.F90:675-699) of every spectrum at given parameters: J^T J [n_fits][na * na] (symmetric, both triangles),
+// J^T r [n_fits][na], chi2 [n_fits] -- for callers with their own loop.
+int gfh_batch_pass(gfh_ctx* c, const double* pars, int na, const int32_t* active, double* JTJ, double* JTres, double* chi2) try {
+  if (check_context(c, "gfh_batch_pass") || check_model(c, "gfh_batch_pass", na, active)) return 1;
+  if (!pars || !JTJ || !JTres || !chi2) return fail(c, "gfh_batch_pass: null argument");
+  if (check_geometry(c, "gfh_batch_pass", na)) return 1;
+  NEED_GPU(c);
+  if (!c->batch.on_device) return fail(c, "gfh_batch_pass: no batch data on the device (gfh_set_batch_data)");
+  ModelKernels* mk = nullptr;
+  if (batch_kernels(c, std::vector<int32_t>(active, active + na), true, &mk)) return 1;
+  const int64_t nf = c->batch.n_fits; const int np = c->model.n_pars;
+  const size_t rec = (size_t)na * na + na + 1;
+  const size_t pb = sizeof(double) * (size_t)nf * (size_t)np, ib = sizeof(double) * (size_t)nf * rec;
+  if (dev_alloc(c, c->batch.io, pb) || dev_alloc(c, c->batch.img, ib)) return 1;
+  c->batch.host.resize(ib);
+  HIPCHK(c, hipMemcpyAsync(c->batch.io.p, pars, pb, hipMemcpyHostToDevice, c->stream));
+  void* x = c->batch.x.p; void* y = c->batch.y.p; void* w = c->batch.w.p; void* off = c->batch.off_d.p;
+  void* dp = c->batch.io.p; void* img = c->batch.img.p; long long n = nf; void* stp = c->status.p;
+  void* args[] = {&x, &y, &w, &off, &dp, &img, &n, &stp};
+  HIPCHK(c, hipModuleLaunchKernel(mk->batch_pass, (unsigned)((nf + 3) / 4), 1, 1, 256, 1, 1, 0, c->stream, args, nullptr));
+  HIPCHK(c, hipMemcpyAsync(c->batch.host.data(), c->batch.img.p, ib, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const double* h = reinterpret_cast<const double*>(c->batch.host.data());
+  for (int64_t f = 0; f < nf; f++) {
+    const double* r = h + (size_t)f * rec;
+    memcpy(JTJ + (size_t)f * na * na, r, sizeof(double) * (size_t)na * na);
+    memcpy(JTres + (size_t)f * na, r + (size_t)na * na, sizeof(double) * (size_t)na);
+    chi2[f] = r[(size_t)na * na + na];
+  }
+  return 0;
+} catch (const std::exception& e) { return fail(c, std::string("gfh_batch_pass: ") + e.what()); }
+
+// The generated source of the batch translation unit for the current model and an active set, as gfh_model_source.
+int64_t gfh_batch_source(gfh_ctx* c, int na, const int32_t* active, char* buf, int64_t cap) try {
+  if (check_context(c, "gfh_batch_source") || check_model(c, "gfh_batch_source", na, active)) return -1;
+  std::string src, err;
+  if (!generate_source(c->model, std::vector<int32_t>(active, active + na), batch_config(c), &src, &err)) { fail(c, err); return -1; }
+  if (buf && cap > 0) { const size_t n = std::min<size_t>((size_t)cap - 1, src.size()); memcpy(buf, src.data(), n); buf[n] = 0; }
+  return (int64_t)src.size() + 1;
+} catch (const std::exception& e) { fail(c, std::string("gfh_batch_source: ") + e.what()); return -1; }
+
+// Compiles the batch translation unit (or finds it in the cache) without launching, as gfh_model_prepare; needs no GPU.
+int gfh_batch_prepare(gfh_ctx* c, int na, const int32_t* active) try {
+  if (check_context(c, "gfh_batch_prepare") || check_model(c, "gfh_batch_prepare", na, active)) return 1;
+  return batch_kernels(c, std::vector<int32_t>(active, active + na), false, nullptr);
+} catch (const std::exception& e) { return fail(c, std::string("gfh_batch_prepare: ") + e.what()); }
+
+}  // extern "C"

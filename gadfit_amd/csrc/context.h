@@ -159,6 +159,17 @@ struct gfh_ctx {
     bool pending = false;           // the Jacobian buffer was (re)allocated and is large: the next sweep that writes it times candidates first
   } place;
   hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // batched independent fits (batch.cpp): the geometry gfh_set_batch_data was given (kept on the host: the argument checks of the
+  // launches read it before the device is asked for), the spectra back to back, and one block each for what a launch takes and
+  // returns -- io = [pars n_fits x n_pars | result records], img = the images of gfh_batch_pass
+  struct Batch {
+    int64_t n_fits = 0;
+    std::vector<int64_t> off;       // [n_fits + 1]
+    int64_t min_points = 0;         // of the shortest spectrum
+    bool on_device = false;
+    gfh::DevBuf x, y, w, off_d, io, img;
+    std::vector<char> host;         // where the one device-to-host copy of a call lands
+  } batch;
 };
 
 namespace gfh {

@@ -31,6 +31,8 @@ int dev_alloc(gfh_ctx* c, DevBuf& b, size_t bytes);
 bool dev_alloc_fresh(DevBuf& b, size_t bytes);
 void dev_free(DevBuf& b);
 void dev_release(int device, DevBuf& b);
+void batch_free(gfh_ctx* c);
+size_t batch_bytes(const gfh_ctx* c);
 int pinned_reserve(gfh_ctx* c, size_t bytes);
 int pinned_stage(gfh_ctx* c, double*& p, size_t& have, size_t bytes);
 bool base_adopt(gfh_ctx* c);
@@ -80,6 +82,9 @@ int place_jacobian_now(gfh_ctx* c, bool fused);
 // passes.cpp
 extern std::recursive_mutex g_handler_mutex;
 int status_check(gfh_ctx* c, int st);
+
+// batch.cpp: nothing crosses its boundary but the C ABI (gfh_set_batch_data, gfh_fit_batch, gfh_batch_pass, gfh_batch_source,
+// gfh_batch_prepare); its kernels live in the context's kernel cache and its blocks in gfh_ctx::batch
 
 // inspect.cpp
 double ev_ms(hipEvent_t a, hipEvent_t b);

@@ -82,6 +82,17 @@ void gfh::dev_release(int device, DevBuf& b) {
   dev_free(b);
 }
 
+// the blocks of a batch of independent fits (context.h, Batch; batch.cpp fills them): dropped together by the next
+// gfh_set_batch_data, and what gfh_device_memory reports of them
+void gfh::batch_free(gfh_ctx* c) {
+  DevBuf* bufs[] = {&c->batch.x, &c->batch.y, &c->batch.w, &c->batch.off_d, &c->batch.io, &c->batch.img};
+  for (DevBuf* b : bufs) dev_free(*b);
+  c->batch.on_device = false;
+}
+size_t gfh::batch_bytes(const gfh_ctx* c) {
+  return c->batch.x.bytes + c->batch.y.bytes + c->batch.w.bytes + c->batch.off_d.bytes + c->batch.io.bytes + c->batch.img.bytes;
+}
+
 int gfh::pinned_reserve(gfh_ctx* c, size_t bytes) {
   if (c->h_pinned_bytes >= bytes) return 0;
   if (c->h_pinned) hipHostFree(c->h_pinned);

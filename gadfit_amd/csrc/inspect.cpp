@@ -242,6 +242,7 @@ int gfh_device_memory(gfh_ctx* c, int64_t* out3) {
   out3[0] = (int64_t)free_b; out3[1] = (int64_t)total_b; out3[2] = 0;
   const int n = c->grp ? gfh_group_size(c) : 1;
   for (int r = 0; r < n; r++) out3[2] += (int64_t)(c->grp ? gfh::group_member(c, r) : c)->ws.wsg.bytes;
+  out3[2] += (int64_t)batch_bytes(c);
   return 0;
 }
 

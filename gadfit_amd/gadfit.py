@@ -283,6 +283,58 @@ def gadf_fit(lambda_=None, lam_up=None, lam_down=None, accth=None, grad_chi2=Non
     return r
 
 
+def gadf_fit_batch(xs, ys, ws, pars, lambda_=None, lam_up=None, lam_down=None, accth=None, rel_error=None, chi2_rel=None,
+                   chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, **kw):
+    """Many independent fits of the session's model in one kernel launch (gfh_fit_batch): gadf_fit's loop (gadfit.F90:670-915) per
+    spectrum, each with its own data, start parameters, lambda history and exit.  On a session initialised with one dataset slot
+    (``gadf_init(f)``); the active set is the one ``gadf_set`` left.  ``xs, ys, ws``: one array per spectrum (``ws``: the weights as
+    used in (y - f) * w; None = ones); ``pars`` [n_fits][n_pars] start values, passive entries included.  The fit arguments are
+    gadf_fit's; those a device-resident loop does not carry (uphill, nielsen, umnigh, grad_chi2, cos_phi, rel_error_global) are refused
+    by the library, and max_iter is required.  Returns (parameters [n_fits][n_pars], record array of per-fit results with the fields
+    iterations, exit_reason, n_sweeps, n_chi2, n_omega, dof, lambda_, chi2)."""
+    _need_init()
+    if 'lambda' in kw:
+        lambda_ = kw.pop('lambda')
+    if _S.n_datasets != 1:
+        raise GadfitError('gadf_fit_batch needs a session with one dataset slot: gadf_init(f)')
+    active = [i for i, a in enumerate(_S.active) if a]
+    if not active:
+        raise GadfitError('There are no active parameters.')
+    xs = [np.asarray(v, dtype=np.float64).ravel() for v in xs]; ys = [np.asarray(v, dtype=np.float64).ravel() for v in ys]
+    ws = [np.ones_like(v) for v in xs] if ws is None else [np.asarray(v, dtype=np.float64).ravel() for v in ws]
+    if not (len(xs) == len(ys) == len(ws)) or not xs or any(not (a.size == b.size == c.size) for a, b, c in zip(xs, ys, ws)):
+        raise GadfitError('gadf_fit_batch: xs, ys and ws must hold one array per spectrum, of equal lengths')
+    pars = np.asarray(pars, dtype=np.float64)
+    if pars.shape != (len(xs), len(_S.fitfuncs[0].pars)):
+        raise GadfitError('gadf_fit_batch: pars must be [n_fits][n_pars] = [%d][%d]' % (len(xs), len(_S.fitfuncs[0].pars)))
+    if _S.comm is not None:
+        raise GadfitError('gadf_fit_batch: the fits are independent; split the batch over the ranks instead of sharing a communicator')
+    if _S.ctx is None:
+        _S.ctx = _lib.Context(_S.device)
+        if 'GADFIT_HIP_KEEP_J' not in os.environ:
+            _S.ctx.set_keep_jacobian(2)       # (as _ensure_device: a gadf_fit of this session may follow)
+    if _S.tape is None or not _tape_is_current():
+        try:
+            _S.tape = _S.fitfuncs[0].trace()
+        except TypeError as e:
+            raise GadfitError('gadf_fit_batch: %s' % e)
+        _S.ctx.set_model(_S.tape)
+        _S.uploaded = False
+    _S.ctx.set_loss(_S.loss)
+    _S.ctx.set_use_ad(True)
+    off = np.zeros(len(xs) + 1, dtype=np.int64)
+    np.cumsum([v.size for v in xs], out=off[1:])
+    try:
+        _S.ctx.set_batch_data(off, np.concatenate(xs), np.concatenate(ys), np.concatenate(ws))
+        out, res, _ = _S.ctx.fit_batch(pars, active, DTD_min=DTD_min, lambda_=_f32(lambda_), lam_up=_f32(lam_up), lam_down=_f32(lam_down),
+                                       accth=_f32(accth), rel_error=_f32(rel_error), chi2_rel=_f32(chi2_rel), chi2_abs=_f32(chi2_abs),
+                                       lam_incs=lam_incs, max_iter=max_iter, damp_max=None if damp_max is None else int(damp_max),
+                                       **{k: v for k, v in kw.items() if v is not None})
+    except _lib.GadfitHipError as e:
+        raise GadfitError(str(e))
+    return out, res
+
+
 def gadf_print(begin=None, end=None, points=None, output=None, grouped=None, logplot=None):
     """gadfit.F90:1255-1395 writes curve / parameter files; here only the parameter table."""
     _need_init()

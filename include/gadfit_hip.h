@@ -218,7 +218,8 @@ int  gfh_debug_mesh_stats(gfh_ctx* ctx, int64_t* out4);
  * context's pool of quadrature workspaces -- the user-sized interval workspaces of integrate() (numerical_integration.F90:40-51,
  * 128-134: heap arrays there) live in ONE allocation of the context, a slot per wave of a launch, once they exceed 8 KB of scratch per
  * lane; it is cut at the first pass that needs it, an error code if the card cannot provide it, and freed by gfh_destroy.  A group
- * handle reports member 0's card and the sum of the members' pools. */
+ * handle reports member 0's card and the sum of the members' pools.  The blocks of a batch of independent fits (gfh_set_batch_data:
+ * the spectra, their offsets, the parameter / result block and the images of gfh_batch_pass) are counted in out3[2] as well. */
 int  gfh_device_memory(gfh_ctx* ctx, int64_t* out3);
 /* Generated HIP source for the current model and an active set (debug / AOT builds).
  * Returns bytes needed (including NUL); copies at most cap bytes. */
@@ -358,6 +359,38 @@ int  gfh_fit(gfh_ctx* ctx, double* pars, int n_act, const int32_t* active_pars,
  * state3 in/out = {lambda, old_chi2 (<0: evaluate first), accepted count}; DTD in/out [dim]. */
 int  gfh_lm_iterate(gfh_ctx* ctx, double* pars, int n_act, const int32_t* active_pars,
                     const int32_t* is_global, int n_iter, double* state3, double* DTD);
+
+/* ---- Batched independent fits: MANY Levenberg-Marquardt fits of ONE model in ONE kernel launch -- a detector image, a
+ * hyperspectral cube, a time series of decays.  Not a global fit with every parameter local: each fit has its own data, start
+ * parameters, lambda history, accept / reject decisions and exit, so the loop of gadf_fit (gadfit.F90:670-915) runs on the device,
+ * a wave per fit, and nothing returns to the host between iterations.
+ * Carried: plain models (no integrate(), one recorded path, no auxiliary columns, no pars hook), automatic differentiation, the
+ * linear loss, 1 to 8 active parameters, and the options lambda, lam_up, lam_down, lam_incs, accth, DTD_min (one vector for all
+ * fits), damp_max, chi2_abs, chi2_rel, rel_error, max_iter (required: the loop must be bounded).  Everything else -- group handles,
+ * communicators of several ranks, uphill, nielsen, umnigh, grad_chi2, cos_phi, rel_error_global -- is refused with a message of its
+ * own before the device is asked for.
+ *
+ * gfh_set_batch_data: the spectra back to back; fit f owns points [offsets[f], offsets[f + 1]) of x, y, w, offsets[0] = 0 and
+ * ascending; w are the weights as used in (y - f) * w (gadfit.F90:682-683).  Replaces the batch the context held; independent of
+ * gfh_set_data. */
+int  gfh_set_batch_data(gfh_ctx* ctx, int64_t n_fits, const int64_t* offsets, const double* x, const double* y, const double* w);
+/* One record per fit.  exit_reason as gfh_fit_result (0 max_iter, 1 chi2_abs, 2 chi2_rel, 5 rel_error, 7 lambda raised lam_incs + 1
+ * times in a row), and 8: the damped matrix of THIS fit was not positive definite (dpotrf's failure, gadfit_linalg.F90:36-57) -- it
+ * ends with the parameters of its last accepted step while its neighbours go on.  n_sweeps, n_chi2, n_omega count STEP 1+2 passes,
+ * chi2() values and STEP 3 passes by the reference's schedule. */
+typedef struct gfh_batch_result { int iterations, exit_reason, n_sweeps, n_chi2, n_omega, dof; double lambda, chi2; } gfh_batch_result;
+/* gadf_fit (gadfit.F90:502-1035) for every spectrum of the batch: pars [n_fits][n_pars] in/out (passive entries are read per fit),
+ * results [n_fits]; *seconds (may be NULL) = device time of the launch.  The damped solve repeats gfh_fit's host solve operation for
+ * operation, so a fit of the batch and gfh_fit on the same spectrum differ by the order of the point sums only. */
+int  gfh_fit_batch(gfh_ctx* ctx, double* pars, int n_act, const int32_t* active_pars, const gfh_fit_options* opt,
+                   gfh_batch_result* results, double* seconds);
+/* STEP 1 + 2 (gadfit.F90:675-699) of every spectrum at given parameters, for callers with their own loop: JTJ [n_fits][n_act*n_act]
+ * (symmetric, both triangles), JTres [n_fits][n_act], chi2 [n_fits]. */
+int  gfh_batch_pass(gfh_ctx* ctx, const double* pars, int n_act, const int32_t* active_pars, double* JTJ, double* JTres, double* chi2);
+/* The generated source of the batch kernels (gfh_k_fit_batch, gfh_k_batch_pass: a translation unit of their own, behind the
+ * model's point functions) as gfh_model_source, and its compilation without a launch as gfh_model_prepare (needs no GPU). */
+int64_t gfh_batch_source(gfh_ctx* ctx, int n_act, const int32_t* active_pars, char* buf, int64_t cap);
+int  gfh_batch_prepare(gfh_ctx* ctx, int n_act, const int32_t* active_pars);
 
 /* ---- Jacobian_indices / dim (gadfit.F90:615-631) as a helper for callers */
 int  gfh_jacobian_indices(int n_datasets, int n_act, const int32_t* active_pars,
