@@ -55,7 +55,8 @@ class FitResult(C.Structure):
     _fields_ = [('iterations', C.c_int), ('dim', C.c_int), ('lambda_', C.c_double), ('chi2', C.c_double),
                 ('dof', C.c_int), ('exit_reason', C.c_int), ('n_sweeps', C.c_int), ('n_chi2', C.c_int),
                 ('n_omega', C.c_int), ('JTJ0', C.POINTER(C.c_double)), ('JTres0', C.POINTER(C.c_double)),
-                ('delta1_0', C.POINTER(C.c_double)), ('delta2_0', C.POINTER(C.c_double)), ('chi2_0', C.c_double)]
+                ('delta1_0', C.POINTER(C.c_double)), ('delta2_0', C.POINTER(C.c_double)), ('chi2_0', C.c_double),
+                ('min_margin', C.c_double)]
 
 
 def _dp(a):

@@ -1076,7 +1076,7 @@ int orc_fit(orc_problem* p, orc_fit_options* o, orc_fit_result* r) {
   if (dof == 0) dof = 1;
   for (int i = 0; i < nd; i++) for (int j = 0; j < na; j++) old_pars[i * na + j] = p->pars[i * np + p->active_pars[j]];
   double old_chi2, new_chi2 = 0, old_old_chi2 = 0, acc_ratio = 0, beta = 0;
-  if (r) { r->n_sweeps = r->n_chi2 = r->n_omega = 0; r->dim = dim; r->dof = dof; r->exit_reason = -1; }
+  if (r) { r->n_sweeps = r->n_chi2 = r->n_omega = 0; r->dim = dim; r->dof = dof; r->exit_reason = -1; r->min_margin = INFINITY; }
   if (orc_chi2(p, P, &old_chi2, res)) goto done;                          /* GF:670 */
   if (r) r->n_chi2++;
 #define SOLVE(rhs_src, out) do { for (int q = 0; q < dim; q++) out[q] = rhs_src[q]; \
@@ -1110,6 +1110,7 @@ int orc_fit(orc_problem* p, orc_fit_options* o, orc_fit_result* r) {
     for (int i = 1; i <= lam_incs + 1; i++) {                             /* STEP 4, GF:752-819 */
       if (orc_chi2(p, P, &new_chi2, res)) goto done;
       if (r) r->n_chi2++;
+      if (r) { double m_ = fabs(new_chi2 - old_chi2) / old_chi2; if (!(m_ >= r->min_margin)) r->min_margin = m_; }
       if (iterations == 0) beta = 0.0;
       else beta = dtd_dot(dim, DTD, delta1, old_delta1) / sqrt(dtd_dot(dim, DTD, delta1, delta1)) / sqrt(dtd_dot(dim, DTD, old_delta1, old_delta1));
       if (powi(1.0 - beta, uphill) * new_chi2 < old_chi2) {               /* GF:761 */

@@ -81,6 +81,9 @@ typedef struct orc_fit_result {
   /* first-iteration snapshots, caller-allocated (dim*dim, dim, dim, dim) or NULL */
   double* JTJ0; double* JTres0; double* delta1_0; double* delta2_0;
   double chi2_0;
+  /* the closest of the loop's decisions: min |new_chi2 - old_chi2| / old_chi2 over every STEP 4 comparison, accepted or rejected
+     (inf if there was none); a report only, nothing in the loop reads it */
+  double min_margin;
 } orc_fit_result;
 
 const char* orc_last_error(void);

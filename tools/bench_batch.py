@@ -2,7 +2,7 @@
 profiles/r05_small_fits.txt: 1000 points, a Gaussian on a background, 4 parameters, lambda0 = 1, max_iter = 30.
 
     python tools/bench_batch.py [--sizes 1024,16384,131072] [--launches 7] [--warmup 2] [--one-at-a-time 200]
-                                [--observed FILE] [--out profiles/batch_fits.json]
+                                [--observed FILE [--observed-only]] [--out profiles/batch_fits.json]
 
 Per batch size: warm-up launches, then the median of the timed launches -- device time from the HIP events around the kernel
 (gfh_fit_batch's `seconds`) and wall time around the whole call (parameters down, launch, results back).  Two yardsticks, neither of
@@ -12,8 +12,9 @@ them the code under test:
  2. the per-point rate of the model's N-sized kernels (gfh_time_kernel: fused sweep and chi2) on the points of 16384 spectra as one
     dataset -- what the card does per point evaluation when it is full and streams every point from HBM once per pass -- against
     the batch kernel's time for the same passes (whose spectra stay in cache from one pass of a fit to the next).
-Needs a GPU; there is no fallback.  --observed: a JSON file of observed parity maxima (tests/test_gpu_batch.py under
-GADFIT_BATCH_OBSERVE) copied into the record."""
+Needs a GPU; there is no fallback.  --observed: a JSON file of observed parity maxima copied into the record, written under
+GADFIT_BATCH_OBSERVE by tests/test_gpu_batch_shapes.py and tests/test_gpu_batch.py run in ONE pytest process (the maxima are kept per
+process, so a module run alone writes its own keys only).  --observed-only: the record's timings stay, its maxima are replaced."""
 import argparse
 import json
 import os
@@ -59,10 +60,22 @@ def main():
     ap.add_argument('--rate-fits', type=int, default=16384)
     ap.add_argument('--observed', default=None)
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'batch_fits.json'))
+    ap.add_argument('--observed-only', action='store_true', help='replace observed_maxima_against_the_oracle of the record at --out by --observed; '
+                                                                 'nothing is timed, no GPU is needed')
     a = ap.parse_args()
     sizes = [int(s) for s in a.sizes.split(',')]
     if a.observed and not os.path.exists(a.observed):
-        sys.exit('--observed %s: no such file (run tests/test_gpu_batch.py under GADFIT_BATCH_OBSERVE first)' % a.observed)
+        sys.exit('--observed %s: no such file (run tests/test_gpu_batch_shapes.py tests/test_gpu_batch.py in one pytest process under GADFIT_BATCH_OBSERVE first)' % a.observed)
+    if a.observed_only:
+        if not a.observed:
+            sys.exit('--observed-only needs --observed FILE')
+        rec = json.load(open(a.out))
+        rec['observed_maxima_against_the_oracle'] = json.load(open(a.observed))
+        with open(a.out, 'w') as fh:
+            json.dump(rec, fh, indent=1, sort_keys=True)
+            fh.write('\n')
+        print('wrote', a.out)
+        return
     if a.launches < 5:
         sys.exit('at least 5 timed launches')
     tape = trace_model(model, 4)
