@@ -8,9 +8,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libgadfit_hip.so')
-# every source and header of csrc/ (a new file is built, and watched by the staleness check, without being listed here)
+# every source and header of csrc/ (a new file is built, and watched by the staleness check, without being listed here).  csrc/device/
+# is not compiled on its own: device_text.cpp embeds its files and kernels.hip includes one of them, so they are watched like headers.
 SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith(('.cpp', '.hip')))
-HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith('.h')) + ['exports.map', '../../include/gadfit_hip.h', '../../include/gadfit_tape.h']
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith('.h')) + sorted('device/' + f for f in os.listdir(os.path.join(CSRC, 'device'))) + \
+          ['exports.map', '../../include/gadfit_hip.h', '../../include/gadfit_tape.h']
 ROCM = os.environ.get('ROCM_PATH', '/opt/rocm')
 
 
@@ -28,7 +30,7 @@ def build_lib(force=False, verbose=False):
     def compile_one(s):
         o = os.path.join(LIBDIR, os.path.splitext(s)[0] + '.o')
         cmd = [os.path.join(ROCM, 'bin', 'hipcc'), '-O3', '-std=c++17', '-fPIC', '-fvisibility=hidden', '--offload-arch=gfx950',
-               '-Wall', '-Wno-unused-result', '-Wno-unused-value', '-c', os.path.join(CSRC, s), '-o', o]
+               '-Wall', '-Wno-unused-result', '-Wno-unused-value', '-Wno-c23-extensions', '-c', os.path.join(CSRC, s), '-o', o]
         if verbose:
             print(' '.join(cmd))
         subprocess.check_call(cmd)

@@ -1,7 +1,7 @@
 // batch.cpp -- batched independent fits: many Levenberg-Marquardt fits of ONE model in ONE kernel launch, each with its own data,
 // start parameters, lambda history and exit (gfh_set_batch_data, gfh_fit_batch, gfh_batch_pass, gfh_batch_source, gfh_batch_prepare).
 // This file validates, uploads, compiles / loads and launches; the loop itself (gadfit.F90:670-915) is the generated kernel
-// gfh_k_fit_batch (codegen.cpp, emit_batch_kernels), a wave per fit.  One stream, one launch and one device-to-host copy per call.
+// gfh_k_fit_batch (batch_fit.hip; codegen.cpp, emit_batch_kernels), a wave per fit.  One stream, one launch and one device-to-host copy per call.
 // Everything the kernels do not carry is refused here with its own message, before anything touches the device.
 #include "context_internal.h"
 #include <algorithm>
@@ -12,7 +12,7 @@ using namespace gfh;
 
 namespace {
 
-// layouts shared with the generated source (codegen.cpp: gfh_batch_opts, gfh_batch_rec)
+// layouts shared with the generated source (batch_fit.hip: gfh_batch_opts, gfh_batch_rec)
 struct BatchOpts {
   double lambda, lam_up, lam_down, accth, chi2_abs, chi2_rel, rel_error;
   double dtd_min[kValuGramMax];

@@ -15,244 +15,22 @@
 //   gfh_k_sweep  STEP 1 (gadfit.F90:675-693): res_i = (y_i-f)*w_i, J[a][i] = df/dp_a * w_i
 //   gfh_k_chi2   chi2() (gadfit.F90:1015-1034): all parameters passive, res_i and sum res^2
 //   gfh_k_omega  STEP 3 (gadfit.F90:715-731): omega_i = -f''_delta(x_i) * w_i, forward mode
+//
+// Only what depends on the tape is generated here: the point functions, the quadrature call sites, the selector and the
+// #defines in front of them.  The kernels themselves are hand-written HIP that no tape changes; they are plain files under
+// device/ (sweep.hip, fused_sweep_gram.hip, chi2.hip, omega.hip, omega_jt.hip, batch_fit.hip, ...), embedded by
+// device_text.cpp and streamed into the translation unit by generate_source as they are.  Loading and validating a tape is
+// model.cpp.
 #include "model.h"
+#include "device_text.h"
 #include "../../include/gadfit_gk_tables.h"
 #include <cmath>
 #include <cstdio>
-#include <cstring>
 #include <algorithm>
 #include <functional>
 #include <sstream>
 
 namespace gfh {
-
-bool Model::load(const gfh_tape* t, std::string* err) {
-  if (!t || t->n_subtapes < 1 || !t->sub) { *err = "empty tape"; return false; }
-  n_pars = t->n_pars;
-  sub.clear(); integrals.clear(); ipar_nodes.clear();
-  int n_bind = 0;
-  for (int i = 0; i < t->n_integrals; i++) {
-    const gfh_integral& g = t->integrals[i];
-    integrals.push_back({g.integrand, g.lower, g.upper, g.lower_inf, g.upper_inf, g.n_ipars,
-                         g.ipar_off, g.depth, g.rel_error, g.abs_error});
-    if (g.ipar_off + g.n_ipars > n_bind) n_bind = g.ipar_off + g.n_ipars;
-    if (g.integrand < 1 || g.integrand >= t->n_subtapes) { *err = "integral refers to a missing sub-tape"; return false; }
-  }
-  for (int i = 0; i < n_bind; i++) ipar_nodes.push_back(t->ipar_nodes[i]);
-  for (int s = 0; s < t->n_subtapes; s++) {
-    const gfh_subtape& st = t->sub[s];
-    SubTape o; o.result = st.result;
-    if (st.n_nodes < 1 || st.result < 0 || st.result >= st.n_nodes) { *err = "malformed sub-tape"; return false; }
-    for (int k = 0; k < st.n_nodes; k++) {
-      const gfh_node& n = st.nodes[k];
-      Node d{n.op, n.a, n.b, n.flags, n.c};
-      auto bad_ref = [&](int r) { return r < 0 || r >= k; };
-      switch (n.op) {
-        case GFH_CONST: case GFH_X: case GFH_IVAR: break;
-        case GFH_AUX:
-          // (inside an integrand too: a real of the enclosing eval() that the integrand takes without passing it through pars(:))
-          if (n.a < 0 || n.a >= t->n_aux) { *err = "auxiliary column out of range"; return false; }
-          break;
-        case GFH_PARAM: if (n.a < 0 || n.a >= n_pars) { *err = "parameter index out of range"; return false; } break;
-        case GFH_IPARAM: if (n.a < 0) { *err = "bad integrand parameter"; return false; } break;
-        case GFH_LIFT: case GFH_NEG: case GFH_POWI: case GFH_VAL:
-          if (bad_ref(n.a)) { *err = "operand refers forward"; return false; } break;
-        case GFH_ADD: case GFH_SUB: case GFH_MUL: case GFH_DIV: case GFH_POW:
-          if (bad_ref(n.a) || bad_ref(n.b)) { *err = "operand refers forward"; return false; } break;
-        case GFH_INTEGRATE: if (n.a < 0 || n.a >= t->n_integrals) { *err = "bad integral index"; return false; } break;
-        case GFH_GUARD_GT: case GFH_GUARD_LT:
-          // (inside an integrand, s != 0: decided per evaluation of the integrand -- Model::alts, emit_family)
-          if (bad_ref(n.a) || bad_ref(n.b)) { *err = "operand refers forward"; return false; }
-          break;
-        default:
-          if (n.op >= GFH_ABS && n.op <= GFH_ERF) { if (bad_ref(n.a)) { *err = "operand refers forward"; return false; } }
-          else { *err = "unknown op code " + std::to_string(n.op); return false; }
-      }
-      o.nodes.push_back(d);
-    }
-    sub.push_back(std::move(o));
-  }
-  gk_points = t->gk_points ? t->gk_points : 15;
-  n_aux = t->n_aux > 0 ? t->n_aux : 0;
-  rel_error_outer = t->rel_error_outer; rel_error_inner = t->rel_error_inner;
-  ws_size = t->ws_size > 0 ? t->ws_size : 1000;                       // NI:40 DEFAULT_WORKSPACE_SIZE
-  ws_size_inner = t->ws_size_inner > 0 ? t->ws_size_inner : 1000;
-  if (ws_size < 2 || ws_size_inner < 2) { *err = "quadrature workspace size must be at least 2"; return false; }
-  // (any size the device's memory holds: workspaces beyond the scratch budget live in the context's global pool, plan_workspaces)
-  if (ws_size > (1 << 22) || ws_size_inner > (1 << 22)) { *err = "quadrature workspace size beyond 4194304 intervals"; return false; }
-  more_evals.clear(); hint_aux = -1; hint_cols.clear(); tape_variant.assign(1, 0);
-  alts.assign(integrals.size(), {});
-  // a guard has no value: nothing may use one as an operand, a bound, a binding or the result
-  for (const SubTape& st : sub) {
-    auto guard = [&](int k) { return k >= 0 && k < (int)st.nodes.size() && is_guard_op(st.nodes[(size_t)k].op); };
-    bool bad = guard(st.result);
-    for (const Node& nd : st.nodes) {
-      switch (nd.op) {
-        case GFH_CONST: case GFH_X: case GFH_AUX: case GFH_PARAM: case GFH_IVAR: case GFH_IPARAM: case GFH_GUARD_GT: case GFH_GUARD_LT: break;
-        case GFH_INTEGRATE: {
-          const Integral& in = integrals[(size_t)nd.a];
-          if ((!in.lower_inf && guard(in.lower)) || (!in.upper_inf && guard(in.upper))) bad = true;
-          for (int q = 0; q < in.n_ipars; q++) if (guard(ipar_nodes[(size_t)in.ipar_off + q])) bad = true;
-          break;
-        }
-        case GFH_ADD: case GFH_SUB: case GFH_MUL: case GFH_DIV: case GFH_POW: if (guard(nd.a) || guard(nd.b)) bad = true; break;
-        default: if (guard(nd.a)) bad = true; break;
-      }
-    }
-    if (bad) { *err = "a comparison is used as a value"; return false; }
-  }
-  return true;
-}
-
-bool Model::has_guards() const {
-  for (int v = 0; v < n_variants(); v++) for (const Node& nd : eval(v).nodes) if (is_guard_op(nd.op)) return true;
-  return false;
-}
-
-namespace {
-bool same_bits(double a, double b) { return memcmp(&a, &b, sizeof a) == 0; }
-// same operation (guards: whatever their recorded outcome)
-bool same_node(const Node& a, const Node& b) {
-  return a.op == b.op && a.a == b.a && a.b == b.b && (a.flags & ~GFH_F_TAKEN) == (b.flags & ~GFH_F_TAKEN) && same_bits(a.c, b.c);
-}
-bool same_subtape(const SubTape& a, const SubTape& b) {
-  if (a.result != b.result || a.nodes.size() != b.nodes.size()) return false;
-  for (size_t k = 0; k < a.nodes.size(); k++) if (!same_node(a.nodes[k], b.nodes[k]) || a.nodes[k].flags != b.nodes[k].flags) return false;
-  return true;
-}
-}  // namespace
-
-// Further recorded paths of the same eval().  Their integrand sub-tapes and integrate() call sites join the pool of variant 0
-// (sub[1..], integrals, ipar_nodes), identical ones shared -- so one generated device function serves every variant that calls
-// it, and an INTEGRATE node of two variants is the same operation exactly when it carries the same pooled index.
-bool Model::load_variants(int n, const gfh_tape* const* t, int hint, std::string* err, const std::vector<int32_t>* cols) {
-  if (n < 1 || !t || !t[0]) { *err = "no variant"; return false; }
-  if (!load(t[0], err)) return false;
-  n_tapes = n;
-  tape_variant.assign((size_t)n, 0);
-  for (int v = 1; v < n; v++) {
-    Model o;
-    if (!t[v]) { *err = "null variant"; return false; }
-    if (!o.load(t[v], err)) { *err = "variant " + std::to_string(v) + ": " + *err; return false; }
-    if (o.n_pars != n_pars) { *err = "variants disagree on the number of parameters"; return false; }
-    if (o.gk_points != gk_points || o.rel_error_outer != rel_error_outer || o.rel_error_inner != rel_error_inner ||
-        o.ws_size != ws_size || o.ws_size_inner != ws_size_inner) { *err = "variants disagree on the quadrature settings"; return false; }
-    n_aux = std::max(n_aux, o.n_aux);
-    std::vector<int> sub_map(o.sub.size(), -1), int_map(o.integrals.size(), -1);
-    std::vector<char> busy(o.integrals.size(), 0);
-    bool ok = true;
-    // pooled index of the variant's integral i (its integrand pooled first; integrands may nest call sites: depth <= 2, NI:70)
-    std::function<int(int)> pool_integral;
-    auto pool_sub = [&](int s_) -> int {
-      if (sub_map[(size_t)s_] >= 0) return sub_map[(size_t)s_];
-      SubTape st = o.sub[(size_t)s_];
-      for (Node& nd : st.nodes) if (nd.op == GFH_INTEGRATE) { nd.a = pool_integral(nd.a); if (nd.a < 0) return -1; }
-      for (size_t k = 1; k < sub.size(); k++) if (same_subtape(sub[k], st)) return sub_map[(size_t)s_] = (int)k;
-      sub.push_back(std::move(st));
-      return sub_map[(size_t)s_] = (int)sub.size() - 1;
-    };
-    pool_integral = [&](int i) -> int {
-      if (int_map[(size_t)i] >= 0) return int_map[(size_t)i];
-      if (busy[(size_t)i]) { ok = false; *err = "recursive integrate() call site"; return -1; }
-      busy[(size_t)i] = 1;
-      Integral in = o.integrals[(size_t)i];
-      in.integrand = pool_sub(in.integrand);
-      busy[(size_t)i] = 0;
-      if (in.integrand < 0) return -1;
-      const int32_t* binds = o.ipar_nodes.data() + in.ipar_off;
-      for (size_t k = 0; k < integrals.size(); k++) {
-        const Integral& e = integrals[k];
-        if (e.integrand == in.integrand && e.lower == in.lower && e.upper == in.upper && e.lower_inf == in.lower_inf && e.upper_inf == in.upper_inf &&
-            e.n_ipars == in.n_ipars && e.depth == in.depth && same_bits(e.rel_error, in.rel_error) && same_bits(e.abs_error, in.abs_error) &&
-            std::equal(binds, binds + in.n_ipars, ipar_nodes.begin() + e.ipar_off))
-          return int_map[(size_t)i] = (int)k;
-      }
-      const int off = (int)ipar_nodes.size();
-      ipar_nodes.insert(ipar_nodes.end(), binds, binds + in.n_ipars);
-      in.ipar_off = off;
-      integrals.push_back(in);
-      return int_map[(size_t)i] = (int)integrals.size() - 1;
-    };
-    SubTape ev = o.sub[0];
-    for (Node& nd : ev.nodes) if (nd.op == GFH_INTEGRATE) { nd.a = pool_integral(nd.a); if (nd.a < 0 || !ok) { if (err->empty()) *err = "bad integrate() call site"; return false; } }
-    alts.resize(integrals.size());
-    bool dup = false;
-    for (int w = 0; w < n_variants() && !dup; w++) dup = same_subtape(eval(w), ev);
-    if (dup) { *err = "variant " + std::to_string(v) + " repeats an earlier one"; return false; }
-    // the same path through eval() as an earlier variant, with an integrand that took another path through ITS comparisons (the
-    // call sites agree in everything but the integrand's sub-tape): not a variant of eval() but a further recording of that
-    // integrand.  An integrand that calls integrate() itself is compared the same way, node by node (so the recordings of an INNER
-    // integrand that compares AD variables end up at the inner call site).
-    std::function<bool(int, int, std::vector<std::pair<int, int>>&)> same_site = [&](int Ia, int Ib, std::vector<std::pair<int, int>>& add) -> bool {
-      if (Ia == Ib) return true;
-      const Integral &x = integrals[(size_t)Ia], &y = integrals[(size_t)Ib];
-      const bool site = x.lower == y.lower && x.upper == y.upper && x.lower_inf == y.lower_inf && x.upper_inf == y.upper_inf &&
-                        x.n_ipars == y.n_ipars && x.depth == y.depth && same_bits(x.rel_error, y.rel_error) && same_bits(x.abs_error, y.abs_error) &&
-                        std::equal(ipar_nodes.begin() + x.ipar_off, ipar_nodes.begin() + x.ipar_off + x.n_ipars, ipar_nodes.begin() + y.ipar_off);
-      if (!site) return false;
-      if (x.integrand == y.integrand) return true;
-      const SubTape &sa = sub[(size_t)x.integrand], &sb = sub[(size_t)y.integrand];
-      // the same recording of the integrand up to call sites inside it that are themselves the same site?
-      if (sa.result == sb.result && sa.nodes.size() == sb.nodes.size()) {
-        std::vector<std::pair<int, int>> inner;
-        bool same = true, any_int = false;
-        for (size_t k = 0; k < sa.nodes.size() && same; k++) {
-          const Node &p = sa.nodes[k], &q = sb.nodes[k];
-          if (same_node(p, q) && p.flags == q.flags) continue;
-          if (p.op == GFH_INTEGRATE && q.op == GFH_INTEGRATE && p.b == q.b && p.flags == q.flags && same_site(p.a, q.a, inner)) { any_int = true; continue; }
-          same = false;
-        }
-        if (same && any_int) { add.insert(add.end(), inner.begin(), inner.end()); return true; }
-      }
-      add.push_back({Ia, y.integrand});                  // another path through this integrand's own comparisons
-      return true;
-    };
-    bool joined = false;
-    for (int w = 0; w < n_variants() && !joined; w++) {
-      const SubTape& e = eval(w);
-      if (e.result != ev.result || e.nodes.size() != ev.nodes.size()) continue;
-      std::vector<std::pair<int, int>> add;
-      bool same = true, any_int = false;
-      for (size_t k = 0; k < e.nodes.size() && same; k++) {
-        const Node &p = e.nodes[k], &q = ev.nodes[k];
-        if (same_node(p, q) && p.flags == q.flags) continue;
-        if (p.op == GFH_INTEGRATE && q.op == GFH_INTEGRATE && p.b == q.b && p.flags == q.flags && p.a != q.a && same_site(p.a, q.a, add)) { any_int = true; continue; }
-        same = false;
-      }
-      if (!same || !any_int) continue;
-      for (auto& d : add) {
-        std::vector<int32_t>& f = alts[(size_t)d.first];
-        if (d.second != integrals[(size_t)d.first].integrand && std::find(f.begin(), f.end(), (int32_t)d.second) == f.end()) f.push_back((int32_t)d.second);
-      }
-      joined = true;
-      tape_variant[(size_t)v] = w;
-    }
-    if (joined) continue;
-    more_evals.push_back(std::move(ev));
-    tape_variant[(size_t)v] = n_variants() - 1;
-  }
-  alts.resize(integrals.size());
-  if (hint >= n_aux) { *err = "the per-point variant column lies outside the auxiliary columns"; return false; }
-  hint_aux = hint < 0 ? -1 : hint;
-  hint_cols.clear();
-  if (cols && hint_aux >= 0 && (int)cols->size() == n) {
-    for (int32_t cidx : *cols) if (cidx < 0 || cidx >= n_aux) { *err = "a per-point variant column lies outside the auxiliary columns"; return false; }
-    hint_cols = *cols;
-  }
-  return true;
-}
-
-int Model::hint_col_of_variant(int v) const {
-  if (hint_cols.empty()) return hint_aux;
-  for (size_t t = 0; t < tape_variant.size(); t++) if (tape_variant[t] == v) return hint_cols[t];
-  return hint_aux;
-}
-std::vector<int> Model::tapes_of_variant(int v) const {
-  std::vector<int> out;
-  for (size_t t = 0; t < tape_variant.size(); t++) if (tape_variant[t] == v) out.push_back((int)t);
-  if (out.empty()) out.push_back(v);          // (a model set through gfh_set_model: tape 0 = variant 0)
-  return out;
-}
 
 namespace {
 
@@ -1398,274 +1176,7 @@ static bool emit_batch_kernels(const Model& m, const std::vector<int32_t>& activ
   s << "\n#define GFH_BATCH 1\n#define GFH_BACT {";
   for (int j = 0; j < NA; j++) s << (j ? ", " : "") << active[j];
   s << "}\n";
-  s << R"(
-// ---- Batched independent fits: MANY Levenberg-Marquardt fits of this model in one launch, a wave per fit from its first chi2 to
-// its exit (gadfit.F90:670-915 restated per wave; lm.cpp gfh_fit is the host form of the same lines).  256 threads = 4 waves that
-// never talk to each other: no LDS, no barrier, no atomics; fit f = global wave index.  Lane l takes points off[f] + l, + 64, ...
-// of the fit's contiguous x, y, w (coalesced 512 B rows, no padding between fits); the lanes past the end of the last row re-read
-// the fit's last point with w = 0.  STEP 1+2 is the per-lane outer product of the fused kernel's VALU form (GFH_NA <=
-// GFH_VALU_GRAM_MAX) finished by gfh_wave_sum; the sums come back as wave-uniform values (v_readfirstlane) and every lane runs the
-// damped solve and the lambda logic on them redundantly -- the same operations on the same numbers, so the same decisions -- which
-// keeps the parameter block, the saved parameters and the normal equations in registers for the whole fit.
-#define GFH_BNP (GFH_NA * (GFH_NA + 1) / 2)
-#define GFH_BNACC (GFH_BNP + GFH_NA + 1)
-#define GFH_BIDX(a, b) ((a) * GFH_NA - (a) * ((a) - 1) / 2 + ((b) - (a)))      // packed upper triangle, a <= b
-struct gfh_batch_opts {          // the options of gfh_fit that the batch carries (batch.cpp fills it; absent values hold the reference's defaults)
-  double lambda, lam_up, lam_down, accth, chi2_abs, chi2_rel, rel_error;
-  double dtd_min[GFH_VALU_GRAM_MAX];
-  int lam_incs, max_iter, has_max_iter, use_accth, has_chi2_abs, has_chi2_rel, has_rel_error, damp_plain;
-};
-struct gfh_batch_rec { int iterations, exit_reason, n_sweeps, n_chi2, n_omega, dof; double lambda, chi2; };
-struct gfh_bdata { const double* __restrict__ x; const double* __restrict__ y; const double* __restrict__ w; i64 b, e; int lane; };
-
-static __device__ __forceinline__ double gfh_uni(const double v) {      // lane 0's value as a wave-uniform one
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readfirstlane((int)b), hi = __builtin_amdgcn_readfirstlane((int)(b >> 32));
-  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-// the inputs of pass row i0 (wave-uniform) for this lane; past the end: the last point with w = 0
-#define GFH_BLOAD(X, Y, W, i0) { const i64 i_ = (i0) + d.lane; const i64 c_ = i_ < d.e ? i_ : d.e - 1; \
-  X = d.x[c_]; Y = d.y[c_]; const double w_ = d.w[c_]; W = i_ < d.e ? w_ : 0.0; }
-
-// STEP 1 + 2 (gadfit.F90:675-699) of one fit: S = [J^T J upper triangle, packed | J^T r | sum r^2]
-static __device__ __forceinline__ void gfh_b_sweep(const gfh_bdata& d, const double* __restrict__ P, int* status, double (&S)[GFH_BNACC]) {
-  double av[GFH_BNACC];
-#pragma unroll
-  for (int k = 0; k < GFH_BNACC; k++) av[k] = 0.0;
-  double Xc, Yc, Wc;
-  GFH_BLOAD(Xc, Yc, Wc, d.b)
-  for (i64 i0 = d.b; i0 < d.e; i0 += 64) {
-    double Xn, Yn, Wn;
-    GFH_BLOAD(Xn, Yn, Wn, i0 + 64 < d.e ? i0 + 64 : i0)       // next row's inputs (the last row re-reads its own)
-    double F, G[GFH_NA];
-    gfh_point_grad(Xc, P, F, G, status, (const double*)nullptr, 0 GFH_MESH_NONE GFH_SLOT(i0 + d.lane));
-    const double R = (Yc - F) * Wc;                            // gadfit.F90:682-683
-#pragma unroll
-    for (int a = 0; a < GFH_NA; a++) G[a] = G[a] * Wc;         // gadfit.F90:689-690
-    int p = 0;
-#pragma unroll
-    for (int a = 0; a < GFH_NA; a++)
-#pragma unroll
-      for (int b = a; b < GFH_NA; b++, p++) av[p] += G[a] * G[b];      // gadfit.F90:697
-#pragma unroll
-    for (int a = 0; a < GFH_NA; a++) av[GFH_BNP + a] += G[a] * R;      // gadfit.F90:698
-    av[GFH_BNP + GFH_NA] += R * R;
-    Xc = Xn; Yc = Yn; Wc = Wn;
-  }
-#pragma unroll
-  for (int k = 0; k < GFH_BNACC; k++) S[k] = gfh_uni(gfh_wave_sum(av[k]));
-}
-// chi2() (gadfit.F90:1015-1034): every parameter passive, value only
-static __device__ __forceinline__ double gfh_b_chi2(const gfh_bdata& d, const double* __restrict__ P, int* status) {
-  double acc = 0.0, Xc, Yc, Wc;
-  GFH_BLOAD(Xc, Yc, Wc, d.b)
-  for (i64 i0 = d.b; i0 < d.e; i0 += 64) {
-    double Xn, Yn, Wn;
-    GFH_BLOAD(Xn, Yn, Wn, i0 + 64 < d.e ? i0 + 64 : i0)
-    const double r = (Yc - gfh_point_value(Xc, P, status, (const double*)nullptr, 0 GFH_MESH_NONE GFH_SLOT(i0 + d.lane))) * Wc;   // gadfit.F90:1024-1026
-    acc += r * r;
-    Xc = Xn; Yc = Yn; Wc = Wn;
-  }
-  return gfh_uni(gfh_wave_sum(acc));
-}
-// STEP 3 (gadfit.F90:715-735): omega_i = -f''_delta1(x_i) w_i and J^T omega with the Jacobian row recomputed, as gfh_k_omega_jt
-static __device__ __forceinline__ void gfh_b_omega(const gfh_bdata& d, const double* __restrict__ P, const double* __restrict__ DP, int* status,
-                                                   double (&JTo)[GFH_NA]) {
-  double acc[GFH_NA], Xc, Yc, Wc;
-#pragma unroll
-  for (int a = 0; a < GFH_NA; a++) acc[a] = 0.0;
-  GFH_BLOAD(Xc, Yc, Wc, d.b)
-  for (i64 i0 = d.b; i0 < d.e; i0 += 64) {
-    double Xn, Yn, Wn;
-    GFH_BLOAD(Xn, Yn, Wn, i0 + 64 < d.e ? i0 + 64 : i0)
-    double G[GFH_NA];
-    const double om = -gfh_point_dd_grad(Xc, P, DP, G, status, (const double*)nullptr, 0 GFH_MESH_NONE GFH_SLOT(i0 + d.lane)) * Wc;   // gadfit.F90:722-723
-#pragma unroll
-    for (int a = 0; a < GFH_NA; a++) {
-      const double j = G[a] * Wc;                              // gadfit.F90:689-690
-      acc[a] += j * om;                                        // gadfit.F90:734
-    }
-    Xc = Xn; Yc = Yn; Wc = Wn;
-  }
-  (void)Yc;
-#pragma unroll
-  for (int a = 0; a < GFH_NA; a++) JTo[a] = gfh_uni(gfh_wave_sum(acc[a]));
-}
-// (J^T J + lambda DTD) out = rhs (gadfit.F90:711-713): potrf_upper_plain and potrs_upper of lm.cpp operation for operation,
-// unrolled, without contraction (the host has none), so that this solve and the host's return the same bits from the same
-// sums.  false: a pivot that is not positive, or -- the one test the host's '!(ajj > 0.0)' does not make -- not finite: this fit's
-// normal equations are not positive definite.
-static __device__ __forceinline__ bool gfh_b_solve(const double (&S)[GFH_BNACC], const double (&DTD)[GFH_NA], const double lambda,
-                                                   const double (&rhs)[GFH_NA], double (&out)[GFH_NA]) {
-#pragma clang fp contract(off)
-  double U[GFH_NA][GFH_NA];                                    // U[k][j], k <= j: column j of the upper factor
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < GFH_NA; j++) {
-    double ajj = S[GFH_BIDX(j, j)] + lambda * DTD[j];
-#pragma unroll
-    for (int k = 0; k < j; k++) ajj -= U[k][j] * U[k][j];
-    ok = ok && ajj > 0.0 && ajj < __builtin_inf();
-    ajj = __builtin_sqrt(ajj); U[j][j] = ajj;
-    const double rinv = 1.0 / ajj;
-#pragma unroll
-    for (int c = j + 1; c < GFH_NA; c++) {
-      double t = S[GFH_BIDX(j, c)] + 0.0;
-#pragma unroll
-      for (int k = 0; k < j; k++) t -= U[k][j] * U[k][c];
-      U[j][c] = t * rinv;
-    }
-  }
-  if (!ok) return false;
-#pragma unroll
-  for (int i = 0; i < GFH_NA; i++) {
-    double t = rhs[i];
-#pragma unroll
-    for (int k = 0; k < i; k++) t -= U[k][i] * out[k];
-    out[i] = t / U[i][i];
-  }
-#pragma unroll
-  for (int k = GFH_NA - 1; k >= 0; k--) if (out[k] != 0.0) {
-    out[k] /= U[k][k];
-#pragma unroll
-    for (int i = 0; i < k; i++) out[i] -= out[k] * U[i][k];
-  }
-#pragma unroll
-  for (int i = 0; i < GFH_NA; i++) out[i] = gfh_uni(out[i]);
-  return true;
-}
-static __device__ __forceinline__ double gfh_b_dtd(const double (&a)[GFH_NA], const double (&DTD)[GFH_NA], const double (&b)[GFH_NA]) {
-#pragma clang fp contract(off)
-  double t = 0.0;
-#pragma unroll
-  for (int i = 0; i < GFH_NA; i++) t += a[i] * (DTD[i] * b[i]);       // dot(a, matmul(DTD, b)), DTD diagonal
-  return t;
-}
-
-// The whole fit of each spectrum (gadfit.F90:670-915).  Exit reasons as gfh_fit_result (0 max_iter, 1 chi2_abs, 2 chi2_rel, 5 rel_error,
-// 7 lambda raised lam_incs + 1 times in a row), and 8: the damped matrix was not positive definite -- that fit ends with the
-// parameters of its last accepted step, its neighbours go on.  uphill is 0 in a batch, so the acceptance test of gadfit.F90:761 is
-// new_chi2 < old_chi2 and old_delta1 (read only by its factor (1 - beta)**uphill) is not kept.
-extern "C" __global__ __launch_bounds__(256)
-void gfh_k_fit_batch(const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ w,
-                     const i64* __restrict__ off, double* __restrict__ pars, const gfh_batch_opts o,
-                     gfh_batch_rec* __restrict__ recs, const i64 n_fits, int* __restrict__ status) {
-#pragma clang fp contract(off)
-  const i64 f = (i64)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (f >= n_fits) return;
-  constexpr int act[GFH_NA] = GFH_BACT;
-  const gfh_bdata d = {x, y, w, off[f], off[f + 1], (int)(threadIdx.x & 63)};
-  double P[GFH_NP], old_pars[GFH_NA], DTD[GFH_NA], delta1[GFH_NA], delta2[GFH_NA], S[GFH_BNACC], JTr[GFH_NA];
-#pragma unroll
-  for (int k = 0; k < GFH_NP; k++) P[k] = gfh_uni(pars[f * GFH_NP + k]);
-#pragma unroll
-  for (int j = 0; j < GFH_NA; j++) { DTD[j] = o.dtd_min[j]; old_pars[j] = P[act[j]]; delta2[j] = 0.0; }      // gadfit.F90:641-646
-  const i64 dof_ = (d.e - d.b) - GFH_NA;                                                     // gadfit.F90:648-657
-  const double dof = dof_ == 0 ? 1.0 : (double)dof_;
-  double lambda = o.lambda;
-  int iterations = 0, exit_reason = -1, n_sweeps = 0, n_chi2 = 0, n_omega = 0;
-  double old_chi2 = gfh_b_chi2(d, P, status), new_chi2 = 0.0, old_old_chi2 = 0.0;             // gadfit.F90:670
-  n_chi2++;
-  for (;;) {
-    gfh_b_sweep(d, P, status, S);                                                             // STEP 1 + 2, gadfit.F90:675-701
-    n_sweeps++;
-#pragma unroll
-    for (int j = 0; j < GFH_NA; j++) {                                                        // gadfit.F90:702-710
-      const double dj = S[GFH_BIDX(j, j)];
-      DTD[j] = o.damp_plain ? dj : (DTD[j] > dj ? DTD[j] : dj);
-      JTr[j] = S[GFH_BNP + j];
-    }
-    if (!gfh_b_solve(S, DTD, lambda, JTr, delta1)) { exit_reason = 8; break; }                // gadfit.F90:711-713
-    if (o.use_accth) {                                                                        // STEP 3, gadfit.F90:715-743
-      double DP[GFH_NP], JTo[GFH_NA];
-#pragma unroll
-      for (int k = 0; k < GFH_NP; k++) DP[k] = 0.0;
-#pragma unroll
-      for (int j = 0; j < GFH_NA; j++) DP[act[j]] = delta1[j];
-      gfh_b_omega(d, P, DP, status, JTo);
-      n_omega++;
-      if (!gfh_b_solve(S, DTD, lambda, JTo, delta2)) { exit_reason = 8; break; }              // gadfit.F90:736-738 (the same matrix: the same factor)
-      const double acc_ratio = __builtin_sqrt(gfh_b_dtd(delta2, DTD, delta2) / gfh_b_dtd(delta1, DTD, delta1));
-      if (acc_ratio > o.accth) {
-#pragma unroll
-        for (int j = 0; j < GFH_NA; j++) delta2[j] = 0.0;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < GFH_NA; j++) P[act[j]] = P[act[j]] + delta1[j] + 0.5 * delta2[j];    // gadfit.F90:745-750
-    bool quit = false;
-    for (int i = 1; i <= o.lam_incs + 1; i++) {                                               // STEP 4, gadfit.F90:752-819
-      new_chi2 = gfh_b_chi2(d, P, status);
-      n_chi2++;
-      if (new_chi2 < old_chi2) {                                                              // gadfit.F90:761
-        lambda = lambda / o.lam_down;                                                         // gadfit.F90:780-782
-        break;
-      } else if (i <= o.lam_incs) {                                                           // gadfit.F90:785-808
-        lambda = o.lam_up * lambda;
-#pragma unroll
-        for (int j = 0; j < GFH_NA; j++) P[act[j]] = old_pars[j];
-        if (!gfh_b_solve(S, DTD, lambda, JTr, delta1)) { exit_reason = 8; quit = true; break; }
-#pragma unroll
-        for (int j = 0; j < GFH_NA; j++) P[act[j]] += delta1[j];
-      } else {                                                                                // gadfit.F90:809-816
-#pragma unroll
-        for (int j = 0; j < GFH_NA; j++) P[act[j]] = old_pars[j];
-        exit_reason = 7; quit = true; break;
-      }
-    }
-    if (quit) break;
-#pragma unroll
-    for (int j = 0; j < GFH_NA; j++) old_pars[j] = P[act[j]];                                 // gadfit.F90:821-827
-    old_old_chi2 = old_chi2;
-    old_chi2 = old_chi2 < new_chi2 ? old_chi2 : new_chi2;
-    iterations++;
-    // STEP 5 (gadfit.F90:835-915), in the reference's order
-    if (o.has_chi2_abs && old_chi2 / dof < o.chi2_abs) { exit_reason = 1; break; }
-    if (o.has_chi2_rel && (old_old_chi2 - old_chi2) / old_chi2 < o.chi2_rel) { exit_reason = 2; break; }
-    if (o.has_rel_error) {                                                                    // gadfit.F90:885-898
-      bool all = true;
-#pragma unroll
-      for (int j = 0; j < GFH_NA; j++) all = all && !(__builtin_fabs(delta1[j] / P[act[j]]) > o.rel_error);
-      if (all) { exit_reason = 5; break; }
-    }
-    if (o.has_max_iter && iterations >= o.max_iter) { exit_reason = 0; break; }              // gadfit.F90:911-915
-  }
-  if (d.lane == 0) {
-#pragma unroll
-    for (int j = 0; j < GFH_NA; j++) pars[f * GFH_NP + act[j]] = P[act[j]];
-    gfh_batch_rec r;
-    r.iterations = iterations; r.exit_reason = exit_reason; r.n_sweeps = n_sweeps; r.n_chi2 = n_chi2; r.n_omega = n_omega;
-    r.dof = dof_ == 0 ? 1 : (dof_ > 2147483647LL ? 2147483647 : (int)dof_);
-    r.lambda = lambda; r.chi2 = old_chi2;
-    recs[f] = r;
-  }
-}
-
-// STEP 1 + 2 only, at given parameters: each fit's J^T J [na x na] (both triangles), J^T r [na] and chi2 -- the "one pass" of
-// callers with their own loop.  img [n_fits][na * na + na + 1].
-extern "C" __global__ __launch_bounds__(256)
-void gfh_k_batch_pass(const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ w,
-                      const i64* __restrict__ off, const double* __restrict__ pars, double* __restrict__ img,
-                      const i64 n_fits, int* __restrict__ status) {
-  const i64 f = (i64)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (f >= n_fits) return;
-  const gfh_bdata d = {x, y, w, off[f], off[f + 1], (int)(threadIdx.x & 63)};
-  double P[GFH_NP], S[GFH_BNACC];
-#pragma unroll
-  for (int k = 0; k < GFH_NP; k++) P[k] = gfh_uni(pars[f * GFH_NP + k]);
-  gfh_b_sweep(d, P, status, S);
-  if (d.lane == 0) {
-    double* __restrict__ out = img + f * (GFH_NA * GFH_NA + GFH_NA + 1);
-#pragma unroll
-    for (int a = 0; a < GFH_NA; a++)
-#pragma unroll
-      for (int b = 0; b < GFH_NA; b++) out[a * GFH_NA + b] = a <= b ? S[GFH_BIDX(a, b)] : S[GFH_BIDX(b, a)];
-#pragma unroll
-    for (int a = 0; a < GFH_NA; a++) out[GFH_NA * GFH_NA + a] = S[GFH_BNP + a];
-    out[GFH_NA * GFH_NA + GFH_NA] = S[GFH_BNP + GFH_NA];
-  }
-}
-)";
+  s << kBatchFit;                   // batch_fit.hip: gfh_k_fit_batch, gfh_k_batch_pass
   return true;
 }
 
@@ -1686,98 +1197,12 @@ bool generate_source(const Model& m, const std::vector<int32_t>& active, const G
     << "\n#define GFH_STORE_J " << (cfg.store_j ? 1 : 0) << "\n#define GFH_STORE_RES " << (cfg.store_res ? 1 : 0) << "\n#define GFH_LOSS " << cfg.loss << "\n#define GFH_BLOCK " << cfg.block << "\n#define GFH_NP " << NP
     << "\n#define GFH_NA " << (NA > 0 ? NA : 1) << "\n#define GFH_VALU_GRAM_MAX " << kValuGramMax << "\n#define GFH_AD_PRIO " << (cfg.store_j ? 0 : 1) << "\n";
   s << "#define GFH_PARG " << cfg.kernarg_pars << "\n";
-  s << R"(
-// exp(x): the operations of the device library's exp (ROCm device-libs, __ocml_exp_f64: n = rint(x log2 e), two-step
-// Cody-Waite reduction, its degree-11 polynomial, ldexp), so the same bits for every x that is not a NaN.  What differs
-// is how the ends of the range are handled: the library computes ldexp(p, n) and then SELECTS +inf for x > 1024 and 0 for
-// x < -1075 -- two v_cmp_f64 and three v_cndmask_b32 per call, and a v_cndmask_b32 that takes its mask from VCC costs
-// 16-18 cycles per wave on gfx950 against 4-5 for an FP64 multiply-add (tools/microbench/fp64_rates.hip): a third of the
-// call.  Here x is clamped to [-1075, 1024] first (two full-rate instructions; ldexp then overflows to +inf and
-// underflows to 0 by itself, at the same x), and the one thing a clamp loses -- a NaN argument -- is put back with a
-// compare into an SGPR pair and a select on the high word that takes its mask from there (4-5 cycles each).
-typedef int int2_t_ __attribute__((ext_vector_type(2)));
-static __device__ __forceinline__ double gfh_exp(const double x) {
-  const double xc = __builtin_fmin(__builtin_fmax(x, -1075.0), 1024.0);
-  const double dn = __builtin_rint(xc * 0x1.71547652b82fep+0);
-  double r = __builtin_fma(-dn, 0x1.62e42fefa39efp-1, xc);
-  r = __builtin_fma(-dn, 0x1.abc9e3b39803fp-56, r);
-  double p = __builtin_fma(r, 0x1.ade156a5dcb37p-26, 0x1.28af3fca7ab0cp-22);
-  p = __builtin_fma(r, p, 0x1.71dee623fde64p-19);
-  p = __builtin_fma(r, p, 0x1.a01997c89e6b0p-16);
-  p = __builtin_fma(r, p, 0x1.a01a014761f6ep-13);
-  p = __builtin_fma(r, p, 0x1.6c16c1852b7b0p-10);
-  p = __builtin_fma(r, p, 0x1.1111111122322p-7);
-  p = __builtin_fma(r, p, 0x1.55555555502a1p-5);
-  p = __builtin_fma(r, p, 0x1.5555555555511p-3);
-  p = __builtin_fma(r, p, 0x1.000000000000bp-1);
-  p = __builtin_fma(r, p, 1.0);
-  p = __builtin_fma(r, p, 1.0);
-  int2_t_ z = __builtin_bit_cast(int2_t_, __builtin_ldexp(p, (int)dn));
-  unsigned long long is_nan;
-  asm("v_cmp_u_f64 %0, %1, %1" : "=s"(is_nan) : "v"(x));
-  int hi = z.y;
-  asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(hi) : "v"(hi), "v"(0x7ff80000), "s"(is_nan));
-  z.y = hi;
-  return __builtin_bit_cast(double, z);
-}
-)";
+  s << kExp;                        // exp.hip: gfh_exp
   {
     bool has_pow = false;
     for (const SubTape& t_ : m.sub) for (const Node& nd : t_.nodes) if (nd.op == GFH_POW && !(nd.flags & GFH_F_REAL)) has_pow = true;
     for (const SubTape& t_ : m.more_evals) for (const Node& nd : t_.nodes) if (nd.op == GFH_POW && !(nd.flags & GFH_F_REAL)) has_pow = true;
-    if (has_pow && cfg.fast_div) s << R"(
-// x**a and ln x from ONE extended-precision logarithm.  The device library's pow is 226 VALU instructions (28 of them selects
-// on special cases), its log 98, and the derivative code of x**a wants both -- at every Kronrod node of every bisection of
-// a quadrature model.  Here: x = 2^e m with m in [sqrt(1/2), sqrt(2)), s = (m - 1) / (m + 1) as a double-double (the
-// quotient corrected by its own residual), ln m = 2 s + s z (2/3 + 2 z / 5 + ... + 2 z^9 / 21), z = s^2 (the truncation is
-// below 2^-60 of the result for |s| <= 0.1716); ln x = e ln 2 + ln m summed as a double-double; x**a = exp(a ln x) with the
-// low part of the product applied to first order.  About 90 VALU instructions for both results; measured against 60-digit
-// references (tests/test_gpu_parity.py, test_device_pow_accuracy): <= 3 ulp (1.3 from the logarithm and the product, the rest gfh_exp) for |a ln x| <= 700 and 2^-1022 <= x < inf.
-// Everything else -- x <= 0, subnormal, inf, NaN, overflowing exponents -- takes the library's pow and log, whose special
-// cases are the reference's (IEEE pow).
-static __device__ __forceinline__ double gfh_pow_ln(const double x, const double a, double& lnx) {
-  if (x >= 0x1p-1022 && x < __builtin_inf()) {
-    int e = __builtin_amdgcn_frexp_exp(x);
-    double m = __builtin_amdgcn_frexp_mant(x);                    // [0.5, 1)
-    if (m < 0x1.6a09e667f3bcdp-1) { m = m + m; e -= 1; }         // [sqrt(1/2), sqrt(2))
-    const double f = m - 1.0;                                      // exact
-    const double dh = 2.0 + f, dl = (2.0 - dh) + f;               // m + 1 as a double-double
-    double g = __builtin_amdgcn_rcp(dh);
-    g = __builtin_fma(__builtin_fma(-dh, g, 1.0), g, g);
-    g = __builtin_fma(__builtin_fma(-dh, g, 1.0), g, g);
-    const double sh = f * g;
-    const double sl = __builtin_fma(-sh, dl, __builtin_fma(-sh, dh, f)) * g;
-    const double z = sh * sh;
-    double p = __builtin_fma(z, 0x1.8618618618618p-4, 0x1.af286bca1af28p-4);      // 2/21, 2/19
-    p = __builtin_fma(z, p, 0x1.e1e1e1e1e1e1ep-4);                                  // 2/17
-    p = __builtin_fma(z, p, 0x1.1111111111111p-3);                                  // 2/15
-    p = __builtin_fma(z, p, 0x1.3b13b13b13b14p-3);                                  // 2/13
-    p = __builtin_fma(z, p, 0x1.745d1745d1746p-3);                                  // 2/11
-    p = __builtin_fma(z, p, 0x1.c71c71c71c71cp-3);                                  // 2/9
-    p = __builtin_fma(z, p, 0x1.2492492492492p-2);                                  // 2/7
-    p = __builtin_fma(z, p, 0x1.999999999999ap-2);                                  // 2/5
-    p = __builtin_fma(z, p, 0x1.5555555555555p-1);                                  // 2/3
-    const double mh = sh + sh;
-    const double ml = __builtin_fma(sh * z, p, sl + sl);                           // ln m = mh + ml
-    const double ed = (double)e;
-    const double th = ed * 0x1.62e42fee00000p-1;                                    // e ln2_hi: exact (ln2_hi carries 32 trailing zero bits)
-    const double lh = th + mh;
-    const double bb = lh - th;
-    const double le = (th - (lh - bb)) + (mh - bb);                                // two-sum: th + mh = lh + le
-    const double ll = __builtin_fma(ed, 0x1.a39ef35793c76p-33, le + ml);           // + e ln2_lo
-    const double nh = lh + ll, nl = ll - (nh - lh);                                // renormalised: ln x = nh + nl, |nl| <= ulp(nh) / 2
-    lnx = nh;
-    const double ph = a * nh;
-    const double pl = __builtin_fma(a, nl, __builtin_fma(a, nh, -ph));
-    if (__builtin_fabs(ph) < 700.0) {
-      const double r = gfh_exp(ph);
-      return __builtin_fma(r, pl, r);
-    }
-  }
-  lnx = log(x);
-  return pow(x, a);
-}
-)";
+    if (has_pow && cfg.fast_div) s << kPowLn;      // pow_ln.hip: gfh_pow_ln
   }
   bool lane_stash = false;          // some integrand reads the data point's abscissa or auxiliary columns (Gen::in_integrand)
   for (size_t k = 1; k < m.sub.size(); k++) for (const Node& nd : m.sub[k].nodes) if (nd.op == GFH_X || nd.op == GFH_AUX) lane_stash = true;
@@ -1789,28 +1214,7 @@ static __device__ __forceinline__ double gfh_pow_ln(const double x, const double
          "__shared__ double gfh_lane_x[512];\n__shared__ const double* gfh_lane_axp[512];\n__shared__ i64 gfh_lane_lda;\n"
          "#define GFH_LANE_STASH gfh_lane_x[threadIdx.x] = X; gfh_lane_axp[threadIdx.x] = AXP; gfh_lane_lda = LDA;\n";
   else s << "#define GFH_LANE_STASH\n";
-  s << R"(
-// The parameter block [n_datasets][GFH_NP].  Up to 480 doubles (GFH_PARG = n_datasets * GFH_NP) it travels in the
-// kernel-argument segment: no host-to-device copy is queued in front of every pass, and the
-// parameters are scalar loads from the kernarg pointer.  Otherwise it is a device array.
-#if GFH_PARG
-struct gfh_parg { double v[GFH_PARG]; };
-#define GFH_PARS_DECL const gfh_parg pars
-#define GFH_DPARS_DECL const gfh_parg dpars
-#if GFH_PARG == GFH_NP
-#define GFH_PARS_AT(ds) pars.v
-#define GFH_DPARS_AT(ds) dpars.v
-#else
-#define GFH_PARS_AT(ds) (pars.v + (ds) * GFH_NP)      // wave-uniform dataset index: scalar loads at a register offset
-#define GFH_DPARS_AT(ds) (dpars.v + (ds) * GFH_NP)
-#endif
-#else
-#define GFH_PARS_DECL const double* __restrict__ pars
-#define GFH_PARS_AT(ds) (pars + (i64)(ds) * GFH_NP)
-#define GFH_DPARS_DECL const double* __restrict__ dpars
-#define GFH_DPARS_AT(ds) (dpars + (i64)(ds) * GFH_NP)
-#endif
-)";
+  s << kParsBlock;                  // pars_block.hip: GFH_PARS_DECL / GFH_PARS_AT
   if (m.has_integrals()) {
     const double *roots = gk15_roots, *wg = gk15_wg, *wk = gk15_wk; int npts = 15;
     switch (m.gk_points) {
@@ -2033,1000 +1437,8 @@ static __device__ __forceinline__ double gfh_point_dd(const double X, const doub
     emit_value_fn(st, "", " GFH_SLOT_DECL");
     emit_dd_fn(st, "", " GFH_SLOT_DECL");
   }
-  // ---- hand-written kernel skeletons (the model body above is the only generated part)
-  s << R"(
-// Device layout (DESIGN.md "Data layout"): slots are data points padded per dataset to a
-// multiple of the tile so every tile is full and belongs to one dataset; pad slots carry
-// w = 0.  x, y, w, res, omega: [n_slots]; J: [NA][ldj] (parameter-major: a wave's store of
-// one Jacobian column is 64 consecutive doubles = one fully coalesced 512 B write).
-#define GFH_TILE GFH_BLOCK
-
-// Robust cost of the C++ solver (lm_solver.cpp:255-284, 303-317): the weighted residual and its
-// Jacobian row are scaled by sqrt(rho'(res^2)); chi2() stays the plain sum (lm_solver.cpp:513-529).
-#if GFH_LOSS == 1
-#define GFH_ROBUST(R, Wv) { const double ls_ = sqrt(1.0 / (1.0 + (R) * (R))); R *= ls_; Wv *= ls_; }
-#elif GFH_LOSS == 2
-#define GFH_ROBUST(R, Wv) { const double ls_ = (R) * (R) > 1.0 ? sqrt(1.0 / fabs(R)) : 1.0; R *= ls_; Wv *= ls_; }
-#else
-#define GFH_ROBUST(R, Wv)
-#endif
-
-typedef double gfh_d4 __attribute__((ext_vector_type(4)));
-typedef int gfh_v2i __attribute__((ext_vector_type(2)));
-
-// One wave stores 64 consecutive doubles at a WAVE-UNIFORM base: buffer_store_dwordx2 with
-// the descriptor in SGPRs (built by scalar adds) and a 32-bit lane offset -- no per-lane
-// 64-bit address VALU work and half the address bytes through the vector-memory issue path.
-static __device__ __forceinline__ void gfh_store64(double* base, const int lane8, const double v) {
-  __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, 512, 0x00020000);
-  __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(gfh_v2i, v), rs, lane8, 0, 2);   // aux 2 = nt: written once, streamed
-}
-
-extern "C" __global__ __launch_bounds__(GFH_BLOCK) GFH_OCC
-void gfh_k_sweep(const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ w,
-                 GFH_PARS_DECL, const int* __restrict__ tile_ds, const int n_tiles,
-                 double* __restrict__ res, double* __restrict__ J, const i64 ldj, int* __restrict__ status,
-                 const double* __restrict__ aux, const i64 lda GFH_MESH_KPARAMS GFH_ORDER_KPARAMS GFH_WSG_KPARAMS) {
-  GFH_WSG_INIT
-  for (int tb = blockIdx.x; tb < n_tiles; tb += gridDim.x) {
-    const int t = GFH_ORD(tb);
-#if GFH_HAS_ORDER
-    const unsigned long long c0_ = __builtin_amdgcn_s_memtime();
-#endif
-    const double* __restrict__ P = GFH_PARS_AT(tile_ds[t]);   // wave-uniform: scalar loads
-    const i64 i = (i64)t * GFH_TILE + threadIdx.x;
-    const i64 iw = (i64)t * GFH_TILE + 64 * __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // this wave's first slot
-    const int lane8 = (threadIdx.x & 63) * 8;
-    const double X = x[i], Y = y[i];
-    double W = w[i];
-    double F, G[GFH_NA];
-    gfh_point_grad(X, P, F, G, status, aux + i, lda GFH_MESH_AT(i) GFH_SLOT(i));
-    double R = (Y - F) * W;                     // gadfit.F90:682-683
-    GFH_ROBUST(R, W)
-    gfh_store64(res + iw, lane8, R);
-#pragma unroll
-    for (int a = 0; a < GFH_NA; a++) gfh_store64(J + (i64)a * ldj + iw, lane8, G[a] * W);   // gadfit.F90:689-690
-#if GFH_HAS_ORDER
-    if (cost && threadIdx.x == 0) { const unsigned long long d_ = (__builtin_amdgcn_s_memtime() - c0_) >> 6; cost[t] = d_ < 0x7fffffffull ? (int)d_ : 0x7fffffff; }
-#endif
-  }
-}
-
-// Cross-workgroup hand-off without fences (MI355X_MICROARCH.md, "Workgroup dispatch, XCD placement &
-// inter-workgroup visibility", valid forms and the table's first row): every handed-off byte is stored `sc1` (write-through,
-// past the XCD's L2), every storing wave drains (`s_waitcnt vmcnt(0)`) before a workgroup barrier, one lane then adds to
-// an agent-scope counter, and the workgroup whose add came last reads the bytes with `sc1` loads -- global_ instructions,
-// never flat_: the pointers are cast to the global address space so the compiler cannot fall back to flat accesses.
-#define GFH_GLOBAL(p) ((__attribute__((address_space(1))) __typeof__(*(p))*)(p))
-#define GFH_ST_DEV(p, v) __hip_atomic_store(GFH_GLOBAL(p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define GFH_LD_DEV(p) __hip_atomic_load(GFH_GLOBAL(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define GFH_ST_SYS(p, v) __hip_atomic_store(GFH_GLOBAL(p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)
-
-// lane l reads lane l + N of its row of 16 (DPP row_shl:N; lanes that would read past the row get 0): the low levels of a wave tree
-template <int N> static __device__ __forceinline__ double gfh_row_down(const double v) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)b, 0x100 | N, 0xf, 0xf, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), 0x100 | N, 0xf, 0xf, true);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-// the wave tree t_l += t_(l+32), (l+16), (l+8), (l+4), (l+2), (l+1) -- lane 0 ends with the sum, the additions of the __shfl_down loop it
-// replaces bit for bit -- with the four levels inside a row as DPP moves instead of trips through the LDS crossbar (ds_bpermute)
-static __device__ __forceinline__ double gfh_wave_sum(double t) {
-  t += __shfl_down(t, 32, 64);
-  t += __shfl_down(t, 16, 64);
-  t += gfh_row_down<8>(t); t += gfh_row_down<4>(t); t += gfh_row_down<2>(t); t += gfh_row_down<1>(t);
-  return t;
-}
-
-// (the fused kernels exist for up to 128 active parameters = 8 tiles, model.h kFusedMaxActive / fused_max_active; beyond that STEP 1 and STEP 2 run as
-// gfh_k_sweep + k_gram_block launches; models whose quadrature workspaces are the global pool never run them: launch.cpp, fusable_model)
-#if GFH_NA <= GFH_FUSED_MAX && !GFH_WSG
-// Fused STEP 1 + STEP 2 (gadfit.F90:675-699): the sweep above plus J^T J / J^T r / sum r^2 of
-// the same points on the FP64 matrix cores, so J is written once and never re-read.
-// One wave = 64 points per pass.  After the AD body each lane holds its point's weighted
-// gradient; the wave transposes it through a private LDS stage [row = parameter][col = point]
-// (stride 66 doubles: the 16 rows x 2 columns a half-wave reads hit 32 distinct bank pairs)
-// into v_mfma_f64_16x16x4_f64 fragments: lane (r = l&15, q = l>>4) reads stage[16t+r][4s+q]
-// for k-step s; the same fragment is A operand of row tile t and B operand of column tile t.
-// Workgroup partial layout is identical to k_gram's, so the reduction/assembly kernels are shared.
-#define GFH_T ((GFH_NA + 15) / 16)
-#define GFH_NPAIR (GFH_T * (GFH_T + 1) / 2)
-// GFH_HALF: the stage holds 32 points (stride 34) and a pass runs as two half-passes -- lanes 0-31 stage their points and the
-// matrix cores take k-steps 0-7, then lanes 32-63 and k-steps 8-15: the k-steps in the order of the full stage, so the same sums
-// bit for bit, for half the LDS per wave (more waves per SIMD; the gradient of the upper half waits in registers meanwhile).
-#if GFH_HALF
-#define GFH_S 34
-#define GFH_NH 2
-#define GFH_KS 8
-#else
-#define GFH_S 66
-#define GFH_NH 1
-#define GFH_KS 16
-#endif
-// Descriptor of the fused kernel's tail (filled by the host, launch.cpp TailDesc).
-struct gfh_tail {
-  const int* ds_first_gb;          // [nd+1] first workgroup of each dataset
-  const int* inv;                  // [nd][dim] inverse of Jacobian_indices
-  double* slice;                   // [nd][32][pstride] slice sums
-  double* G;                       // [nd][pstride] per-dataset Gram images
-  double* packed;                  // [dim*dim + dim + 1]
-  double* host_out;                // pinned result mailbox
-  unsigned long long* host_flag;   // pinned sequence flag
-  unsigned* counters;              // [1 + nd*32], zero between launches
-  int nd, dim, n_slices, pad;
-};
-
-// GFH_FW waves per workgroup, kept in phase (__syncthreads between the AD phase and the matrix phase):
-// on gfx950 FP64 VALU and FP64 MFMA share one datapath and mixing the two kinds from different waves of
-// a SIMD costs throughput (tools/microbench/fp64_overlap.hip), so a SIMD runs one kind at a time.
-#define GFH_FTHREADS (64 * GFH_FW)
-// Without the Jacobian store (gfh_set_keep_jacobian) the kernel carries another name, so that
-// profiles keep the two apart.
-#if GFH_STORE_J
-#define GFH_K_SWEEP_GRAM gfh_k_sweep_gram
-#else
-#define GFH_K_SWEEP_GRAM gfh_k_sweep_gram_nostore
-#endif
-extern "C" __global__ __launch_bounds__(GFH_FTHREADS)
-void GFH_K_SWEEP_GRAM(const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ w,
-                      GFH_PARS_DECL, const i64* __restrict__ gb_start,
-                      const int* __restrict__ gb_slots, const int* __restrict__ gb_ds,
-                      double* __restrict__ res, double* __restrict__ J, const i64 ldj,
-                      double* __restrict__ partial, const int pstride, int* __restrict__ status, const double* __restrict__ aux, const i64 lda,
-                      const gfh_tail* __restrict__ tl, const unsigned long long seq, const int tail_mode) {
-#if GFH_NA <= GFH_VALU_GRAM_MAX
-  // Up to 8 active parameters a 16-row matrix tile would be half empty and the whole outer product of a point is
-  // NA (NA + 1) / 2 + NA + 1 <= 45 multiply-adds: it stays on the VALU, in per-lane accumulators -- no LDS stage, no
-  // transposition, no matrix instructions (16 of them per pass = 1024 cycles of the FP64 pipe against 180 here) -- and the
-  // kernel is left with the store stream.  Every lane sums its own points pass by pass; wave tree and the waves in order
-  // at the end (for sum r^2 that is gfh_k_chi2's order, as in the matrix path).  Same partial image as the matrix path.
-  constexpr int NP_ = GFH_NA * (GFH_NA + 1) / 2, NACC = NP_ + GFH_NA + 1;
-  __shared__ double red[GFH_FW][NACC];
-  __shared__ double tot[NACC];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const i64 s0 = gb_start[blockIdx.x];
-  const i64 e = s0 + gb_slots[blockIdx.x];                   // multiple of GFH_FTHREADS slots
-  const double* __restrict__ P = GFH_PARS_AT(gb_ds[blockIdx.x]);
-  double av[NACC];
-#pragma unroll
-  for (int k = 0; k < NACC; k++) av[k] = 0.0;
-  i64 iw = s0 + 64 * __builtin_amdgcn_readfirstlane(wv);
-  double Xc = (x + iw)[lane], Yc = (y + iw)[lane], Wc = (w + iw)[lane];
-  auto body = [&](const double XC, const double YC, const double WC) __attribute__((always_inline)) {
-    double* __restrict__ Jw = J + iw;
-    double F, G[GFH_NA];
-    gfh_point_grad(XC, P, F, G, status, aux + iw + lane, lda GFH_MESH_NONE GFH_SLOT(iw + lane));
-    double R = (YC - F) * WC;                               // gadfit.F90:682-683
-    double Wl = WC;
-    GFH_ROBUST(R, Wl)
-    gfh_store64(res + iw, lane * 8, R);
-#pragma unroll
-    for (int a = 0; a < GFH_NA; a++) {
-      G[a] = G[a] * Wl;                                     // gadfit.F90:689-690
-#if GFH_STORE_J
-      gfh_store64(Jw + (i64)a * ldj, lane * 8, G[a]);
-#endif
-    }
-    int p = 0;
-#pragma unroll
-    for (int a = 0; a < GFH_NA; a++)
-#pragma unroll
-      for (int b = a; b < GFH_NA; b++, p++) av[p] += G[a] * G[b];      // gadfit.F90:697
-#pragma unroll
-    for (int a = 0; a < GFH_NA; a++) av[NP_ + a] += G[a] * R;          // gadfit.F90:698
-    av[NP_ + GFH_NA] += R * R;
-  };
-  asm volatile("" :: "v"(Xc), "v"(Yc), "v"(Wc));             // (see the matrix path: keeps the per-pass wait a counted one)
-  for (; iw < e; iw += GFH_FTHREADS) {
-    const i64 in = iw + GFH_FTHREADS < e ? iw + GFH_FTHREADS : iw;
-    const double Xn = (x + in)[lane], Yn = (y + in)[lane], Wn = (w + in)[lane];
-    body(Xc, Yc, Wc);
-    Xc = Xn; Yc = Yn; Wc = Wn;
-  }
-  // wave tree of the NACC sums: t_l += t_(l+32), += t_(l+16) through the LDS crossbar (ds_bpermute, what __shfl_down compiles to), then
-  // += t_(l+8), (l+4), (l+2), (l+1) as DPP row shifts inside the 16 lanes of row 0 -- the additions __shfl_down's tree makes, the same
-  // bits, with a third of the crossbar operations: 45 sums x 6 levels x 2 halves = 540 ds_bpermute per wave, all waves of the chip
-  // at once at the end of the launch, were most of this kernel's epilogue (round 6)
-#pragma unroll
-  for (int k = 0; k < NACC; k++) {
-    const double t = gfh_wave_sum(av[k]);
-    if (lane == 0) red[wv][k] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < NACC) {
-    double t = red[0][threadIdx.x];
-#pragma unroll
-    for (int wq = 1; wq < GFH_FW; wq++) t += red[wq][threadIdx.x];
-    tot[threadIdx.x] = t;
-  }
-  __syncthreads();
-  double* out = partial + (i64)blockIdx.x * pstride;
-  __shared__ double tail_img[273];                                   // (read by the single-workgroup tail below)
-  for (int idx = threadIdx.x; idx < 273; idx += GFH_FTHREADS) {      // [16][16] tile (both triangles) | JTr[16] | rTr
-    double t;
-    if (idx < 256) {
-      int a = idx >> 4, b = idx & 15;
-      if (a > b) { const int t_ = a; a = b; b = t_; }
-      t = b < GFH_NA ? tot[a * GFH_NA - a * (a - 1) / 2 + (b - a)] : 0.0;
-    } else if (idx < 272) t = idx - 256 < GFH_NA ? tot[NP_ + idx - 256] : 0.0;
-    else t = tot[NP_ + GFH_NA];
-    GFH_ST_DEV(out + idx, t);
-    tail_img[idx] = t;
-  }
-#elif GFH_COOP
-  // ---- Workgroup-cooperative Gram (round 6): 81 ... 128 active parameters, 6 ... 8 tiles (model.h, fused_coop).  Up to 4 tiles every wave keeps ALL
-  // T (T + 1) / 2 accumulator tiles for its own 64 points; that grows as T^2 (15 tiles = 120 registers at T = 5, 36 = 288 at T = 8)
-  // next to a gradient of 2 NA registers that waits for the half-passes.  Here the waves still differentiate and stage their own
-  // points (half stages: 32 points, stride 34) but after a barrier every wave reads ALL stages of the workgroup and owns a contiguous
-  // run of the row-major list of tile pairs (GFH_CK = ceil(NPAIR / FW) of them: 4 ... 9 accumulator tiles): the registers stop
-  // growing as T^2, nothing spills, and no cross-wave reduction of the pair images is left -- a pair's accumulator IS the workgroup's
-  // sum.  Every pair is a plain v_mfma_f64_16x16x4_f64 on two fragments (the diagonal tiles too: their 4x4x4 form saves a third of
-  // a tile's cycles but needs rotated fragments per owner); J^T r of tile t rides with the owner of pair (t, t) on the VALU; sum r^2
-  // stays per lane over the lane's own points (gfh_k_chi2's order).  Points enter a pair's sum in the order stage of wave 0, 1, ...,
-  // half 0 then half 1, pass by pass: fixed, so deterministic.
-  constexpr int ROWS = 16 * GFH_T + 1;                       // parameters (padded to 16T) + residual row
-  constexpr int STAGE = ROWS * GFH_S;
-  constexpr int IMG = GFH_NPAIR * 256 + 16 * GFH_T + 1;      // the workgroup's sums (partial image)
-  constexpr int EPI = GFH_T * 64 + 8 + IMG;                  // epilogue: J^T r fragments per tile | wave sums of r^2 | the image, laid over the stages
-  static_assert(GFH_FW == 4, "the cooperative form is written for one wave per SIMD: GFH_CSTAGES / GFH_CPUT dispatch, coop_defines");
-  __shared__ double lds[GFH_FW * STAGE > EPI ? GFH_FW * STAGE : EPI];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int r = lane & 15, q = lane >> 4;
-  double* __restrict__ st = lds + wv * STAGE;
-  const i64 s0 = gb_start[blockIdx.x];
-  const i64 e = s0 + gb_slots[blockIdx.x];                   // multiple of GFH_FTHREADS slots
-  const double* __restrict__ P = GFH_PARS_AT(gb_ds[blockIdx.x]);
-#pragma unroll
-  for (int a = GFH_NA; a < 16 * GFH_T; a++) st[a * GFH_S + (lane & 31)] = 0.0;      // padding rows: zero once
-  // this wave's pairs: a contiguous run of the row-major upper triangle (generator: coop_defines -- per wave W the macros
-  // GFH_CLOAD_W(B, U): the fragments of the DISTINCT tiles its pairs touch, read once per k-step (a run of K pairs touches about
-  // K / 2 + 2 tiles: a third of the 2 K reads a pair-by-pair form makes, and the LDS reads were this kernel's bottleneck);
-  // GFH_CMMA_W(B): its matrix instructions and, for its diagonal pairs, J^T r on the VALU; GFH_CPUT_W: its part of the epilogue)
-  constexpr int CK = GFH_CK;
-  const int wvu = __builtin_amdgcn_readfirstlane(wv);
-  gfh_d4 acc[CK];
-  double accr[CK];
-#pragma unroll
-  for (int k = 0; k < CK; k++) { acc[k] = (gfh_d4){0.0, 0.0, 0.0, 0.0}; accr[k] = 0.0; }
-  double accc = 0.0;
-  i64 iw = s0 + 64 * __builtin_amdgcn_readfirstlane(wv);
-  double Xc = (x + iw)[lane], Yc = (y + iw)[lane], Wc = (w + iw)[lane];
-  asm volatile("" :: "v"(Xc), "v"(Yc), "v"(Wc));             // (see the matrix path below: keeps the per-pass wait a counted one)
-  for (; iw < e; iw += GFH_FTHREADS) {
-    const i64 in = iw + GFH_FTHREADS < e ? iw + GFH_FTHREADS : iw;
-    const double Xn = (x + in)[lane], Yn = (y + in)[lane], Wn = (w + in)[lane];
-    double F, G[GFH_NA];
-    gfh_point_grad(Xc, P, F, G, status, aux + iw + lane, lda GFH_MESH_NONE GFH_SLOT(iw + lane));
-    double R = (Yc - F) * Wc;                               // gadfit.F90:682-683
-    double Wl = Wc;
-    GFH_ROBUST(R, Wl)
-    gfh_store64(res + iw, lane * 8, R);
-    accc += R * R;                                          // every lane sums its own points pass by pass: the order gfh_k_chi2 uses
-#pragma unroll
-    for (int a = 0; a < GFH_NA; a++) {
-      G[a] = G[a] * Wl;                                     // gadfit.F90:689-690
-#if GFH_STORE_J
-      gfh_store64(J + iw + (i64)a * ldj, lane * 8, G[a]);
-#endif
-    }
-#pragma unroll 1
-    for (int h = 0; h < 2; h++) {
-      if ((lane >> 5) == h) {                                // this half's 32 points into the wave's stage
-        st[16 * GFH_T * GFH_S + (lane & 31)] = R;
-#pragma unroll
-        for (int a = 0; a < GFH_NA; a++) st[a * GFH_S + (lane & 31)] = G[a];
-      }
-      __syncthreads();
-      // 8 k-steps per stage, the stages in wave order; inside a stage the fragments of step u + 1 are read before the matrix
-      // instructions of step u (the stage loop itself stays a loop: unrolled over all 8 FW steps the kernel spilled hundreds of registers)
-#define GFH_CSTAGES(W_)                                                                                             \
-      _Pragma("unroll 1") for (int sw = 0; sw < GFH_FW; sw++) {                                                     \
-        const double* __restrict__ sb = lds + sw * STAGE;                                                           \
-        double f[2][GFH_CND], fr[2];                                                                                 \
-        GFH_CLOAD_##W_(0, 0)                                                                                        \
-        _Pragma("unroll") for (int u = 0; u < 8; u++) {                                                             \
-          /* the first matrix instruction of the step, THEN the next step's fragment reads (issued while it runs: a wave issues in   \
-             order, and reads in front of the step's first matrix instruction cost their whole issue time), then the rest */         \
-          __builtin_amdgcn_sched_barrier(0);                                                                        \
-          if (u & 1) { GFH_CMMA0_##W_(1) } else { GFH_CMMA0_##W_(0) }                                               \
-          __builtin_amdgcn_sched_barrier(0);                                                                        \
-          if (u + 1 < 8) { if (u & 1) { GFH_CLOAD_##W_(0, u + 1) } else { GFH_CLOAD_##W_(1, u + 1) } }              \
-          __builtin_amdgcn_sched_barrier(0);                                                                        \
-          if (u & 1) { GFH_CMMA_##W_(1) } else { GFH_CMMA_##W_(0) }                                                 \
-          __builtin_amdgcn_sched_barrier(0);                                                                        \
-        }                                                                                                           \
-      }
-#define GFH_MFMA(A_, B_, C_) C_ = __builtin_amdgcn_mfma_f64_16x16x4f64(A_, B_, C_, 0, 0, 0)
-      if (wvu == 0) { GFH_CSTAGES(0) }
-      else if (wvu == 1) { GFH_CSTAGES(1) }
-      else if (wvu == 2) { GFH_CSTAGES(2) }
-      else { GFH_CSTAGES(3) }
-      __syncthreads();
-    }
-    Xc = Xn; Yc = Yn; Wc = Wn;
-  }
-  // epilogue: the owners write their pairs straight into the workgroup's image (global partial + the LDS copy the one-workgroup tail reads)
-  double* vecs = lds;
-  double* wsum = lds + GFH_T * 64;
-  double* tail_img = wsum + 8;
-  double* out = partial + (i64)blockIdx.x * pstride;
-#define GFH_CPUT(K_, PP_)                                                                                            \
-  _Pragma("unroll") for (int j = 0; j < 4; j++) {       /* f64 16x16 C/D map: row = (l>>4) + 4*reg, column = l & 15 */ \
-    const int idx = (PP_) * 256 + (q + 4 * j) * 16 + r;                                                              \
-    GFH_ST_DEV(out + idx, acc[K_][j]);                                                                               \
-    tail_img[idx] = acc[K_][j]; }
-#define GFH_CPUTR(K_, T_) vecs[(T_) * 64 + lane] = accr[K_];
-  if (wvu == 0) { GFH_CPUT_0 }
-  else if (wvu == 1) { GFH_CPUT_1 }
-  else if (wvu == 2) { GFH_CPUT_2 }
-  else { GFH_CPUT_3 }
-  {
-    const double t = gfh_wave_sum(accc);                     // wave tree, then the waves in order: gfh_k_chi2's order
-    if (lane == 0) wsum[wv] = t;
-  }
-  __syncthreads();
-  for (int idx = threadIdx.x; idx < 16 * GFH_T; idx += GFH_FTHREADS) {
-    const int t = idx >> 4, rr_ = idx & 15;
-    const double sacc = ((vecs[t * 64 + rr_] + vecs[t * 64 + 16 + rr_]) + vecs[t * 64 + 32 + rr_]) + vecs[t * 64 + 48 + rr_];
-    GFH_ST_DEV(out + GFH_NPAIR * 256 + idx, sacc);
-    tail_img[GFH_NPAIR * 256 + idx] = sacc;
-  }
-  if (threadIdx.x == 0) {
-    double sacc = wsum[0];
-#pragma unroll
-    for (int wq = 1; wq < GFH_FW; wq++) sacc += wsum[wq];
-    GFH_ST_DEV(out + GFH_NPAIR * 256 + 16 * GFH_T, sacc);
-    tail_img[GFH_NPAIR * 256 + 16 * GFH_T] = sacc;
-  }
-#else
-  constexpr int ROWS = 16 * GFH_T + 1;                       // parameters (padded to 16T) + residual row
-  constexpr int STAGE = ROWS * GFH_S;
-  constexpr int RED = GFH_NPAIR * 256 + GFH_T * 64 + 4;      // cross-wave reduction image (as k_gram)
-  constexpr int IMG = GFH_NPAIR * 256 + 16 * GFH_T + 1;      // the workgroup's own sums (partial image), kept for the single-workgroup tail
-#if GFH_RED1
-  // 5 tiles: ONE pair image that the waves add into in order + the waves' J^T r / r^T r vectors + the workgroup's sums,
-  // laid over the stages once the pass loop is done (model.h, fused_lds_bytes_for)
-  constexpr int VEC = GFH_T * 64 + 4;
-  constexpr int RED1 = GFH_NPAIR * 256 + GFH_FW * VEC + IMG;
-  __shared__ double lds[GFH_FW * STAGE > RED1 ? GFH_FW * STAGE : RED1];
-#else
-  __shared__ double lds[GFH_FW * (STAGE > RED ? STAGE : RED)];
-#endif
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int r = lane & 15, q = lane >> 4;
-  double* __restrict__ st = lds + wv * STAGE;
-  const i64 s0 = gb_start[blockIdx.x];
-  const i64 e = s0 + gb_slots[blockIdx.x];                   // multiple of GFH_FTHREADS slots
-  const double* __restrict__ P = GFH_PARS_AT(gb_ds[blockIdx.x]);
-
-  // rows GFH_NA .. 16T-1 of the stage are padding: zero once
-#pragma unroll
-  for (int a = GFH_NA; a < 16 * GFH_T; a++) st[a * GFH_S + (lane & (64 / GFH_NH - 1))] = 0.0;
-
-  gfh_d4 acc[GFH_NPAIR];
-#pragma unroll
-  for (int p = 0; p < GFH_NPAIR; p++) acc[p] = (gfh_d4){0.0, 0.0, 0.0, 0.0};
-  // Diagonal tiles: only 10 of the 16 4x4 blocks of a symmetric 16x16 tile are distinct, and
-  // v_mfma_f64_4x4x4_4b_f64 (four independent 4x4 blocks, 17.5 cycles against 64, tools/microbench/mfma_4x4.hip) takes
-  // its A operand in exactly the fragment layout of the 16x16x4 form (lane = 16 k + 4 block + row).  With B = the same
-  // fragment it yields the four diagonal blocks (b,b); with B read from rows rotated by one block, (b,b+1 mod 4) -- which is
-  // (0,1) (1,2) (2,3) and (3,0) = (0,3) transposed; the remaining (0,2) (1,3) of TWO tiles share one more instruction whose
-  // lanes of blocks 0,1 read the first tile and those of blocks 2,3 the second (rows rotated by two blocks for B).
-  // 2.5 x 17.5 cycles per diagonal tile and k-step instead of 64.
-  constexpr int NMIX = GFH_T / 2;
-  double dga[GFH_T], dgb[GFH_T], dgm[NMIX + 1];
-#pragma unroll
-  for (int t = 0; t < GFH_T; t++) dga[t] = dgb[t] = 0.0;
-#pragma unroll
-  for (int m = 0; m <= NMIX; m++) dgm[m] = 0.0;
-  const int r4 = (r + 4) & 15, r8 = (r + 8) & 15, hi = r >> 3;
-  double accr[GFH_T];
-#pragma unroll
-  for (int t = 0; t < GFH_T; t++) accr[t] = 0.0;
-  double accc = 0.0;
-
-  // iw: first slot of this wave's pass, kept wave-uniform (SGPRs) so every global access is
-  // "scalar base + lane*8": no per-lane 64-bit address arithmetic, 32-bit offsets to the TA
-  i64 iw = s0 + 64 * __builtin_amdgcn_readfirstlane(wv);
-  // every workgroup owns at least one whole pass (gb_slots is a positive multiple of GFH_FTHREADS)
-  double Xc = (x + iw)[lane], Yc = (y + iw)[lane], Wc = (w + iw)[lane];
-  // The first pass's inputs are consumed here, outside the loop.  vmcnt counts loads and stores in
-  // issue order; if these loads were still pending at the loop header the compiler would have to
-  // wait for the loop-carried inputs with vmcnt(2) -- correct for this entry path, but on the
-  // back edge it means "every Jacobian store of the previous pass has completed": a full drain of
-  // the store queue at the top of every pass.  With a clean entry state the wait inside the loop
-  // is the counted one (the 3 prefetch loads are OLDER than the pass's stores).
-  asm volatile("" :: "v"(Xc), "v"(Yc), "v"(Wc));
-#if GFH_AD_PRIO
-  __builtin_amdgcn_s_setprio(3);                             // (the AD phase of the first pass; GenConfig::store_j)
-#endif
-  for (; iw < e; iw += GFH_FTHREADS) {
-    // prefetch the next pass's inputs before the long compute phase (the last pass re-reads its
-    // own: no branch, so the number of memory operations in flight is the same on every path)
-    const i64 in = iw + GFH_FTHREADS < e ? iw + GFH_FTHREADS : iw;
-    const double Xn = (x + in)[lane], Yn = (y + in)[lane], Wn = (w + in)[lane];
-    double* __restrict__ Jw = J + iw;
-    double F, G[GFH_NA];
-    gfh_point_grad(Xc, P, F, G, status, aux + iw + lane, lda GFH_MESH_NONE GFH_SLOT(iw + lane));
-    double R = (Yc - F) * Wc;                               // gadfit.F90:682-683
-    double Wl = Wc;
-    GFH_ROBUST(R, Wl)
-    gfh_store64(res + iw, lane * 8, R);
-    accc += R * R;                                          // every lane sums its own points pass by pass: the order gfh_k_chi2 uses
-#if !GFH_HALF
-    st[16 * GFH_T * GFH_S + lane] = R;
-#endif
-#pragma unroll
-    for (int a = 0; a < GFH_NA; a++) {
-      G[a] = G[a] * Wl;                                     // gadfit.F90:689-690
-#if !GFH_HALF
-      st[a * GFH_S + lane] = G[a];
-#endif
-    }
-#if GFH_STORE_J
-    // phase alignment (the stage itself is wave-private): with the Jacobian stores in the matrix phase the kernel is faster when
-    // the waves of a workgroup are in the same phase (0.53 against 0.58 ms); without them it is the FP64 pipe alone and any
-    // barrier is idle time (0.352 against 0.334 ms)
-    __syncthreads();
-#endif
-    // k-steps: the fragment reads of step s+1 are issued while the matrix instructions of step s run, so the
-    // LDS latency hides under them (sched_barrier pins the order)
-    double fn[GFH_T], f4n[GFH_T], man[NMIX + 1], mbn[NMIX + 1], rn;
-#define GFH_FRAGS(S_)                                                                                            \
-    _Pragma("unroll") for (int t = 0; t < GFH_T; t++) {                                                          \
-      fn[t] = st[(16 * t + r) * GFH_S + 4 * (S_) + q];                                                           \
-      f4n[t] = st[(16 * t + r4) * GFH_S + 4 * (S_) + q];                                                         \
-    }                                                                                                            \
-    _Pragma("unroll") for (int m = 0; m < NMIX; m++) {                                                           \
-      man[m] = st[(16 * (2 * m + hi) + r) * GFH_S + 4 * (S_) + q];                                               \
-      mbn[m] = st[(16 * (2 * m + hi) + r8) * GFH_S + 4 * (S_) + q];                                              \
-    }                                                                                                            \
-    if (GFH_T & 1) mbn[NMIX] = st[(16 * (GFH_T - 1) + r8) * GFH_S + 4 * (S_) + q];                               \
-    rn = st[16 * GFH_T * GFH_S + 4 * (S_) + q];
-#if GFH_AD_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
-#pragma unroll
-    for (int h = 0; h < GFH_NH; h++) {
-#if GFH_HALF
-      // this half's 32 points into the stage (the fragment reads of the half before are older LDS operations of this wave:
-      // the LDS executes a wave's operations in order)
-      if ((lane >> 5) == h) {
-        st[16 * GFH_T * GFH_S + (lane & 31)] = R;
-#pragma unroll
-        for (int a = 0; a < GFH_NA; a++) st[a * GFH_S + (lane & 31)] = G[a];
-      }
-#endif
-      // (the first k-step's reads stay a one-trip loop: written out straight they compile to another instruction order)
-#pragma unroll
-      for (int s = 0; s < 1; s++) { GFH_FRAGS(s) }
-#pragma unroll
-      for (int s = 0; s < GFH_KS; s++) {
-        double fa[GFH_T], f4[GFH_T], ma[NMIX + 1], mb[NMIX + 1];
-#pragma unroll
-        for (int t = 0; t < GFH_T; t++) { fa[t] = fn[t]; f4[t] = f4n[t]; }
-#pragma unroll
-        for (int m = 0; m <= NMIX; m++) { ma[m] = man[m]; mb[m] = mbn[m]; }
-        const double rr = rn;
-        __builtin_amdgcn_sched_barrier(0);
-        int p = 0;
-#pragma unroll
-        for (int ti = 0; ti < GFH_T; ti++)
-#pragma unroll
-          for (int tj = ti; tj < GFH_T; tj++, p++)
-            if (tj > ti) acc[p] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[ti], fa[tj], acc[p], 0, 0, 0);
-        // the next step's fragment reads go out BEHIND this step's 64-cycle matrix instructions (issued, they run by themselves):
-        // the wave's LDS instructions then cost the shared FP64 pipe no idle issue slots (round 5: no-store 0.3135 -> 0.299 ms,
-        // stored 0.209 -> 0.178 ms at N = 4e6, against the reads in front of them)
-        __builtin_amdgcn_sched_barrier(0);
-        if (s + 1 < GFH_KS) { GFH_FRAGS(s + 1) }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int t = 0; t < GFH_T; t++) {
-          dga[t] = __builtin_amdgcn_mfma_f64_4x4x4f64(fa[t], fa[t], dga[t], 0, 0, 0);
-          dgb[t] = __builtin_amdgcn_mfma_f64_4x4x4f64(fa[t], f4[t], dgb[t], 0, 0, 0);
-        }
-#pragma unroll
-        for (int m = 0; m < NMIX; m++) dgm[m] = __builtin_amdgcn_mfma_f64_4x4x4f64(ma[m], mb[m], dgm[m], 0, 0, 0);
-        if (GFH_T & 1) dgm[NMIX] = __builtin_amdgcn_mfma_f64_4x4x4f64(fa[GFH_T - 1], mb[NMIX], dgm[NMIX], 0, 0, 0);
-#pragma unroll
-        for (int t = 0; t < GFH_T; t++) accr[t] += fa[t] * rr;
-#if GFH_STORE_J
-        // Jacobian columns leave for HBM a few per k-step, under the matrix instructions,
-        // instead of as one burst that stalls the wave on a full store queue
-#pragma unroll
-        for (int a = (h * GFH_KS + s) * ((GFH_NA + 15) / 16); a < (h * GFH_KS + s + 1) * ((GFH_NA + 15) / 16) && a < GFH_NA; a++)
-          gfh_store64(Jw + (i64)a * ldj, lane * 8, G[a]);
-#endif
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-#if GFH_AD_PRIO
-    __builtin_amdgcn_s_setprio(3);
-#endif
-#if GFH_STORE_J
-    __syncthreads();
-#endif
-    Xc = Xn; Yc = Yn; Wc = Wn;
-  }
-
-#if GFH_AD_PRIO
-  __builtin_amdgcn_s_setprio(0);
-#endif
-#if GFH_RED1
-  // cross-wave reduction, 5 tiles: the waves add their accumulators into ONE image in wave order -- ((w0 + w1) + w2) + w3,
-  // the order in which the per-wave images of the smaller kernels are added -- then J^T r and r^T r from per-wave vectors as there
-  __syncthreads();                                           // (every wave is done with its stage: the image lies over them)
-  double* img1 = lds;
-  double* vecs = lds + GFH_NPAIR * 256;
-  double* tail_img = vecs + GFH_FW * VEC;
-#define GFH_PUT(IDX_, V_) { if (first) img1[IDX_] = (V_); else img1[IDX_] += (V_); }
-  for (int wq = 0; wq < GFH_FW; wq++) {
-    if (wv == wq) {
-      const bool first = wq == 0;
-      int p = 0;
-#pragma unroll
-      for (int ti = 0; ti < GFH_T; ti++)
-#pragma unroll
-        for (int tj = ti; tj < GFH_T; tj++, p++) {
-          if (tj > ti) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) GFH_PUT(p * 256 + (q + 4 * j) * 16 + r, acc[p][j])
-          } else {
-            const int row = (r & 12) + q;
-            GFH_PUT(p * 256 + row * 16 + r, dga[ti])
-            GFH_PUT(p * 256 + row * 16 + r4, dgb[ti])
-            GFH_PUT(p * 256 + r4 * 16 + row, dgb[ti])
-          }
-        }
-#pragma unroll
-      for (int m = 0; m < NMIX; m++) {
-        const int t = 2 * m + hi, pd = t * GFH_T - t * (t - 1) / 2, row = (r & 12) + q;
-        GFH_PUT(pd * 256 + row * 16 + r8, dgm[m])
-        GFH_PUT(pd * 256 + r8 * 16 + row, dgm[m])
-      }
-      if ((GFH_T & 1) && !hi) {
-        const int t = GFH_T - 1, pd = t * GFH_T - t * (t - 1) / 2, row = (r & 12) + q;
-        GFH_PUT(pd * 256 + row * 16 + r8, dgm[NMIX])
-        GFH_PUT(pd * 256 + r8 * 16 + row, dgm[NMIX])
-      }
-    }
-    __syncthreads();
-  }
-#undef GFH_PUT
-  {
-    double* myvec = vecs + wv * VEC;
-#pragma unroll
-    for (int t = 0; t < GFH_T; t++) myvec[t * 64 + lane] = accr[t];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) accc += __shfl_down(accc, off, 64);
-    if (lane == 0) myvec[GFH_T * 64] = accc;
-  }
-  __syncthreads();
-  double* out = partial + (i64)blockIdx.x * pstride;
-  for (int idx = threadIdx.x; idx < GFH_NPAIR * 256; idx += GFH_FTHREADS) {
-    const double sacc = img1[idx];
-    GFH_ST_DEV(out + idx, sacc);
-    tail_img[idx] = sacc;
-  }
-  for (int idx = threadIdx.x; idx < 16 * GFH_T; idx += GFH_FTHREADS) {
-    const int t = idx >> 4, rr_ = idx & 15;
-    double sacc = 0.0;
-#pragma unroll
-    for (int wq = 0; wq < 4 * GFH_FW; wq++) sacc += vecs[(wq >> 2) * VEC + t * 64 + (wq & 3) * 16 + rr_];
-    GFH_ST_DEV(out + GFH_NPAIR * 256 + idx, sacc);
-    tail_img[GFH_NPAIR * 256 + idx] = sacc;
-  }
-  if (threadIdx.x == 0) {
-    double sacc = vecs[GFH_T * 64];
-#pragma unroll
-    for (int wq = 1; wq < GFH_FW; wq++) sacc += vecs[wq * VEC + GFH_T * 64];
-    GFH_ST_DEV(out + GFH_NPAIR * 256 + 16 * GFH_T, sacc);
-    tail_img[GFH_NPAIR * 256 + 16 * GFH_T] = sacc;
-  }
-#else
-  // cross-wave reduction in fixed order (deterministic), same image as k_gram
-  __syncthreads();
-  double* mine = lds + wv * RED;
-  {
-    int p = 0;
-#pragma unroll
-    for (int ti = 0; ti < GFH_T; ti++)
-#pragma unroll
-      for (int tj = ti; tj < GFH_T; tj++, p++) {
-        if (tj > ti) {
-#pragma unroll
-          for (int j = 0; j < 4; j++) mine[p * 256 + (q + 4 * j) * 16 + r] = acc[p][j];   // f64 16x16 C/D map: row = (l>>4) + 4*reg
-        } else {
-          // 4x4x4 C/D map: lane = 16 row + 4 block + column; both triangles of the tile image are filled
-          const int row = (r & 12) + q;
-          mine[p * 256 + row * 16 + r] = dga[ti];
-          mine[p * 256 + row * 16 + r4] = dgb[ti];
-          mine[p * 256 + r4 * 16 + row] = dgb[ti];
-        }
-      }
-#pragma unroll
-    for (int m = 0; m < NMIX; m++) {
-      const int t = 2 * m + hi, pd = t * GFH_T - t * (t - 1) / 2, row = (r & 12) + q;
-      mine[pd * 256 + row * 16 + r8] = dgm[m];
-      mine[pd * 256 + r8 * 16 + row] = dgm[m];
-    }
-    if ((GFH_T & 1) && !hi) {             // (blocks 2,3 of the unpaired tile hold the transposes of blocks 0,1: one writer each)
-      const int t = GFH_T - 1, pd = t * GFH_T - t * (t - 1) / 2, row = (r & 12) + q;
-      mine[pd * 256 + row * 16 + r8] = dgm[NMIX];
-      mine[pd * 256 + r8 * 16 + row] = dgm[NMIX];
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < GFH_T; t++) mine[GFH_NPAIR * 256 + t * 64 + lane] = accr[t];
-  // sum r^2: wave tree, then the waves in order -- the same tree and order as gfh_k_chi2, so chi2() at the
-  // parameters of a sweep returns bitwise this sweep's sum
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) accc += __shfl_down(accc, off, 64);
-  if (lane == 0) mine[GFH_NPAIR * 256 + GFH_T * 64] = accc;
-  __syncthreads();
-  double* out = partial + (i64)blockIdx.x * pstride;
-  // (the sums also stay in LDS for the single-workgroup tail below: the pair images in tail_pairs, J^T r and r^T r behind them)
-  __shared__ double tail_img[GFH_NPAIR * 256 + 16 * GFH_T + 1];
-  for (int idx = threadIdx.x; idx < GFH_NPAIR * 256; idx += GFH_FTHREADS) {
-    double sacc = lds[idx];
-#pragma unroll
-    for (int wq = 1; wq < GFH_FW; wq++) sacc += lds[wq * RED + idx];
-    GFH_ST_DEV(out + idx, sacc);
-    tail_img[idx] = sacc;
-  }
-  for (int idx = threadIdx.x; idx < 16 * GFH_T; idx += GFH_FTHREADS) {
-    const int t = idx >> 4, rr_ = idx & 15;
-    double sacc = 0.0;
-#pragma unroll
-    for (int wq = 0; wq < 4 * GFH_FW; wq++) sacc += lds[(wq >> 2) * RED + GFH_NPAIR * 256 + t * 64 + (wq & 3) * 16 + rr_];
-    GFH_ST_DEV(out + GFH_NPAIR * 256 + idx, sacc);
-    tail_img[GFH_NPAIR * 256 + idx] = sacc;
-  }
-  if (threadIdx.x == 0) {
-    double sacc = lds[GFH_NPAIR * 256 + GFH_T * 64];
-#pragma unroll
-    for (int wq = 1; wq < GFH_FW; wq++) sacc += lds[wq * RED + GFH_NPAIR * 256 + GFH_T * 64];
-    GFH_ST_DEV(out + GFH_NPAIR * 256 + 16 * GFH_T, sacc);
-    tail_img[GFH_NPAIR * 256 + 16 * GFH_T] = sacc;
-  }
-#endif  // GFH_RED1
-#endif  // GFH_NA <= GFH_VALU_GRAM_MAX
-  if (!tail_mode) return;
-
-  // ---- tail (STEP 2's sum over workgroups, gadfit.F90:698-699, and the scatter through
-  // Jacobian_indices): what k_reduce_partials + k_assemble + k_publish do as three more launches,
-  // done here by the workgroups that finish last, in exactly their order of additions (bitwise the
-  // same numbers).  Level 1: the workgroups b0+sl, b0+sl+32, ... of a dataset form slice sl; the last
-  // of them to arrive adds their partials in ascending order.  Level 2: the workgroup that completes
-  // the last slice adds the 32 slice sums of every dataset in slice order, assembles the packed
-  // [JTJ | JTres | chi2] and (tail_mode 2) writes it, the status word and the call's sequence number
-  // into the host mailbox.
-  // Cross-workgroup traffic (partials, slice sums, counters) moves ONLY through device-scope atomic
-  // loads/stores (sc1: written through to / read from memory, past the per-XCD L2s, which are not
-  // coherent with each other), each producer waiting for its stores to be acknowledged (vmcnt(0))
-  // before its arrival is counted.  A release fence would do the same job by writing back the whole
-  // L2 -- which in this kernel is full of dirty Jacobian lines: measured +50 us per launch.
-  constexpr int W = GFH_NPAIR * 256 + 16 * GFH_T + 1;
-  __shared__ int role;
-  const int d = gb_ds[blockIdx.x];
-  // Assembly of the packed [JTJ | JTres | chi2] from per-dataset images (source `src`, image of dataset dd at src + dd * stride,
-  // datasets [d_lo, d_hi)), the scatter through Jacobian_indices, and (tail_mode 2) the host mailbox.
-  auto assemble_and_post = [&](auto at, const int d_lo, const int d_hi) {       // at(dd, k): entry k of dataset dd's image
-    const int dim = tl->dim;
-    const i64 nn = (i64)dim * dim, total = nn + dim + 1;
-    const int* __restrict__ inv = tl->inv;
-    double* packed = tl->packed;
-    double* host_out = tl->host_out;
-    for (i64 idx = threadIdx.x; idx < total; idx += GFH_FTHREADS) {
-      double v = 0.0;
-      if (idx < nn) {
-        const int col = (int)(idx / dim), row = (int)(idx % dim);
-        for (int dd = d_lo; dd < d_hi; dd++) {
-          int a = inv[dd * dim + row], b = inv[dd * dim + col];
-          if (a < 0 || b < 0) continue;
-          if (a > b) { const int t_ = a; a = b; b = t_; }     // upper triangle of tile pairs is stored
-          const int ti = a >> 4, tj = b >> 4;
-          const int p = ti * GFH_T - ti * (ti - 1) / 2 + (tj - ti);
-          v += at(dd, p * 256 + (a & 15) * 16 + (b & 15));
-        }
-      } else if (idx < nn + dim) {
-        const int row = (int)(idx - nn);
-        for (int dd = d_lo; dd < d_hi; dd++) {
-          const int a = inv[dd * dim + row];
-          if (a >= 0) v += at(dd, GFH_NPAIR * 256 + a);
-        }
-      } else {
-        for (int dd = d_lo; dd < d_hi; dd++) v += at(dd, GFH_NPAIR * 256 + 16 * GFH_T);
-      }
-      packed[idx] = v;
-      if (tail_mode == 2) GFH_ST_SYS(host_out + idx, v);       // pinned host memory is uncached: the store goes straight out
-    }
-    if (tail_mode != 2) {
-      // (one process per GPU: element `total` of the packed buffer is the status slot of the cross-rank sum that follows --
-      // 0, 1, 4096, 2^24 by code, so the sum over the ranks still tells which codes occurred: comm.cpp, allreduce_sum)
-      if (threadIdx.x == 0) packed[total] = GFH_STATUS_SLOT(GFH_LD_DEV(status));
-      return;
-    }
-    // the status word travels with the data (every workgroup's status updates were acknowledged before its arrival was
-    // counted, this workgroup's own before the barrier in front of this call): ONE wait for the stores to host memory, then the flag
-    if (threadIdx.x == 0) GFH_ST_SYS(host_out + total, (double)GFH_LD_DEV(status));
-    asm volatile("s_waitcnt vmcnt(0)\n" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(GFH_GLOBAL(tl->host_flag), seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  };
-  if (gridDim.x == 1) {
-    // One workgroup (the small fits most of gadfit's use consists of): its partial IS the sum over workgroups of its dataset --
-    // the two levels of the hand-off below would add 0.0 to it twice and cost five round trips to memory.  The same numbers
-    // (0.0 + t in the assembly, as there), bitwise.
-    // The sums are still in LDS (tail_img, written next to the partial image above): no trip through memory either.
-    __syncthreads();
-    assemble_and_post([&](int, int k) { return tail_img[k]; }, d, d + 1);
-    return;
-  }
-  const int b0 = tl->ds_first_gb[d], b1 = tl->ds_first_gb[d + 1];
-  const int sl = ((int)blockIdx.x - b0) & 31;
-  unsigned* cnt = tl->counters;
-  asm volatile("s_waitcnt vmcnt(0)\n" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned members = (unsigned)((b1 - b0 - sl + 31) >> 5);
-    const bool last = __hip_atomic_fetch_add(GFH_GLOBAL(cnt + 1 + d * 32 + sl), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == members - 1;
-    if (last) GFH_ST_DEV(cnt + 1 + d * 32 + sl, 0u);          // ready for the next launch (stream-ordered)
-    role = last;
-  }
-  __syncthreads();
-  if (!role) return;
-  {
-    double* sdst = tl->slice + ((i64)d * 32 + sl) * pstride;
-    for (int idx = threadIdx.x; idx < W; idx += GFH_FTHREADS) {
-      double sacc = 0.0;
-      for (int b = b0 + sl; b < b1; b += 32 * 16) {           // 16 loads in flight, added in ascending order
-        double v[16];
-#pragma unroll
-        for (int u = 0; u < 16; u++) v[u] = b + 32 * u < b1 ? GFH_LD_DEV(partial + (i64)(b + 32 * u) * pstride + idx) : 0.0;
-#pragma unroll
-        for (int u = 0; u < 16; u++) if (b + 32 * u < b1) sacc += v[u];
-      }
-      GFH_ST_DEV(sdst + idx, sacc);
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)\n" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const bool last = __hip_atomic_fetch_add(GFH_GLOBAL(cnt), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)tl->n_slices - 1;
-    if (last) GFH_ST_DEV(cnt, 0u);
-    role = last;
-  }
-  __syncthreads();
-  if (!role) return;
-  const int nd = tl->nd;
-  double* G = tl->G;                                          // written and read by this workgroup only
-  for (int dd = 0; dd < nd; dd++) {
-    const int nb = tl->ds_first_gb[dd + 1] - tl->ds_first_gb[dd];
-    const double* ssrc = tl->slice + (i64)dd * 32 * pstride;
-    for (int idx = threadIdx.x; idx < W; idx += GFH_FTHREADS) {
-      double v[32];
-#pragma unroll
-      for (int k = 0; k < 32; k++) v[k] = k < nb ? GFH_LD_DEV(ssrc + (i64)k * pstride + idx) : 0.0;
-      double t = v[0];
-#pragma unroll
-      for (int k = 1; k < 32; k++) t += v[k];
-      G[(i64)dd * pstride + idx] = t;
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)\n" ::: "memory");
-  __syncthreads();
-  assemble_and_post([&](int dd, int k) { return G[(i64)dd * pstride + k]; }, 0, nd);
-}
-
-#endif  // GFH_NA <= GFH_FUSED_MAX && !GFH_WSG
-
-// chi2() (gadfit.F90:1015-1034): every parameter passive, value only.  Same partition and thread-to-point
-// map as the fused kernel -- one workgroup of GFH_FW waves per gram block, wave wv of pass k takes the 64 slots
-// at s0 + 64 wv + k * 64 GFH_FW -- every lane sums its own points pass by pass, then the wave tree, the waves
-// in order, the workgroups by slices of 32 and the datasets in order: the order of additions of the fused
-// kernel's sum r^2, so chi2() is bitwise the sum a sweep at the same parameters returns (GFH_FAST_DIV = 1: the
-// reference's own value-only and active division forms differ by rounding, AD:814-913).  The parameter block
-// is fixed per workgroup, so parameter-only subexpressions (reciprocals of widths ...) leave the pass loop.
-// The next pass's inputs are loaded before the current pass's value is computed.
-// tail_mode 0: workgroup sums only; 1: the last workgroup to arrive adds them up into out[0]; 2: and posts
-// {sum, status} to the host mailbox.  The hand-off is the release / acquire form (MI355X_MICROARCH.md,
-// inter-workgroup visibility: valid for any number of workgroups per CU).
-#define GFH_CW (GFH_NA <= GFH_FUSED_MAX ? GFH_FW : 8)      // (beyond that there is no fused kernel to agree with)
-#define GFH_CTHREADS (64 * GFH_CW)
-extern "C" __global__ __launch_bounds__(GFH_CTHREADS) GFH_OCC
-void gfh_k_chi2(const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ w,
-                GFH_PARS_DECL, const i64* __restrict__ gb_start, const int* __restrict__ gb_slots,
-                const int* __restrict__ gb_ds, double* __restrict__ res, double* partial, int* __restrict__ status,
-                const double* __restrict__ aux, const i64 lda, const int* __restrict__ ds_first_gb, const int nd,
-                double* out, double* host_out, unsigned long long* host_flag, unsigned* counter,
-                const unsigned long long seq, const int tail_mode GFH_MESH_KPARAMS GFH_ORDER_KPARAMS GFH_WSG_KPARAMS) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  __shared__ double ws[GFH_CW];
-  __shared__ double sl_sum[512];
-  __shared__ double ds_sum[16];
-  __shared__ int role;
-  GFH_WSG_INIT
-#if GFH_WSG
-  // (workspaces in the global pool: the grid is capped at the pool's slots and a workgroup takes gram blocks blockIdx.x, + gridDim.x, ...;
-  // every sum is defined on the partition into gram blocks, so which workgroup does a block changes no bit)
-  for (int bb_ = blockIdx.x, nb_ = ds_first_gb[nd]; bb_ < nb_; bb_ += gridDim.x) {
-  const int B = GFH_ORD(bb_);
-#else
-  {
-  const int B = GFH_ORD(blockIdx.x);                                       // the gram block this workgroup works on
-#endif
-  const i64 s0 = gb_start[B];                                              // gb_slots: a positive multiple of GFH_CTHREADS slots
-  const double* __restrict__ P = GFH_PARS_AT(gb_ds[B]);
-  // Two passes per trip; the inputs of a trip are loaded during the trip before it, i.e. two passes (about a
-  // microsecond of arithmetic) ahead: one pass ahead is less than the latency of an HBM load under load, and the
-  // waves of a workgroup run in step, so they would all wait for it together.
-  const int np = gb_slots[B] / GFH_CTHREADS;                              // passes of this workgroup (wave-uniform)
-  const double* __restrict__ xb = x + s0 + threadIdx.x; const double* __restrict__ yb = y + s0 + threadIdx.x;
-  const double* __restrict__ wb = w + s0 + threadIdx.x; const double* __restrict__ ab = aux + s0 + threadIdx.x;
-  double* __restrict__ rb = res + s0 + threadIdx.x;
-  double X0 = xb[0], Y0 = yb[0], W0 = wb[0];
-  const i64 o1 = np > 1 ? GFH_CTHREADS : 0;
-  double X1 = xb[o1], Y1 = yb[o1], W1 = wb[o1];
-  double s = 0.0;
-  for (int k = 0; k < np; k += 2) {
-    const i64 oa = (i64)(k + 2 < np ? k + 2 : k) * GFH_CTHREADS, ob = (i64)(k + 3 < np ? k + 3 : k) * GFH_CTHREADS;
-    const double Xa = xb[oa], Ya = yb[oa], Wa = wb[oa], Xb = xb[ob], Yb = yb[ob], Wb = wb[ob];
-    const i64 oc = (i64)k * GFH_CTHREADS;
-    const double r0 = (Y0 - gfh_point_value(X0, P, status, ab + oc, lda GFH_MESH_AT(s0 + threadIdx.x + oc) GFH_SLOT(s0 + threadIdx.x + oc))) * W0;   // gadfit.F90:1024-1026
-#if GFH_STORE_RES
-    __builtin_nontemporal_store(r0, rb + oc);
-#endif
-    s += r0 * r0;
-    if (k + 1 < np) {
-      const double r1 = (Y1 - gfh_point_value(X1, P, status, ab + oc + GFH_CTHREADS, lda GFH_MESH_AT(s0 + threadIdx.x + oc + GFH_CTHREADS) GFH_SLOT(s0 + threadIdx.x + oc + GFH_CTHREADS))) * W1;
-#if GFH_STORE_RES
-      __builtin_nontemporal_store(r1, rb + oc + GFH_CTHREADS);
-#endif
-      s += r1 * r1;
-    }
-    X0 = Xa; Y0 = Ya; W0 = Wa; X1 = Xb; Y1 = Yb; W1 = Wb;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if (lane == 0) ws[wv] = s;
-  if (tail_mode) asm volatile("s_waitcnt vmcnt(0)\n" ::: "memory");       // this wave's status raise (if any) has landed
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double tot = ws[0];
-#pragma unroll
-    for (int k = 1; k < GFH_CW; k++) tot += ws[k];
-    partial[B] = tot;
-  }
-#if GFH_WSG
-  __syncthreads();                                                        // (ws[] is written again in the next round)
-#endif
-  }
-  if (threadIdx.x == 0) {
-    if (tail_mode) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)\n" ::: "memory");
-      const bool last = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
-      if (last) {
-        __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ready for the next launch (stream-ordered)
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)\n" ::: "memory");
-      }
-      role = last;
-    }
-  }
-  if (!tail_mode) return;
-  __syncthreads();
-  if (!role) return;
-  // level 1: slice sl of dataset d adds its workgroups b0+sl, b0+sl+32, ... in ascending order; level 2: the 32
-  // slice sums in slice order; level 3: the datasets in order (k_reduce_partials + k_gather_sum, and the fused tail)
-  double total = 0.0;
-  constexpr int DPR = GFH_CTHREADS / 32 < 16 ? GFH_CTHREADS / 32 : 16;     // datasets per round
-  for (int d0 = 0; d0 < nd; d0 += DPR) {
-    const int dl = threadIdx.x >> 5, sl = threadIdx.x & 31;
-    if (dl < DPR && d0 + dl < nd) {
-      const int b1 = ds_first_gb[d0 + dl + 1];
-      double a = 0.0;
-      for (int b = ds_first_gb[d0 + dl] + sl; b < b1; b += 32) a += partial[b];
-      sl_sum[dl * 32 + sl] = a;
-    }
-    __syncthreads();
-    if (threadIdx.x < DPR && d0 + (int)threadIdx.x < nd) {
-      double t = sl_sum[threadIdx.x * 32];
-#pragma unroll
-      for (int k = 1; k < 32; k++) t += sl_sum[threadIdx.x * 32 + k];
-      ds_sum[threadIdx.x] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) for (int k = 0; k < DPR && d0 + k < nd; k++) total += ds_sum[k];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    out[0] = total;
-    if (tail_mode == 1) out[1] = GFH_STATUS_SLOT(GFH_LD_DEV(status));      // the status slot of the cross-rank sum that follows
-    if (tail_mode == 2) {
-      GFH_ST_SYS(host_out, total);
-      GFH_ST_SYS(host_out + 1, (double)GFH_LD_DEV(status));
-      asm volatile("s_waitcnt vmcnt(0)\n" ::: "memory");
-      __hip_atomic_store(GFH_GLOBAL(host_flag), seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
-}
-
-// The tangent block of STEP 3 (delta1 per parameter).  Parameters and tangents are wave-uniform; with more than 16 of each
-// they no longer fit the scalar registers next to each other, and what the compiler then does with loop-invariant scalars
-// is to park them in VGPR lanes and fetch them back with v_readlane_b32 every pass (216 of them per pass at 32 parameters: a
-// quarter of the loop's VALU issue).  Re-reading the tangents through the scalar cache inside the loop (constant address
-// space, pointer made opaque so the loads stay in the loop) costs four s_load_dwordx16 per pass instead.
-typedef const double __attribute__((address_space(4))) * gfh_cptr;
-#if GFH_PARG
-// (by value with the kernel arguments: addressed through the kernarg segment itself -- x, w, pars, dpars are the first
-// four parameters of both STEP 3 kernels, so dpars sits at 16 + sizeof(gfh_parg); taking the address of the parameter
-// object instead would make the compiler copy it to scratch.  tests/test_cpu_generated_source.py checks the offset
-// against the code object's metadata.)
-#define GFH_DPARS_CONST(ds) ((gfh_cptr)((const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr() + 16 + sizeof(gfh_parg)) + (GFH_PARG == GFH_NP ? 0 : (ds) * GFH_NP))
-#else
-#define GFH_DPARS_CONST(ds) ((gfh_cptr)(unsigned long long)(dpars + (i64)(ds) * GFH_NP))
-#endif
-#if GFH_NP > 16
-#define GFH_TANGENTS(DPl, ds)                                                                  \
-  double DPl[GFH_NP];                                                                          \
-  { gfh_cptr c_ = GFH_DPARS_CONST(ds); asm volatile("" : "+s"(c_));                            \
-    _Pragma("unroll") for (int k_ = 0; k_ < GFH_NP; k_++) DPl[k_] = c_[k_]; }
-#else
-#define GFH_TANGENTS(DPl, ds) const double* __restrict__ DPl = GFH_DPARS_AT(ds);
-#endif
-
-// omega kernel (STEP 3, forward mode): a workgroup owns a CONTIGUOUS chunk of tiles.  When the whole chunk
-// lies in one dataset (always, unless a dataset boundary falls inside it) the parameter block is
-// fixed for the loop, so everything that depends on parameters only leaves the per-point code.  The host sizes
-// the grid to what is resident at once (launch.cpp, resident_grid), so no workgroup waits for a second round.
-extern "C" __global__ __launch_bounds__(GFH_BLOCK) GFH_OCC
-void gfh_k_omega(const double* __restrict__ x, const double* __restrict__ w,
-                 GFH_PARS_DECL, GFH_DPARS_DECL,
-                 const int* __restrict__ tile_ds, const int n_tiles, double* __restrict__ omega, int* __restrict__ status,
-                 const double* __restrict__ aux, const i64 lda GFH_MESH_KPARAMS GFH_ORDER_KPARAMS GFH_WSG_KPARAMS) {
-  GFH_WSG_INIT
-#if GFH_WSG
-  // (workspaces in the global pool: the grid is capped at the pool's slots; a workgroup takes tiles blockIdx.x, + gridDim.x, ... of
-  // the table sorted by cost, like gfh_k_sweep)
-  for (int tb = blockIdx.x; tb < n_tiles; tb += gridDim.x) {
-    const int t = GFH_ORD(tb);
-    const double* __restrict__ P = GFH_PARS_AT(tile_ds[t]);
-    const double* __restrict__ DP = GFH_DPARS_AT(tile_ds[t]);
-    for (i64 i = (i64)t * GFH_TILE + threadIdx.x; i < (i64)(t + 1) * GFH_TILE; i += GFH_BLOCK)
-      omega[i] = -gfh_point_dd(x[i], P, DP, status, aux + i, lda GFH_MESH_AT(i) GFH_SLOT(i)) * w[i];
-  }
-  return;
-#endif
-  // tiles split as evenly as integers allow: workgroup b takes [b n / G, (b + 1) n / G)
-  const int bi = gridDim.x == (unsigned)n_tiles ? GFH_ORD(blockIdx.x) : (int)blockIdx.x;      // (one tile per workgroup: in the order of cost)
-  const int t0 = (int)((i64)bi * n_tiles / gridDim.x), t1 = (int)((i64)(bi + 1) * n_tiles / gridDim.x);
-  if (t0 >= t1) return;
-  if (tile_ds[t0] == tile_ds[t1 - 1]) {
-    const double* __restrict__ P = GFH_PARS_AT(tile_ds[t0]);
-    const int ds0 = tile_ds[t0];                                 // delta1 scattered per dataset
-    const i64 e = (i64)t1 * GFH_TILE;
-    i64 i = (i64)t0 * GFH_TILE + threadIdx.x;
-    double Xc = x[i], Wc = w[i];
-    for (; i < e; i += GFH_BLOCK) {
-      const i64 in = i + GFH_BLOCK < e ? i + GFH_BLOCK : i;       // next pass's inputs (the last pass re-reads its own)
-      const double Xn = x[in], Wn = w[in];
-      GFH_TANGENTS(DPl, ds0)
-      omega[i] = -gfh_point_dd(Xc, P, DPl, status, aux + i, lda GFH_MESH_AT(i) GFH_SLOT(i)) * Wc;                  // gadfit.F90:722-723
-      Xc = Xn; Wc = Wn;
-    }
-  } else {
-    for (int t = t0; t < t1; t++) {
-      const double* __restrict__ P = GFH_PARS_AT(tile_ds[t]);
-      const double* __restrict__ DP = GFH_DPARS_AT(tile_ds[t]);
-      for (i64 i = (i64)t * GFH_TILE + threadIdx.x; i < (i64)(t + 1) * GFH_TILE; i += GFH_BLOCK)
-        omega[i] = -gfh_point_dd(x[i], P, DP, status, aux + i, lda GFH_MESH_AT(i) GFH_SLOT(i)) * w[i];
-    }
-  }
-}
-)";
+  // ---- the hand-written kernels, in this order (the model body above is the only generated part)
+  s << kSweep << kWaveSum << kFusedSweepGram << kChi2 << kOmega;
   if (cfg.omega_jt && !cfg.finite_diff && !m.has_integrals() && cfg.loss == 0 && NA <= 64) {
     // One data point, forward mode AND reverse mode over ONE evaluation of the forward values: the second directional
     // derivative along DP and the gradient.  The forward values are the expressions of gfh_point_grad / gfh_point_dd (the same
@@ -3053,72 +1465,10 @@ void gfh_k_omega(const double* __restrict__ x, const double* __restrict__ w,
       s << "    default:\n#pragma unroll\n      for (int a = 0; a < GFH_NA; a++) G[a] = 0.0;\n      gfh_report_unseen(STATUS, SLOT, path, ng); return 0.0;\n  }\n}\n";
     }
   }
-  if (cfg.omega_jt && !cfg.finite_diff && !m.has_integrals() && cfg.loss == 0 && NA <= 64) s << R"(
-// STEP 3 in one pass (gadfit.F90:715-735): omega_i = -f''_delta1(x_i) w_i in forward mode AND
-// J^T omega, with the Jacobian row of the point recomputed in registers (the reverse sweep of
-// gfh_k_sweep over the forward values the forward-mode pass has just formed: the same expressions,
-// so the same J_i) instead of re-read from HBM -- 8*p B/point
-// of traffic less than J^T omega from the stored Jacobian, and STEP 3 no longer needs J in HBM
-// at all.  One workgroup per gram block; the thread-to-point map, the order of additions, the wave
-// and workgroup reductions are those of k_jtv (kernels.hip), so partial[b][a] is bitwise what
-// k_jtv returns from the stored J.
-extern "C" __global__ __launch_bounds__(256)
-void gfh_k_omega_jt(const double* __restrict__ x, const double* __restrict__ w,
-                    GFH_PARS_DECL, GFH_DPARS_DECL,
-                    const i64* __restrict__ gb_start, const int* __restrict__ gb_slots, const int* __restrict__ gb_ds,
-                    double* __restrict__ omega, double* __restrict__ partial, const int pstride, int* __restrict__ status,
-                    const double* __restrict__ aux, const i64 lda) {
-  const i64 s0 = gb_start[blockIdx.x], e = s0 + gb_slots[blockIdx.x];
-  const double* __restrict__ P = GFH_PARS_AT(gb_ds[blockIdx.x]);
-  const int ds0 = gb_ds[blockIdx.x];
-  double acc[GFH_NA];
-#pragma unroll
-  for (int a = 0; a < GFH_NA; a++) acc[a] = 0.0;
-  for (i64 i = s0 + threadIdx.x; i < e; i += 256) {
-    const double X = x[i], W = w[i];                   // (no prefetch of the next pass here: at 32 parameters it would not fit 256 VGPRs)
-    double G[GFH_NA];
-    GFH_TANGENTS(DPl, ds0)
-    const double om = -gfh_point_dd_grad(X, P, DPl, G, status, aux + i, lda GFH_MESH_NONE GFH_SLOT(i)) * W;    // gadfit.F90:722-723
-    omega[i] = om;
-#pragma unroll
-    for (int a = 0; a < GFH_NA; a++) {
-      const double j = G[a] * W;                                                      // the stored J entry, gadfit.F90:689-690
-      acc[a] += j * om;                                                               // gadfit.F90:734
-    }
-  }
-  __shared__ double ws[GFH_NA][4];
-#pragma unroll
-  for (int a = 0; a < GFH_NA; a++) {
-    const double v = gfh_wave_sum(acc[a]);
-    if ((threadIdx.x & 63) == 0) ws[a][threadIdx.x >> 6] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < GFH_NA) partial[(i64)blockIdx.x * pstride + threadIdx.x] =
-      ((ws[threadIdx.x][0] + ws[threadIdx.x][1]) + ws[threadIdx.x][2]) + ws[threadIdx.x][3];
-}
-)";
+  if (cfg.omega_jt && !cfg.finite_diff && !m.has_integrals() && cfg.loss == 0 && NA <= 64) s << kOmegaJt;      // omega_jt.hip: gfh_k_omega_jt
   if (cfg.batch && !emit_batch_kernels(m, active, cfg, s, err)) return false;
   *src = s.str();
   return true;
 }
 
 }  // namespace gfh
-
-// The Gauss-Kronrod rule the kernels are generated with, for the Fortran layer's host-side integrate() (gadf_print and calls of
-// eval() outside gadf_fit: numerical_integration.F90, host_integral): reference node order, even 1-based positions = Gauss nodes.
-extern "C" __attribute__((visibility("default"))) int gfh_gk_rule(int points, double* roots, double* wg, double* wk) {
-  const double *r = nullptr, *g = nullptr, *k = nullptr;
-  if (!roots || !wg || !wk) return 1;
-  switch (points) {
-    case 15: r = gk15_roots; g = gk15_wg; k = gk15_wk; break;
-    case 21: r = gk21_roots; g = gk21_wg; k = gk21_wk; break;
-    case 31: r = gk31_roots; g = gk31_wg; k = gk31_wk; break;
-    case 41: r = gk41_roots; g = gk41_wg; k = gk41_wk; break;
-    case 51: r = gk51_roots; g = gk51_wg; k = gk51_wk; break;
-    case 61: r = gk61_roots; g = gk61_wg; k = gk61_wk; break;
-    default: return 1;
-  }
-  for (int i = 0; i < points; i++) { roots[i] = r[i]; wk[i] = k[i]; }
-  for (int i = 0; i < points / 2; i++) wg[i] = g[i];
-  return 0;
-}

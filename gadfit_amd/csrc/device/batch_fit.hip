@@ -1,0 +1,267 @@
+
+// ---- Batched independent fits: MANY Levenberg-Marquardt fits of this model in one launch, a wave per fit from its first chi2 to
+// its exit (gadfit.F90:670-915 restated per wave; lm.cpp gfh_fit is the host form of the same lines).  256 threads = 4 waves that
+// never talk to each other: no LDS, no barrier, no atomics; fit f = global wave index.  Lane l takes points off[f] + l, + 64, ...
+// of the fit's contiguous x, y, w (coalesced 512 B rows, no padding between fits); the lanes past the end of the last row re-read
+// the fit's last point with w = 0.  STEP 1+2 is the per-lane outer product of the fused kernel's VALU form (GFH_NA <=
+// GFH_VALU_GRAM_MAX) finished by gfh_wave_sum; the sums come back as wave-uniform values (v_readfirstlane) and every lane runs the
+// damped solve and the lambda logic on them redundantly -- the same operations on the same numbers, so the same decisions -- which
+// keeps the parameter block, the saved parameters and the normal equations in registers for the whole fit.
+#define GFH_BNP (GFH_NA * (GFH_NA + 1) / 2)
+#define GFH_BNACC (GFH_BNP + GFH_NA + 1)
+#define GFH_BIDX(a, b) ((a) * GFH_NA - (a) * ((a) - 1) / 2 + ((b) - (a)))      // packed upper triangle, a <= b
+struct gfh_batch_opts {          // the options of gfh_fit that the batch carries (batch.cpp fills it; absent values hold the reference's defaults)
+  double lambda, lam_up, lam_down, accth, chi2_abs, chi2_rel, rel_error;
+  double dtd_min[GFH_VALU_GRAM_MAX];
+  int lam_incs, max_iter, has_max_iter, use_accth, has_chi2_abs, has_chi2_rel, has_rel_error, damp_plain;
+};
+struct gfh_batch_rec { int iterations, exit_reason, n_sweeps, n_chi2, n_omega, dof; double lambda, chi2; };
+struct gfh_bdata { const double* __restrict__ x; const double* __restrict__ y; const double* __restrict__ w; i64 b, e; int lane; };
+
+static __device__ __forceinline__ double gfh_uni(const double v) {      // lane 0's value as a wave-uniform one
+  const long long b = __double_as_longlong(v);
+  const int lo = __builtin_amdgcn_readfirstlane((int)b), hi = __builtin_amdgcn_readfirstlane((int)(b >> 32));
+  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
+}
+// the inputs of pass row i0 (wave-uniform) for this lane; past the end: the last point with w = 0
+#define GFH_BLOAD(X, Y, W, i0) { const i64 i_ = (i0) + d.lane; const i64 c_ = i_ < d.e ? i_ : d.e - 1; \
+  X = d.x[c_]; Y = d.y[c_]; const double w_ = d.w[c_]; W = i_ < d.e ? w_ : 0.0; }
+
+// STEP 1 + 2 (gadfit.F90:675-699) of one fit: S = [J^T J upper triangle, packed | J^T r | sum r^2]
+static __device__ __forceinline__ void gfh_b_sweep(const gfh_bdata& d, const double* __restrict__ P, int* status, double (&S)[GFH_BNACC]) {
+  double av[GFH_BNACC];
+#pragma unroll
+  for (int k = 0; k < GFH_BNACC; k++) av[k] = 0.0;
+  double Xc, Yc, Wc;
+  GFH_BLOAD(Xc, Yc, Wc, d.b)
+  for (i64 i0 = d.b; i0 < d.e; i0 += 64) {
+    double Xn, Yn, Wn;
+    GFH_BLOAD(Xn, Yn, Wn, i0 + 64 < d.e ? i0 + 64 : i0)       // next row's inputs (the last row re-reads its own)
+    double F, G[GFH_NA];
+    gfh_point_grad(Xc, P, F, G, status, (const double*)nullptr, 0 GFH_MESH_NONE GFH_SLOT(i0 + d.lane));
+    const double R = (Yc - F) * Wc;                            // gadfit.F90:682-683
+#pragma unroll
+    for (int a = 0; a < GFH_NA; a++) G[a] = G[a] * Wc;         // gadfit.F90:689-690
+    int p = 0;
+#pragma unroll
+    for (int a = 0; a < GFH_NA; a++)
+#pragma unroll
+      for (int b = a; b < GFH_NA; b++, p++) av[p] += G[a] * G[b];      // gadfit.F90:697
+#pragma unroll
+    for (int a = 0; a < GFH_NA; a++) av[GFH_BNP + a] += G[a] * R;      // gadfit.F90:698
+    av[GFH_BNP + GFH_NA] += R * R;
+    Xc = Xn; Yc = Yn; Wc = Wn;
+  }
+#pragma unroll
+  for (int k = 0; k < GFH_BNACC; k++) S[k] = gfh_uni(gfh_wave_sum(av[k]));
+}
+// chi2() (gadfit.F90:1015-1034): every parameter passive, value only
+static __device__ __forceinline__ double gfh_b_chi2(const gfh_bdata& d, const double* __restrict__ P, int* status) {
+  double acc = 0.0, Xc, Yc, Wc;
+  GFH_BLOAD(Xc, Yc, Wc, d.b)
+  for (i64 i0 = d.b; i0 < d.e; i0 += 64) {
+    double Xn, Yn, Wn;
+    GFH_BLOAD(Xn, Yn, Wn, i0 + 64 < d.e ? i0 + 64 : i0)
+    const double r = (Yc - gfh_point_value(Xc, P, status, (const double*)nullptr, 0 GFH_MESH_NONE GFH_SLOT(i0 + d.lane))) * Wc;   // gadfit.F90:1024-1026
+    acc += r * r;
+    Xc = Xn; Yc = Yn; Wc = Wn;
+  }
+  return gfh_uni(gfh_wave_sum(acc));
+}
+// STEP 3 (gadfit.F90:715-735): omega_i = -f''_delta1(x_i) w_i and J^T omega with the Jacobian row recomputed, as gfh_k_omega_jt
+static __device__ __forceinline__ void gfh_b_omega(const gfh_bdata& d, const double* __restrict__ P, const double* __restrict__ DP, int* status,
+                                                   double (&JTo)[GFH_NA]) {
+  double acc[GFH_NA], Xc, Yc, Wc;
+#pragma unroll
+  for (int a = 0; a < GFH_NA; a++) acc[a] = 0.0;
+  GFH_BLOAD(Xc, Yc, Wc, d.b)
+  for (i64 i0 = d.b; i0 < d.e; i0 += 64) {
+    double Xn, Yn, Wn;
+    GFH_BLOAD(Xn, Yn, Wn, i0 + 64 < d.e ? i0 + 64 : i0)
+    double G[GFH_NA];
+    const double om = -gfh_point_dd_grad(Xc, P, DP, G, status, (const double*)nullptr, 0 GFH_MESH_NONE GFH_SLOT(i0 + d.lane)) * Wc;   // gadfit.F90:722-723
+#pragma unroll
+    for (int a = 0; a < GFH_NA; a++) {
+      const double j = G[a] * Wc;                              // gadfit.F90:689-690
+      acc[a] += j * om;                                        // gadfit.F90:734
+    }
+    Xc = Xn; Yc = Yn; Wc = Wn;
+  }
+  (void)Yc;
+#pragma unroll
+  for (int a = 0; a < GFH_NA; a++) JTo[a] = gfh_uni(gfh_wave_sum(acc[a]));
+}
+// (J^T J + lambda DTD) out = rhs (gadfit.F90:711-713): potrf_upper_plain and potrs_upper of lm.cpp operation for operation,
+// unrolled, without contraction (the host has none), so that this solve and the host's return the same bits from the same
+// sums.  false: a pivot that is not positive, or -- the one test the host's '!(ajj > 0.0)' does not make -- not finite: this fit's
+// normal equations are not positive definite.
+static __device__ __forceinline__ bool gfh_b_solve(const double (&S)[GFH_BNACC], const double (&DTD)[GFH_NA], const double lambda,
+                                                   const double (&rhs)[GFH_NA], double (&out)[GFH_NA]) {
+#pragma clang fp contract(off)
+  double U[GFH_NA][GFH_NA];                                    // U[k][j], k <= j: column j of the upper factor
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < GFH_NA; j++) {
+    double ajj = S[GFH_BIDX(j, j)] + lambda * DTD[j];
+#pragma unroll
+    for (int k = 0; k < j; k++) ajj -= U[k][j] * U[k][j];
+    ok = ok && ajj > 0.0 && ajj < __builtin_inf();
+    ajj = __builtin_sqrt(ajj); U[j][j] = ajj;
+    const double rinv = 1.0 / ajj;
+#pragma unroll
+    for (int c = j + 1; c < GFH_NA; c++) {
+      double t = S[GFH_BIDX(j, c)] + 0.0;
+#pragma unroll
+      for (int k = 0; k < j; k++) t -= U[k][j] * U[k][c];
+      U[j][c] = t * rinv;
+    }
+  }
+  if (!ok) return false;
+#pragma unroll
+  for (int i = 0; i < GFH_NA; i++) {
+    double t = rhs[i];
+#pragma unroll
+    for (int k = 0; k < i; k++) t -= U[k][i] * out[k];
+    out[i] = t / U[i][i];
+  }
+#pragma unroll
+  for (int k = GFH_NA - 1; k >= 0; k--) if (out[k] != 0.0) {
+    out[k] /= U[k][k];
+#pragma unroll
+    for (int i = 0; i < k; i++) out[i] -= out[k] * U[i][k];
+  }
+#pragma unroll
+  for (int i = 0; i < GFH_NA; i++) out[i] = gfh_uni(out[i]);
+  return true;
+}
+static __device__ __forceinline__ double gfh_b_dtd(const double (&a)[GFH_NA], const double (&DTD)[GFH_NA], const double (&b)[GFH_NA]) {
+#pragma clang fp contract(off)
+  double t = 0.0;
+#pragma unroll
+  for (int i = 0; i < GFH_NA; i++) t += a[i] * (DTD[i] * b[i]);       // dot(a, matmul(DTD, b)), DTD diagonal
+  return t;
+}
+
+// The whole fit of each spectrum (gadfit.F90:670-915).  Exit reasons as gfh_fit_result (0 max_iter, 1 chi2_abs, 2 chi2_rel, 5 rel_error,
+// 7 lambda raised lam_incs + 1 times in a row), and 8: the damped matrix was not positive definite -- that fit ends with the
+// parameters of its last accepted step, its neighbours go on.  uphill is 0 in a batch, so the acceptance test of gadfit.F90:761 is
+// new_chi2 < old_chi2 and old_delta1 (read only by its factor (1 - beta)**uphill) is not kept.
+extern "C" __global__ __launch_bounds__(256)
+void gfh_k_fit_batch(const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ w,
+                     const i64* __restrict__ off, double* __restrict__ pars, const gfh_batch_opts o,
+                     gfh_batch_rec* __restrict__ recs, const i64 n_fits, int* __restrict__ status) {
+#pragma clang fp contract(off)
+  const i64 f = (i64)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (f >= n_fits) return;
+  constexpr int act[GFH_NA] = GFH_BACT;
+  const gfh_bdata d = {x, y, w, off[f], off[f + 1], (int)(threadIdx.x & 63)};
+  double P[GFH_NP], old_pars[GFH_NA], DTD[GFH_NA], delta1[GFH_NA], delta2[GFH_NA], S[GFH_BNACC], JTr[GFH_NA];
+#pragma unroll
+  for (int k = 0; k < GFH_NP; k++) P[k] = gfh_uni(pars[f * GFH_NP + k]);
+#pragma unroll
+  for (int j = 0; j < GFH_NA; j++) { DTD[j] = o.dtd_min[j]; old_pars[j] = P[act[j]]; delta2[j] = 0.0; }      // gadfit.F90:641-646
+  const i64 dof_ = (d.e - d.b) - GFH_NA;                                                     // gadfit.F90:648-657
+  const double dof = dof_ == 0 ? 1.0 : (double)dof_;
+  double lambda = o.lambda;
+  int iterations = 0, exit_reason = -1, n_sweeps = 0, n_chi2 = 0, n_omega = 0;
+  double old_chi2 = gfh_b_chi2(d, P, status), new_chi2 = 0.0, old_old_chi2 = 0.0;             // gadfit.F90:670
+  n_chi2++;
+  for (;;) {
+    gfh_b_sweep(d, P, status, S);                                                             // STEP 1 + 2, gadfit.F90:675-701
+    n_sweeps++;
+#pragma unroll
+    for (int j = 0; j < GFH_NA; j++) {                                                        // gadfit.F90:702-710
+      const double dj = S[GFH_BIDX(j, j)];
+      DTD[j] = o.damp_plain ? dj : (DTD[j] > dj ? DTD[j] : dj);
+      JTr[j] = S[GFH_BNP + j];
+    }
+    if (!gfh_b_solve(S, DTD, lambda, JTr, delta1)) { exit_reason = 8; break; }                // gadfit.F90:711-713
+    if (o.use_accth) {                                                                        // STEP 3, gadfit.F90:715-743
+      double DP[GFH_NP], JTo[GFH_NA];
+#pragma unroll
+      for (int k = 0; k < GFH_NP; k++) DP[k] = 0.0;
+#pragma unroll
+      for (int j = 0; j < GFH_NA; j++) DP[act[j]] = delta1[j];
+      gfh_b_omega(d, P, DP, status, JTo);
+      n_omega++;
+      if (!gfh_b_solve(S, DTD, lambda, JTo, delta2)) { exit_reason = 8; break; }              // gadfit.F90:736-738 (the same matrix: the same factor)
+      const double acc_ratio = __builtin_sqrt(gfh_b_dtd(delta2, DTD, delta2) / gfh_b_dtd(delta1, DTD, delta1));
+      if (acc_ratio > o.accth) {
+#pragma unroll
+        for (int j = 0; j < GFH_NA; j++) delta2[j] = 0.0;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < GFH_NA; j++) P[act[j]] = P[act[j]] + delta1[j] + 0.5 * delta2[j];    // gadfit.F90:745-750
+    bool quit = false;
+    for (int i = 1; i <= o.lam_incs + 1; i++) {                                               // STEP 4, gadfit.F90:752-819
+      new_chi2 = gfh_b_chi2(d, P, status);
+      n_chi2++;
+      if (new_chi2 < old_chi2) {                                                              // gadfit.F90:761
+        lambda = lambda / o.lam_down;                                                         // gadfit.F90:780-782
+        break;
+      } else if (i <= o.lam_incs) {                                                           // gadfit.F90:785-808
+        lambda = o.lam_up * lambda;
+#pragma unroll
+        for (int j = 0; j < GFH_NA; j++) P[act[j]] = old_pars[j];
+        if (!gfh_b_solve(S, DTD, lambda, JTr, delta1)) { exit_reason = 8; quit = true; break; }
+#pragma unroll
+        for (int j = 0; j < GFH_NA; j++) P[act[j]] += delta1[j];
+      } else {                                                                                // gadfit.F90:809-816
+#pragma unroll
+        for (int j = 0; j < GFH_NA; j++) P[act[j]] = old_pars[j];
+        exit_reason = 7; quit = true; break;
+      }
+    }
+    if (quit) break;
+#pragma unroll
+    for (int j = 0; j < GFH_NA; j++) old_pars[j] = P[act[j]];                                 // gadfit.F90:821-827
+    old_old_chi2 = old_chi2;
+    old_chi2 = old_chi2 < new_chi2 ? old_chi2 : new_chi2;
+    iterations++;
+    // STEP 5 (gadfit.F90:835-915), in the reference's order
+    if (o.has_chi2_abs && old_chi2 / dof < o.chi2_abs) { exit_reason = 1; break; }
+    if (o.has_chi2_rel && (old_old_chi2 - old_chi2) / old_chi2 < o.chi2_rel) { exit_reason = 2; break; }
+    if (o.has_rel_error) {                                                                    // gadfit.F90:885-898
+      bool all = true;
+#pragma unroll
+      for (int j = 0; j < GFH_NA; j++) all = all && !(__builtin_fabs(delta1[j] / P[act[j]]) > o.rel_error);
+      if (all) { exit_reason = 5; break; }
+    }
+    if (o.has_max_iter && iterations >= o.max_iter) { exit_reason = 0; break; }              // gadfit.F90:911-915
+  }
+  if (d.lane == 0) {
+#pragma unroll
+    for (int j = 0; j < GFH_NA; j++) pars[f * GFH_NP + act[j]] = P[act[j]];
+    gfh_batch_rec r;
+    r.iterations = iterations; r.exit_reason = exit_reason; r.n_sweeps = n_sweeps; r.n_chi2 = n_chi2; r.n_omega = n_omega;
+    r.dof = dof_ == 0 ? 1 : (dof_ > 2147483647LL ? 2147483647 : (int)dof_);
+    r.lambda = lambda; r.chi2 = old_chi2;
+    recs[f] = r;
+  }
+}
+
+// STEP 1 + 2 only, at given parameters: each fit's J^T J [na x na] (both triangles), J^T r [na] and chi2 -- the "one pass" of
+// callers with their own loop.  img [n_fits][na * na + na + 1].
+extern "C" __global__ __launch_bounds__(256)
+void gfh_k_batch_pass(const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ w,
+                      const i64* __restrict__ off, const double* __restrict__ pars, double* __restrict__ img,
+                      const i64 n_fits, int* __restrict__ status) {
+  const i64 f = (i64)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (f >= n_fits) return;
+  const gfh_bdata d = {x, y, w, off[f], off[f + 1], (int)(threadIdx.x & 63)};
+  double P[GFH_NP], S[GFH_BNACC];
+#pragma unroll
+  for (int k = 0; k < GFH_NP; k++) P[k] = gfh_uni(pars[f * GFH_NP + k]);
+  gfh_b_sweep(d, P, status, S);
+  if (d.lane == 0) {
+    double* __restrict__ out = img + f * (GFH_NA * GFH_NA + GFH_NA + 1);
+#pragma unroll
+    for (int a = 0; a < GFH_NA; a++)
+#pragma unroll
+      for (int b = 0; b < GFH_NA; b++) out[a * GFH_NA + b] = a <= b ? S[GFH_BIDX(a, b)] : S[GFH_BIDX(b, a)];
+#pragma unroll
+    for (int a = 0; a < GFH_NA; a++) out[GFH_NA * GFH_NA + a] = S[GFH_BNP + a];
+    out[GFH_NA * GFH_NA + GFH_NA] = S[GFH_BNP + GFH_NA];
+  }
+}

@@ -1,0 +1,18 @@
+// device_text.h -- the hand-written device source of the generated translation units: each file of device/ as a
+// NUL-terminated string, byte for byte (device_text.cpp embeds them at compile time; the library reads no file at run time).
+#pragma once
+
+namespace gfh {
+
+extern const char kExp[];              // exp.hip: gfh_exp
+extern const char kPowLn[];            // pow_ln.hip: gfh_pow_ln (models with x ** a, GFH_FAST_DIV)
+extern const char kParsBlock[];        // pars_block.hip: the parameter block as kernel argument or device array
+extern const char kSweep[];            // sweep.hip: layout, GFH_ROBUST, gfh_store64, gfh_k_sweep, the hand-off macros
+extern const char kWaveSum[];          // wave_sum.hip: gfh_row_down, gfh_wave_sum (kernels.hip includes the same file)
+extern const char kFusedSweepGram[];   // fused_sweep_gram.hip: the fused STEP 1 + STEP 2 kernel in all its forms
+extern const char kChi2[];             // chi2.hip: gfh_k_chi2
+extern const char kOmega[];            // omega.hip: the tangent block of STEP 3, gfh_k_omega
+extern const char kOmegaJt[];          // omega_jt.hip: gfh_k_omega_jt
+extern const char kBatchFit[];         // batch_fit.hip: gfh_k_fit_batch, gfh_k_batch_pass
+
+}  // namespace gfh

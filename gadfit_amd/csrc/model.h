@@ -56,6 +56,8 @@ struct Model {
 };
 
 inline bool is_guard_op(int op) { return op == GFH_GUARD_GT || op == GFH_GUARD_LT; }
+// same operation (guards: whatever their recorded outcome)
+bool same_node(const Node& a, const Node& b);
 
 // Options of the generated kernels (kept in the source text so the cache key sees them).
 struct GenConfig {
@@ -109,7 +111,7 @@ constexpr int kMeshRecord = 64, kMeshSitesMax = 4;
 int mesh_sites(const Model& m);
 
 // Up to this many active parameters the fused kernel forms J^T J / J^T r in per-lane VALU accumulators
-// (n (n + 1) / 2 + n + 1 of them) instead of on the matrix cores (codegen.cpp, GFH_K_SWEEP_GRAM).  Measured at N = 1e7: 8 parameters
+// (n (n + 1) / 2 + n + 1 of them) instead of on the matrix cores (fused_sweep_gram.hip, GFH_K_SWEEP_GRAM).  Measured at N = 1e7: 8 parameters
 // 0.166 ms against 0.179 ms with one matrix tile; 12 parameters 0.258 ms (252 VGPRs) against 0.188 ms: the boundary stays at 8.
 constexpr int kValuGramMax = 8;
 // ... and how many passes ahead that form loads its inputs: ONE.  Two (three rotating register sets) were built

@@ -44,7 +44,7 @@ def nostore_roofline(sha, count, kernel_ms):
     """gfh_k_sweep_gram_nostore against the FP64 pipe of a SIMD, which vector and matrix instructions share (their times add:
     tools/microbench/fp64_phases.hip, profiles/r04_nostore.md).  `frac`: the kernel's own instruction count of THIS round's counter
     pass (SQ_INSTS_VALU includes the matrix instructions; of SQ_INSTS_VALU_MFMA_F64 one in six is a 64-cycle 16x16x4, five are
-    17.5-cycle 4x4x4_4b: codegen.cpp, GFH_K_SWEEP_GRAM), priced at 4 / 64 / 17.5 cycles per instruction and SIMD, refused when the
+    17.5-cycle 4x4x4_4b: fused_sweep_gram.hip, GFH_K_SWEEP_GRAM), priced at 4 / 64 / 17.5 cycles per instruction and SIMD, refused when the
     counts were taken on another source; `flops_frac`: the necessary arithmetic against the 78.6 TFLOP/s peak."""
     r = {'bound': 'fp64 pipe (VALU + MFMA share it)', 'necessary_flop_per_point': NOSTORE_FLOP_PER_POINT, 'fp64_peak_TFLOPs': 78.6,
          'flops_frac': NOSTORE_FLOP_PER_POINT * count / (1e-3 * kernel_ms) / 78.6e12}

@@ -1,7 +1,7 @@
 // Issue cost of the FP64 (and helper 32-bit) VALU instructions the generated model bodies are made of, on gfx950.
 // Per instruction: NI independent streams of it, unrolled, one/two/four waves per SIMD on every CU; the
 // kernel reads s_memtime around the loop, so the result is shader cycles per wave-instruction per SIMD
-// (independent of the clock the chip holds).  Feeds the cost model behind the generated exp() (codegen.cpp).
+// (independent of the clock the chip holds).  Feeds the cost model behind the generated exp() (gadfit_amd/csrc/device/exp.hip).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
