@@ -86,6 +86,7 @@ SYMBOLS = {
     'gfh_set_pars_hook': (_i, [_vp, _vp, _vp]),
     'gfh_get_counters': (_i, [_vp, C.POINTER(_i64)]),
     'gfh_device_memory': (_i, [_vp, C.POINTER(_i64)]),
+    'gfh_debug_deferred': (_i, [_vp, C.POINTER(C.c_longlong)]),
     'gfh_debug_mesh_stats': (_i, [_vp, C.POINTER(_i64)]),
     'gfh_model_source': (_i64, [_vp, _i, _ip, C.c_char_p, _i64]),
     'gfh_model_prepare': (_i, [_vp, _i, _ip]),
@@ -357,6 +358,13 @@ class Context:
         out = (_i64 * 4)()
         self._chk(lib().gfh_get_counters(self._h, out))
         return dict(unseen_rounds=out[0], mesh_replays=out[1], variants=out[2], ws_size=out[3] >> 32, ws_size_inner=out[3] & 0xffffffff)
+
+    def debug_deferred(self):
+        """dict(deferred, stored, materialised, owed): sweeps inside fits without / with the Jacobian store, launches that wrote an
+        owed Jacobian, whether one is owed now -- gfh_debug_deferred"""
+        out = (C.c_longlong * 4)()
+        self._chk(lib().gfh_debug_deferred(self._h, out))
+        return dict(deferred=out[0], stored=out[1], materialised=out[2], owed=bool(out[3]))
 
     def mesh_stats(self):
         """dict(integrals, bisections, unrecorded, sites) of the last recording pass of a quadrature model -- gfh_debug_mesh_stats"""

@@ -62,6 +62,18 @@ int gfh::get_kernels(gfh_ctx* c, const std::vector<int32_t>& active, bool load) 
   return get_kernels_variant(c, active, load, fits ? c->nd * np : 0);
 }
 
+// The kernels of the current active set without the Jacobian store, beside c->cur (which stays what it is): what a sweep of a fit
+// that defers the store launches.  A lookup in the cache; the first call for an active set loads (or compiles) them.
+ModelKernels* gfh::nostore_kernels(gfh_ctx* c) {
+  if (!c->cur || !c->gen.store_j) return c->cur;
+  ModelKernels* const keep = c->cur;
+  c->gen.store_j = false;
+  const int rc = get_kernels(c, c->cur_active, true);
+  ModelKernels* const mk = rc ? nullptr : c->cur;
+  c->gen.store_j = true; c->cur = keep;
+  return mk;
+}
+
 int gfh::check_aux(gfh_ctx* c) {
   if (c->has_model && c->model.n_aux > c->n_aux)
     return fail(c, "the model reads " + std::to_string(c->model.n_aux) + " auxiliary per-point column(s); call gfh_set_aux after gfh_set_data");
@@ -299,11 +311,12 @@ int gfh_model_prepare(gfh_ctx* c, int n_act, const int32_t* active) {
   std::vector<int32_t> a(active, active + n_act);
   if (c->device >= 0) return get_kernels(c, a, false);
   // compile-only context (build time): also the forms gfh_fit switches to under keep_jacobian mode 2 -- without the Jacobian
-  // store (plain fits) and without the residual store -- so that a GPU box finds them in the cache
+  // store (plain fits) and without the residual store -- and the one its sweeps run under mode 1 while the store is deferred (no
+  // Jacobian store, residuals kept), so that a GPU box finds them in the cache
   const bool sj = c->gen.store_j, sr = c->gen.store_res;
   int rc = get_kernels(c, a, false);
-  const bool combos[2][2] = {{false, false}, {true, false}};
-  for (int k = 0; k < 2 && !rc; k++) {
+  const bool combos[3][2] = {{false, false}, {true, false}, {false, true}};
+  for (int k = 0; k < 3 && !rc; k++) {
     c->gen.store_j = combos[k][0] || !c->fused || c->model.has_integrals() || n_act > kFusedMaxActive; c->gen.store_res = combos[k][1];
     rc = get_kernels(c, a, false);
   }

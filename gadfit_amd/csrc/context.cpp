@@ -57,7 +57,7 @@ bool omega_needs_jacobian(const gfh_ctx* c, int n_active) {
 
 void set_store_j(gfh_ctx* c, bool on) {
   if (!c->fused || (c->has_model && c->model.has_integrals())) on = true;   // the two-kernel path re-reads J
-  if (on != c->gen.store_j) { c->gen.store_j = on; c->cur = nullptr; c->have_sweep = false; c->j_valid = false; }
+  if (on != c->gen.store_j) { c->gen.store_j = on; c->cur = nullptr; c->have_sweep = false; c->j_valid = false; c->defer.owed = c->defer.chi2_after = false; }
 }
 // chi2() overwrites the residual vector in the reference (gadfit.F90:1024-1026); only the grad_chi2 / cos_phi tests
 // and read-backs ever look at it, so gfh_fit under keep_jacobian mode 2 lets the chi2 kernel skip the 8 B/point store
@@ -160,6 +160,8 @@ int gfh_create(int device, gfh_ctx** out) {
   if (const char* e = getenv("GADFIT_HIP_FUSED")) c->fused = atoi(e) != 0;
   if (const char* e = getenv("GADFIT_HIP_LOOKAHEAD")) c->lookahead = atoi(e) != 0;
   if (const char* e = getenv("GADFIT_HIP_KEEP_J")) { int v = atoi(e); if (v >= 0 && v <= 2) { c->keep_jacobian = v; c->gen.store_j = v != 0; } }
+  if (const char* e = getenv("GADFIT_HIP_DEFER_J")) c->defer.on = atoi(e) != 0;
+  if (const char* e = getenv("GADFIT_HIP_DEFER_J_FROM")) { const long long v = atoll(e); if (v >= 0) c->defer.from = (size_t)v; }
   if (const char* e = getenv("GADFIT_HIP_MESH")) c->disp.mesh_on = atoi(e) != 0;
   if (const char* e = getenv("GADFIT_HIP_ORDER")) c->disp.order_on = atoi(e) != 0;
   if (const char* e = getenv("GADFIT_HIP_PLACEMENT_AFTER")) { int v = atoi(e); if (v >= 0) c->place.after = v; }

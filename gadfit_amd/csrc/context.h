@@ -19,6 +19,7 @@ constexpr int kPadGranule = 512;    // dataset segments are padded to this many 
 // took a branch of eval() no recorded variant covers), [16] and [24] arrival counters of k_publish / gfh_k_chi2, and from byte 64 the
 // report of unseen branches: an arrival counter, then from byte 128 up to kUnseenCap entries {slot, guard outcomes so far (bit k = guard k
 // taken), their number} -- layout shared with the generated source (codegen.cpp, gfh_report_unseen).
+constexpr size_t kPlacedJacobianBytes = (size_t)256 << 20;   // a Jacobian buffer from this size on is placed (placement.cpp) and its store deferred inside fits
 constexpr int kUnseenCap = 120;
 constexpr size_t kStatusBytes = 128 + (size_t)kUnseenCap * 24;
 struct UnseenEntry { long long slot; unsigned long long path; int n_guards; int pad; };
@@ -130,6 +131,21 @@ struct gfh_ctx {
   bool j_valid = false;             // the Jacobian of that sweep is in HBM
   bool res_valid = false;           // the residual vector of the last pass is in HBM
   int keep_jacobian = 1;            // 0 never, 1 always (reference behaviour), 2 gfh_fit decides (GADFIT_HIP_KEEP_J)
+  // Deferred Jacobian store (gfh_fit, lm.cpp; materialise_jacobian, passes.cpp).  Inside a fit nobody reads the stored J: the fused
+  // kernel forms its sums from registers and every sweep overwrites what the one before it wrote.  Under keep_jacobian mode 1 the
+  // sweeps of such a fit run the no-store kernel, except those no later sweep of the fit can follow (max_iter).  A fit that ends any
+  // other way leaves J OWED: the parameter block of its most recent sweep is kept -- and that of a chi2 pass that wrote res after
+  // it -- and the first call that reads J launches the storing kernel there (and the chi2 kernel again), on this rank alone.
+  struct Deferred {
+    bool on = true;                 // GADFIT_HIP_DEFER_J
+    size_t from = gfh::kPlacedJacobianBytes;   // smallest Jacobian (bytes) whose store is deferred (GADFIT_HIP_DEFER_J_FROM)
+    int fit = 0;                    // 0: no gfh_fit is running, 1: one that stores at every sweep, 2: one that defers
+    bool store_next = true;         // fit == 2: no later sweep of the fit can follow the one about to be requested
+    bool owed = false;              // the most recent sweep (have_sweep) skipped the store: J at `pars` is owed
+    bool chi2_after = false;        // ... and a chi2 pass at `chi2_pars` has written res since
+    std::vector<double> pars, chi2_pars;
+    long long n_deferred = 0, n_stored = 0, n_materialised = 0;   // sweeps inside fits without / with the store; materialising launches
+  } defer;
   int lookahead = 1;                // gfh_fit / gfh_lm_iterate: first trial chi2 from a sweep at the trial point (GADFIT_HIP_LOOKAHEAD)
   bool kernarg = true;              // one dataset: parameters as a by-value kernel argument instead of an H2D copy per pass (GADFIT_HIP_KERNARG)
   bool merge_small = true;          // J^T v: reduce + assemble + publish as one single-workgroup launch when small (GADFIT_HIP_MERGE_SMALL)
@@ -180,6 +196,7 @@ void set_store_res(gfh_ctx* c, bool on);
 bool uses_fused_kernel(const gfh_ctx* c);
 bool sweep_chi2_is_bitwise(const gfh_ctx* c);
 bool omega_needs_jacobian(const gfh_ctx* c, int n_active);
+int materialise_jacobian(gfh_ctx* c);   // passes.cpp: every reader of the stored Jacobian calls it before it looks at j_valid
 int join_pending(gfh_ctx* c);     // waits for an upload started by gfh_set_data_begin; its result
 // Named ranges for `rocprofv3 --marker-trace` (ROCTX): every pass, a fit and its iterations, an upload, the recovery from an unseen
 // branch.  Off unless GADFIT_HIP_ROCTX=1 (the library is looked up at run time: no link dependency, no cost when off).

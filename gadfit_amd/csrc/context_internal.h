@@ -56,6 +56,7 @@ int set_geometry(gfh_ctx* c, int64_t n_total, int nd, const int64_t* dp);
 // active.cpp
 void apply_ws_plan(gfh_ctx* c);
 int get_kernels(gfh_ctx* c, const std::vector<int32_t>& active, bool load);
+ModelKernels* nostore_kernels(gfh_ctx* c);
 int check_aux(gfh_ctx* c);
 int ensure_mesh(gfh_ctx* c);
 int prepare_active(gfh_ctx* c, const int32_t* active, int na, const int32_t* jac, int dim);
@@ -66,7 +67,7 @@ bool use_fused(const gfh_ctx* c);
 int mesh_mode_for(gfh_ctx* c, const double* pars, bool recording_pass);
 int launch_model_sweep(gfh_ctx* c, int mesh_mode = 0);
 int build_orders(gfh_ctx* c);
-int launch_model_sweep_gram(gfh_ctx* c, int tail_mode = 0, unsigned long long seq = 0, unsigned lds_pad = 0);
+int launch_model_sweep_gram(gfh_ctx* c, int tail_mode = 0, unsigned long long seq = 0, unsigned lds_pad = 0, const ModelKernels* mk = nullptr);
 bool tail_one_workgroup_per_cu(const gfh_ctx* c);
 unsigned tail_lds_pad(const gfh_ctx* c);
 int update_tail(gfh_ctx* c);

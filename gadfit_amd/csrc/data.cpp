@@ -179,7 +179,7 @@ int gfh::set_geometry(gfh_ctx* c, int64_t n_total, int nd, const int64_t* dp) {
   for (int d = 0; d < nd; d++) if (dp[d + 1] < dp[d]) return fail(c, "data_positions must be non-decreasing");
   c->n_total = n_total; c->nd = nd; c->dp.assign(dp, dp + nd + 1);
   // new data: the Jacobian/residuals on the device are stale, and the kernel form follows n_datasets
-  c->cur = nullptr; c->cur_active.clear(); c->have_sweep = false; c->j_valid = false; c->prepared = false;
+  c->cur = nullptr; c->cur_active.clear(); c->have_sweep = false; c->j_valid = false; c->defer.owed = c->defer.chi2_after = false; c->prepared = false;
   c->n_aux = 0;                     // auxiliary columns belong to the data they were tabulated for
   c->disp.mesh_valid = false;
   c->disp.order_ready = false; c->disp.order_want = true;

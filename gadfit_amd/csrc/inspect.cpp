@@ -123,7 +123,8 @@ int gfh_time_kernel(gfh_ctx* c, int which, int reps, double* avg_ms) {
       case 8: if (!c->disp.mesh_valid) return fail(c, "no recorded quadrature mesh to replay"); rc = launch_model_sweep(c, 2); break;
       case 9: if (!c->disp.mesh_valid) return fail(c, "no recorded quadrature mesh to replay"); rc = launch_model_omega(c, 2); break;
       case 6: if (!c->cur->omega_jt) return fail(c, "gfh_k_omega_jt is not available for this model"); rc = launch_model_omega_jt(c); break;
-      case 7: if (!c->j_valid) return fail(c, "the Jacobian was not kept (gfh_set_keep_jacobian)");
+      case 7: if (materialise_jacobian(c)) return 1;
+              if (!c->j_valid) return fail(c, "the Jacobian was not kept (gfh_set_keep_jacobian)");
               if (c->n_gb) { hipError_t e = launch_jtv(c->stream, c->J.as<double>(), c->ldj, (int)c->cur_active.size(), c->res.as<double>(),
                                  c->gb_start.as<i64>(), c->gb_slots.as<int>(), c->n_gb, c->partial.as<double>(), gram_partial_stride(c->cur_T));
                              if (e != hipSuccess) return fail(c, hipGetErrorString(e)); } break;
@@ -150,6 +151,7 @@ int gfh_get_jacobian(gfh_ctx* c, double* out) {
   GROUP(c, gfh_get_jacobian(k, out + (size_t)k->begin * k->cur_active.size()));
   NEED_GPU(c);
   if (!c->have_sweep) return fail(c, "no Jacobian on the device yet");
+  if (materialise_jacobian(c)) return 1;
   if (!c->j_valid) return fail(c, "the Jacobian was not kept (gfh_set_keep_jacobian)");
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const int na = (int)c->cur_active.size();
@@ -167,6 +169,7 @@ int gfh_get_points(gfh_ctx* c, int n, const int64_t* index, double* res_out, dou
   NOT_FOR_GROUP(c, "gfh_get_points");
   NEED_GPU(c);
   if (!c->have_sweep) return fail(c, "no sweep on the device yet");
+  if (jac_out && materialise_jacobian(c)) return 1;
   if (jac_out && !c->j_valid) return fail(c, "the Jacobian was not kept (gfh_set_keep_jacobian)");
   if (res_out && !c->res_valid) return fail(c, "the residual vector of the last pass was not kept");
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -230,6 +233,13 @@ int gfh_debug_mesh_stats(gfh_ctx* c, int64_t* out4) {
         if (v == 255) out4[2]++; else { out4[0]++; out4[1] += v; }
       }
   out4[3] = (int64_t)sites;
+  return 0;
+}
+int gfh_debug_deferred(gfh_ctx* c, long long* out4) {
+  if (!c || !out4) return 1;
+  const gfh_ctx* k = c->grp ? gfh::group_member(c, 0) : c;
+  out4[0] = k->defer.n_deferred; out4[1] = k->defer.n_stored; out4[2] = k->defer.n_materialised;
+  out4[3] = k->defer.owed && k->have_sweep ? 1 : 0;
   return 0;
 }
 int gfh_device_memory(gfh_ctx* c, int64_t* out3) {

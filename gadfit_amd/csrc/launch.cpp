@@ -171,9 +171,11 @@ int gfh::build_orders(gfh_ctx* c) {
 }
 
 // tail_mode 0: workgroup partials only; 1: + in-kernel reduction and assembly into c->packed;
-// 2: + the result mailbox (sequence number seq).  Modes 1/2 need update_tail().
-int gfh::launch_model_sweep_gram(gfh_ctx* c, int tail_mode, unsigned long long seq, unsigned lds_pad) {
+// 2: + the result mailbox (sequence number seq).  Modes 1/2 need update_tail().  mk: the kernels of the same active set
+// without the Jacobian store (nostore_kernels) instead of c->cur -- same arguments, same grid.
+int gfh::launch_model_sweep_gram(gfh_ctx* c, int tail_mode, unsigned long long seq, unsigned lds_pad, const ModelKernels* mk) {
   if (!c->n_gb) return 0;
+  if (!mk) mk = c->cur;
   void* x = c->x.p; void* y = c->y.p; void* w = c->w.p; void* pars = c->pars.p; void* parg = c->cur->kernarg_pars ? (void*)c->h_pars : (void*)&pars;
   void* gs = c->gb_start.p; void* gn = c->gb_slots.p; void* gd = c->gb_ds.p;
   void* res = c->res.p; void* J = c->J.p; long long ldj = c->ldj; void* part = c->partial.p;
@@ -181,7 +183,7 @@ int gfh::launch_model_sweep_gram(gfh_ctx* c, int tail_mode, unsigned long long s
   void* ax = c->aux.p; long long lda = c->n_slots;
   void* args[] = {&x, &y, &w, parg, &gs, &gn, &gd, &res, &J, &ldj, &part, &ps, &stp, &ax, &lda, &tl, &seq, &tail_mode};
   const int fw = fused_waves_for((int)c->cur_active.size());
-  HIPCHK(c, hipModuleLaunchKernel(c->cur->sweep_gram, c->n_gb, 1, 1, 64 * fw, 1, 1, lds_pad, c->stream, args, nullptr));
+  HIPCHK(c, hipModuleLaunchKernel(mk->sweep_gram, c->n_gb, 1, 1, 64 * fw, 1, 1, lds_pad, c->stream, args, nullptr));
   return 0;
 }
 

@@ -3,6 +3,7 @@
 // lambda logic stay on the host; they are restated exactly because they decide which device
 // passes are requested.  Host work per iteration is O(dim^3) on a
 // dim x dim matrix; everything N-sized lives in HBM behind gfh_sweep/gfh_chi2/gfh_omega.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -392,7 +393,7 @@ extern "C" int gfh_fit(gfh_ctx* c, double* pars, int na, const int32_t* active, 
   // pattern-only transfer of global fits need not clear them again
   c->jtj_prezeroed = true;
   auto finish = [&](int rc) {
-    c->jtj_prezeroed = false;
+    c->jtj_prezeroed = false; c->defer.fit = 0; c->defer.store_next = true;
     r->iterations = iterations; r->lambda = lambda; r->chi2 = old_chi2;
     r->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return rc;
@@ -404,14 +405,26 @@ extern "C" int gfh_fit(gfh_ctx* c, double* pars, int na, const int32_t* active, 
     set_store_res(c, o->has_grad_chi2 || o->has_cos_phi);
   }
   if (gfh_set_active(c, active, na, f.jac.data(), dim)) return finish(1);
+  // adaptive parallelism (load_balancing, gadfit.F90:672-673): the ranges may be re-cut before an iteration, so no sweep is handed over
+  const bool balancing = c->bal.on && c->nranks > 1;
+  // keep_jacobian = 1 promises that J of the most recent sweep can be read once the fit has returned; until then every sweep
+  // overwrites what the one before it wrote and -- with the fused kernel and options that do not read J -- nobody looks at it.  Such a
+  // fit's sweeps skip the store (context.h, Deferred) unless max_iter guarantees that no later sweep of this fit can follow them:
+  // the sweep handed to, or made by, the last permitted iteration, and the look-ahead sweep that would be handed to it.  A fit
+  // that ends any other way owes J (materialise_jacobian).  (A parameter hook may upload columns that belong to the parameters of
+  // a pass: a pass repeated later would not find them, so such fits store as before.)
+  const bool reads_j = (o->has_accth && o->accth > 1.17549435e-38 && omega_needs_jacobian(c, na)) || o->has_grad_chi2 || o->has_cos_phi;
+  const bool defer = c->defer.on && c->keep_jacobian == 1 && c->gen.store_j && uses_fused_kernel(c) && !reads_j && !balancing && !c->pars_fn &&
+                     sizeof(double) * (size_t)na * (size_t)std::max<int64_t>(1, c->ldj) >= c->defer.from;
+  c->defer.fit = defer ? 2 : 1;
+  auto last_permitted = [&](int iteration) { return o->has_max_iter && iteration >= o->max_iter; };   // (1-based; the loop runs once whatever max_iter says)
   // Look-ahead (gadfit_hip.h, gfh_set_lookahead): the fused sweep already returns sum r^2, so the
   // FIRST trial chi2() of an iteration (gadfit.F90:753) is taken from a sweep at the trial point;
   // when the step is accepted that sweep IS the next iteration's STEP 1+2 (same parameters, same
   // kernel, same numbers), so an accepted iteration costs one N-sized pass instead of two.  Armed
   // while the previous first trial was accepted.  Off when the convergence tests read the device
   // J/res pair the reference has at that point (old J, new res: gadfit.F90:849-850, 865-873).
-  // adaptive parallelism (load_balancing, gadfit.F90:672-673): the ranges may be re-cut before an iteration, so no sweep is handed over
-  const bool balancing = c->bal.on && c->nranks > 1;
+  // (not under adaptive parallelism either: the ranges may be re-cut before an iteration, so no sweep is handed over)
   // ... and only where the sweep's sum r^2 is bitwise what chi2() returns at the same parameters: the fused kernel (same
   // partition and order of additions as gfh_k_chi2) with shared reciprocals (GADFIT_HIP_FAST_DIV=0 keeps the reference's
   // two division forms, whose values differ by rounding between the active and the passive evaluation)
@@ -433,6 +446,7 @@ extern "C" int gfh_fit(gfh_ctx* c, double* pars, int na, const int32_t* active, 
   // old_chi2 = chi2() before the loop (gadfit.F90:670).  With look-ahead the first STEP 1+2 pass -- same
   // parameters -- returns that sum r^2 itself and is handed to the first iteration: one N-sized pass less per fit.
   if (la_ok) {
+    c->defer.store_next = last_permitted(1);
     if (gfh_sweep(c, pars, active, na, f.jac.data(), dim, f.nextJTJ.data(), f.nextJTres.data(), &old_chi2)) return finish(1);
     have_next = true; r->n_lookahead++;
   } else if (gfh_chi2(c, pars, &old_chi2)) return finish(1);
@@ -441,7 +455,10 @@ extern "C" int gfh_fit(gfh_ctx* c, double* pars, int na, const int32_t* active, 
     if (balancing && iterations > 0 && gfh_rebalance(c, nullptr)) return finish(1);                 // re_initialize, gadfit.F90:672-673
     // STEP 1 + 2 (gadfit.F90:675-701)
     if (have_next) { f.JTJ.swap(f.nextJTJ); f.JTres.swap(f.nextJTres); have_next = false; }
-    else if (gfh_sweep(c, pars, active, na, f.jac.data(), dim, f.JTJ.data(), f.JTres.data(), &sweep_chi2)) return finish(1);
+    else {
+      c->defer.store_next = last_permitted(iterations + 1);
+      if (gfh_sweep(c, pars, active, na, f.jac.data(), dim, f.JTJ.data(), f.JTres.data(), &sweep_chi2)) return finish(1);
+    }
     r->n_sweeps++;
     for (int i = 0; i < dim; i++) {                                                                 // gadfit.F90:702-710
       const double d = f.JTJ[(size_t)i * dim + i];
@@ -487,6 +504,7 @@ extern "C" int gfh_fit(gfh_ctx* c, double* pars, int na, const int32_t* active, 
       const bool spec = la_ok && i == 1 && la_predicts_accept && !(o->has_max_iter && iterations + 1 >= o->max_iter);
       const double lambda_of_trial = lambda;
       if (spec) {
+        c->defer.store_next = last_permitted(iterations + 2);          // (handed to the next iteration if this trial is accepted)
         if (gfh_sweep(c, pars, active, na, f.jac.data(), dim, f.nextJTJ.data(), f.nextJTres.data(), &new_chi2)) return finish(1);
         r->n_lookahead++;
       } else if (gfh_chi2(c, pars, &new_chi2)) return finish(1);

@@ -139,6 +139,15 @@ static int sweep_pass(gfh_ctx* c, const double* pars, const int32_t* active, int
   if (upload_pars(c, pars)) return 1;
   // an event record costs ~5 us of stream time: only the model kernel is bracketed by default
   const bool fused = use_fused(c);
+  // a fit that defers the Jacobian store (context.h, Deferred): this sweep runs the kernels without it -- the same sums, bit for bit --
+  // unless the fit has said that no later sweep of it can follow
+  const ModelKernels* nostore = nullptr;
+  if (c->defer.fit == 2 && !c->defer.store_next && fused && c->gen.store_j) {
+    nostore = nostore_kernels(c);
+    if (!nostore) return 1;
+    if (!nostore->sweep_gram) nostore = nullptr;
+  }
+  const bool stores = c->gen.store_j && !nostore;
   // Small assemblies: the fused kernel's own tail reduces the workgroup partials, assembles the packed
   // normal equations and (single rank) writes the host mailbox -- no reduce/assemble/publish launches.
   const bool small = (int64_t)dim * dim * c->nd <= 65536;
@@ -157,10 +166,10 @@ static int sweep_pass(gfh_ctx* c, const double* pars, const int32_t* active, int
     if (!c->comm) seq = ++c->mail_seq;
   }
   // (a sweep writes every column of J anew: moving the buffer between two sweeps loses nothing)
-  if (c->place.pending && c->gen.store_j && c->J.p && c->place.sweeps_on_J >= c->place.after && place_jacobian_now(c, fused)) return 1;
-  if (c->gen.store_j && c->J.p) c->place.sweeps_on_J++;
+  if (c->place.pending && stores && c->J.p && c->place.sweeps_on_J >= c->place.after && place_jacobian_now(c, fused)) return 1;
+  if (stores && c->J.p) c->place.sweeps_on_J++;
   if (td >= 1) HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-  if (fused ? launch_model_sweep_gram(c, tail ? (c->comm ? 1 : 2) : 0, seq, tail ? tail_lds_pad(c) : 0u) : launch_model_sweep(c, mesh_mode_for(c, pars, true))) return 1;
+  if (fused ? launch_model_sweep_gram(c, tail ? (c->comm ? 1 : 2) : 0, seq, tail ? tail_lds_pad(c) : 0u, nostore) : launch_model_sweep(c, mesh_mode_for(c, pars, true))) return 1;
   if (td >= 1) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
   if (tail) {
     // reduction, assembly and (single rank) the mailbox write happened in the fused kernel's tail
@@ -208,7 +217,11 @@ static int sweep_pass(gfh_ctx* c, const double* pars, const int32_t* active, int
     if (JTres) memcpy(JTres, c->h_pinned + (size_t)dim * dim, sizeof(double) * dim);
     if (chi2) *chi2 = c->h_pinned[(size_t)dim * dim + dim];
   }
-  c->have_sweep = true; c->j_valid = c->gen.store_j; c->res_valid = true;
+  c->have_sweep = true; c->j_valid = stores; c->res_valid = true;
+  // (J of THIS sweep is what a reader is owed from now on, or nothing is)
+  c->defer.owed = nostore != nullptr; c->defer.chi2_after = false;
+  if (nostore) { c->defer.pars.assign(pars, pars + (size_t)c->nd * c->model.n_pars); c->defer.n_deferred++; }
+  else if (c->defer.fit && stores) c->defer.n_stored++;
   if (c->disp.order_measured && build_orders(c)) return 1;
   return 0;
 }
@@ -246,6 +259,8 @@ static int chi2_pass(gfh_ctx* c, const double* pars, double* chi2) {
   if (timed) { c->timers.t_chi2 += 1e-3 * ev_ms(c->ev[0], c->ev[1]); c->timers.n_chi2_timed++; }
   c->timers.n_chi2++;
   c->res_valid = c->gen.store_res;
+  // (an owed Jacobian: materialising it rewrites res, so the pass that wrote res last is repeated behind it)
+  if (c->defer.owed && c->gen.store_res) { c->defer.chi2_after = true; c->defer.chi2_pars.assign(pars, pars + (size_t)c->nd * c->model.n_pars); }
   *chi2 = c->h_pinned[0];
   return 0;
 }
@@ -297,6 +312,37 @@ static int jtv_to_host(gfh_ctx* c, const double* v_dev, double* out) {
   return jtv_finish(c, out);
 }
 
+// The Jacobian a fit owes (context.h, Deferred), written now: the storing kernel at the parameters of the fit's most recent sweep --
+// workgroup partials only, no cross-rank sum, no mailbox, nothing of the host's sums changes: a read-back is not a collective --
+// and, where a chi2 pass wrote the residual vector after that sweep, the chi2 kernel again at that pass's parameters, so that res
+// holds the bits it held.  Called by every reader of the stored Jacobian before it looks at j_valid; a no-op when nothing is owed.
+int gfh::materialise_jacobian(gfh_ctx* c) {
+  if (!c->defer.owed || !c->have_sweep) return 0;
+  if (!c->cur || !use_fused(c) || !c->gen.store_j || !c->J.p || c->defer.pars.size() != (size_t)c->nd * c->model.n_pars) {
+    c->defer.owed = c->defer.chi2_after = false;          // (no state this can be true in: the reader then fails with its usual message)
+    return 0;
+  }
+  gfh::Range range("gadfit materialise the deferred Jacobian");
+  harvest_events(c);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (upload_pars(c, c->defer.pars.data()) || launch_model_sweep_gram(c, 0, 0, 0)) return 1;
+  HIPCHK(c, hipStreamSynchronize(c->stream));              // (the staging block of the parameters is free again)
+  if (c->defer.chi2_after) {
+    if (dev_alloc(c, c->chi2_partial, sizeof(double) * (size_t)std::max(1, c->n_gb)) || upload_pars(c, c->defer.chi2_pars.data()) ||
+        launch_model_chi2(c, 0, 0, 0)) return 1;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  int st = 0;
+  HIPCHK(c, hipMemcpy(&st, c->status.p, sizeof(int), hipMemcpyDeviceToHost));
+  if (st) {
+    HIPCHK(c, hipMemset(c->status.p, 0, sizeof(int)));
+    return fail(c, "materialising the deferred Jacobian: device kernel reported status " + std::to_string(st));
+  }
+  c->defer.owed = c->defer.chi2_after = false;
+  c->j_valid = true; c->defer.n_materialised++;
+  return 0;
+}
+
 static int omega_pass(gfh_ctx* c, const double* pars, const double* delta1, double* JTomega) {
   gfh::Range range("gadfit omega (STEP 3)");
   harvest_events(c);
@@ -304,6 +350,7 @@ static int omega_pass(gfh_ctx* c, const double* pars, const double* delta1, doub
   if (c->gen.finite_diff && c->gen.fd_col_sets)
     return fail(c, "gfh_omega: the central difference of use_ad = 0 (fitfunction.F90:188-203) has no column sets at p +- h*delta (gfh_set_fd_column_sets)");
   const bool recompute = c->cur && c->cur->omega_jt && !omega_needs_jacobian(c, (int)c->cur_active.size());
+  if (!recompute && materialise_jacobian(c)) return 1;
   if (!recompute && !c->j_valid) return fail(c, "gfh_omega: the Jacobian was not kept (gfh_set_keep_jacobian)");
   if (ensure_tile_table(c)) return 1;
   std::vector<double> by_par, by_act;
@@ -380,6 +427,7 @@ int gfh_aux(gfh_ctx* c, int what, const double* delta1, double* out) {
     return gfh_aux(k, what, delta1, r ? mine.data() : out); });
   NEED_GPU(c);
   if (!c->have_sweep) return fail(c, "gfh_aux needs the Jacobian of a preceding gfh_sweep");
+  if (materialise_jacobian(c)) return 1;
   if (!c->j_valid) return fail(c, "gfh_aux: the Jacobian was not kept (gfh_set_keep_jacobian)");
   if (!c->res_valid) return fail(c, "gfh_aux: the residual vector was not kept (gfh_set_keep_jacobian)");
   if (what == 0) return jtv_to_host(c, c->res.as<double>(), out);

@@ -23,7 +23,7 @@ int gfh::place_jacobian(gfh_ctx* c, int na) {
   c->place.n = 0; c->place.sweeps_on_J = 0;
   // (only where the kernel that writes the buffer is bound by its store stream: the sweeps of models with integrate() are bound by
   // the quadrature arithmetic, no placement could show in their time)
-  c->place.pending = c->place.tries >= 2 && bytes >= ((size_t)256 << 20) && c->n_gb > 0 && !(c->has_model && c->model.has_integrals());
+  c->place.pending = c->place.tries >= 2 && bytes >= kPlacedJacobianBytes && c->n_gb > 0 && !(c->has_model && c->model.has_integrals());
   return 0;
 }
 

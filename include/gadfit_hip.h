@@ -292,13 +292,26 @@ int  gfh_set_loss(gfh_ctx* ctx, int loss);
  * is a separate matmul (gadfit.F90:689-698); the fused kernel forms J^T J / J^T r from registers,
  * so J is only read back by the grad_chi2 / cos_phi tests (849-850, 865-873), gfh_get_jacobian and --
  * for models with integrate() or a robust loss -- STEP 3 (J^T omega, gadfit.F90:734).  mode 1
- * (default): always written, as the reference.  mode 0: never (those calls then fail with a clear
+ * (default): the Jacobian of the most recent sweep can always be read, bit for bit as if every sweep had written it.  gfh_sweep
+ * and gfh_lm_iterate write it at every sweep.  Inside gfh_fit every sweep overwrites what the sweep before it wrote and nothing reads
+ * it before the fit returns, so where the fused kernel serves the fit, the fit's options do not read J, load balancing is off, no
+ * parameter hook is set and the buffer is large (Env GADFIT_HIP_DEFER_J_FROM, bytes; default 256 MB), only the sweeps that max_iter
+ * guarantees to be the fit's last write it (the one handed to, or made by, the last permitted iteration, and the look-ahead sweep
+ * that would be handed to it).  A fit that ends any other way owes the Jacobian: the first call that reads it (gfh_get_jacobian,
+ * gfh_get_points, gfh_aux, a gfh_omega that reads J) launches the storing kernel at the parameters of the fit's most recent sweep, on
+ * this rank alone (no collective), and repeats the chi2 pass that wrote the residual vector after that sweep, if one did, so that
+ * gfh_get_residuals returns what it returned before.  Anything that invalidates a stored Jacobian (gfh_set_data, gfh_set_model,
+ * another active set, this call with another mode) drops an owed one too.  Env GADFIT_HIP_DEFER_J=0: every sweep writes it.  mode 0: never (those calls then fail with a clear
  * message).  mode 2: gfh_fit writes it only when its options read it back, and likewise lets its chi2() passes skip the
  * residual store (res is read by the grad_chi2 / cos_phi tests and gfh_get_residuals only; a read-back of residuals that were
  * not kept fails with a clear message).  Without the store the sweep is bound by
  * the FP64 pipe instead of HBM writes and needs 8*n_act bytes per point less memory.
  * Env GADFIT_HIP_KEEP_J.  Results (J^T J, J^T r, chi2, res) are bitwise the same in all modes. */
 int  gfh_set_keep_jacobian(gfh_ctx* ctx, int mode);
+/* The deferred store of mode 1, counted since the context was created: out4[0] = sweeps inside fits that skipped the Jacobian store,
+ * out4[1] = sweeps inside fits that wrote it, out4[2] = launches that materialised an owed Jacobian (not counted as sweeps by
+ * gfh_get_timers), out4[3] = 1 while a Jacobian is owed.  A group handle reports member 0. */
+int  gfh_debug_deferred(gfh_ctx* ctx, long long* out4);
 
 /* load_balancing of gadf_fit -- "adaptive parallelism" (gadfit.F90:672-673, re_initialize 935-983): with more than
  * one rank (processes with a communicator, or the members of a device group) gfh_fit re-cuts the contiguous ranges
