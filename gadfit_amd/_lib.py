@@ -87,9 +87,11 @@ SYMBOLS = {
     'gfh_get_counters': (_i, [_vp, C.POINTER(_i64)]),
     'gfh_device_memory': (_i, [_vp, C.POINTER(_i64)]),
     'gfh_debug_deferred': (_i, [_vp, C.POINTER(C.c_longlong)]),
+    'gfh_debug_layout': (_i, [_vp, C.POINTER(_i64)]),
     'gfh_debug_mesh_stats': (_i, [_vp, C.POINTER(_i64)]),
     'gfh_model_source': (_i64, [_vp, _i, _ip, C.c_char_p, _i64]),
     'gfh_model_prepare': (_i, [_vp, _i, _ip]),
+    'gfh_model_prepare_form': (_i, [_vp, _i, _ip, _i, _i]),
     'gfh_set_active': (_i, [_vp, _ip, _i, _ip, _i]),
     'gfh_sweep': (_i, [_vp, _dp, _ip, _i, _ip, _i, _dp, _dp, _dp]),
     'gfh_set_aux': (_i, [_vp, _i, _dp]),
@@ -366,6 +368,13 @@ class Context:
         self._chk(lib().gfh_debug_deferred(self._h, out))
         return dict(deferred=out[0], stored=out[1], materialised=out[2], owed=bool(out[3]))
 
+    def debug_layout(self):
+        """dict(n_slots, n_gb, datasets_with_blocks, fused, waves, tail_mode, sparse, kernarg): the padded slots and gram workgroups of
+        this rank and how the most recent sweep was dispatched (-1 each while there is none) -- gfh_debug_layout"""
+        out = (_i64 * 8)()
+        self._chk(lib().gfh_debug_layout(self._h, out))
+        return dict(zip(('n_slots', 'n_gb', 'datasets_with_blocks', 'fused', 'waves', 'tail_mode', 'sparse', 'kernarg'), (int(v) for v in out)))
+
     def mesh_stats(self):
         """dict(integrals, bisections, unrecorded, sites) of the last recording pass of a quadrature model -- gfh_debug_mesh_stats"""
         out = (_i64 * 4)()
@@ -396,6 +405,11 @@ class Context:
     def model_prepare(self, active):
         a = np.ascontiguousarray(active, dtype=np.int32)
         self._chk(lib().gfh_model_prepare(self._h, a.size, ip(a)))
+
+    def model_prepare_form(self, active, n_datasets, store_jacobian):
+        """one translation unit into the cache: the form a context with n_datasets datasets loads, with or without the Jacobian store"""
+        a = np.ascontiguousarray(active, dtype=np.int32)
+        self._chk(lib().gfh_model_prepare_form(self._h, a.size, ip(a), int(n_datasets), int(bool(store_jacobian))))
 
     # --- hot path
     def jacobian_indices(self, active, is_global):

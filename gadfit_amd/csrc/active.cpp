@@ -324,6 +324,26 @@ int gfh_model_prepare(gfh_ctx* c, int n_act, const int32_t* active) {
   return rc;
 }
 
+// ONE translation unit into the cache, not loaded: the kernels a context that holds n_datasets datasets loads for this active set --
+// the parameter block by value while n_datasets * n_pars doubles fit the kernel-argument segment, else by pointer -- with the Jacobian
+// store or without it.  (gfh_model_prepare on a compile-only context builds the one-dataset and the pointer form in all four
+// combinations of the stores; this is for callers that know which units they will ask for.)  Needs no GPU.
+int gfh_model_prepare_form(gfh_ctx* c, int n_act, const int32_t* active, int n_datasets, int store_jacobian) {
+  if (!c) return 1;
+  NOT_FOR_GROUP(c, "gfh_model_prepare_form");
+  if (!c->has_model) return fail(c, "no model set (gfh_set_model)");
+  if (n_act < 1 || !active || n_datasets < 1) return fail(c, "gfh_model_prepare_form: bad arguments");
+  const std::vector<int32_t> a(active, active + n_act);
+  const int np = c->model.n_pars;
+  const bool by_value = c->kernarg && np >= 1 && (int64_t)n_datasets * np <= kMaxKernargPars;
+  const bool sj = c->gen.store_j;
+  ModelKernels* const keep = c->cur;
+  c->gen.store_j = store_jacobian != 0 || !c->fused || c->model.has_integrals() || n_act > kFusedMaxActive;
+  const int rc = get_kernels_variant(c, a, false, by_value ? n_datasets * np : 0);
+  c->gen.store_j = sj; c->cur = keep;
+  return rc;
+}
+
 // Test hook (no GPU needed): the geometry and the layout of the all-reduced image as rank `rank` of `nranks` derives them.
 // out[0] = length of the packed image, out[1] = pattern-only transfer (0/1), out[2] = nnz, out[3] = FNV-1a hash of the
 // pattern lists and of inv/owner, out[4] = first global point of this rank, out[5] = its point count, out[6] = number

@@ -152,6 +152,9 @@ struct gfh_ctx {
   bool tail = true;                 // fused kernel reduces/assembles/publishes in its own tail for small dim^2*n_datasets (GADFIT_HIP_TAIL)
   gfh::DevBuf slice, counters, tail_dev; std::vector<char> tail_host;
   bool fused = true;                // STEP 1+2 in one kernel (GADFIT_HIP_FUSED=0: separate sweep and Gram kernels)
+  // how the most recent sweep was dispatched (sweep_pass notes it, gfh_debug_layout reports it): the fused kernel or the plain sweep,
+  // its waves per workgroup, the tail mode it was handed (0: the launch chain), the pattern-only image
+  struct LastSweep { int fused = 0, waves = 0, tail_mode = 0, sparse = 0; } last_sweep;
 
   // timers (seconds) + counters (inspect.cpp; the passes count and bracket their launches)
   struct Timers {

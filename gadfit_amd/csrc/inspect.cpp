@@ -242,6 +242,17 @@ int gfh_debug_deferred(gfh_ctx* c, long long* out4) {
   out4[3] = k->defer.owed && k->have_sweep ? 1 : 0;
   return 0;
 }
+int gfh_debug_layout(gfh_ctx* c, int64_t* out8) {
+  if (!c || !out8) return 1;
+  const gfh_ctx* k = c->grp ? gfh::group_member(c, 0) : c;
+  int held = 0;
+  for (int d = 0; d < k->nd && (size_t)d + 1 < k->h_ds_first_gb.size(); d++) if (k->h_ds_first_gb[(size_t)d + 1] > k->h_ds_first_gb[(size_t)d]) held++;
+  out8[0] = k->n_slots; out8[1] = k->n_gb; out8[2] = held;
+  const bool swept = k->have_sweep && k->cur;
+  out8[3] = swept ? k->last_sweep.fused : -1; out8[4] = swept ? k->last_sweep.waves : -1; out8[5] = swept ? k->last_sweep.tail_mode : -1;
+  out8[6] = swept ? k->last_sweep.sparse : -1; out8[7] = swept ? k->cur->kernarg_pars : -1;
+  return 0;
+}
 int gfh_device_memory(gfh_ctx* c, int64_t* out3) {
   if (!c || !out3) return 1;
   gfh_ctx* k = c->grp ? gfh::group_member(c, 0) : c;

@@ -215,7 +215,7 @@ __global__ __launch_bounds__(512) void k_gram_small(const double* __restrict__ J
 // R0 .. R0+TR-1 and the column tiles C0 .. C0+TC-1 of J (the same fragments when the block is on the
 // diagonal) and writes its tile pairs into the SAME per-workgroup partial image k_gram<T> would write
 // (pair index from the global T), so the reduction and assembly kernels do not change.  Diagonal
-// launches also carry J^T r of their rows; the first one carries sum r^2.
+// launches also carry J^T r of their rows; the first one carries sum r^2, added in gfh_k_chi2's order.
 template <int TR, int TC, bool SYM>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_gram_block(const double* __restrict__ J, const i64 ldj, const int na,
                                                     const double* __restrict__ res, const i64* __restrict__ gb_start,
@@ -232,7 +232,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   double accr[TR];
 #pragma unroll
   for (int t = 0; t < TR; t++) accr[t] = 0.0;
-  double accc = 0.0;
   const double* arow[TR]; bool aval[TR];
   const double* brow[TC]; bool bval[TC];
 #pragma unroll
@@ -263,9 +262,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const double4_t rr = *reinterpret_cast<const double4_t*>(res + c);
 #pragma unroll
         for (int t = 0; t < TR; t++) accr[t] += a[t][0] * rr[0] + a[t][1] * rr[1] + a[t][2] * rr[2] + a[t][3] * rr[3];
-        if (R0 == 0) accc += rr[0] * rr[0] + rr[1] * rr[1] + rr[2] * rr[2] + rr[3] * rr[3];
       }
     }
+  }
+  // sum r^2 (the launch with R0 == 0) in gfh_k_chi2's own map and order at the 8 waves it runs with beyond the fused kernel (chi2.hip,
+  // GFH_CW; a gram block is whole passes of 512 slots): this thread stands for threads tid and tid + 256 of such a workgroup -- each
+  // sums its own points pass by pass --, then the wave tree, then the eight waves in order.  With k_reduce_partials and the assembly
+  // above it that is the order of chi2(), so chi2() at a sweep's parameters is bitwise the sweep's sum here too.
+  __shared__ double c8[8];
+  if (SYM && R0 == 0) {
+    double lo = 0.0, hi = 0.0;
+    for (i64 i = s + threadIdx.x; i + 256 < e; i += 512) {
+      const double r0 = res[i], r1 = res[i + 256];
+      lo += r0 * r0; hi += r1 * r1;
+    }
+    lo = gfh_wave_sum(lo); hi = gfh_wave_sum(hi);
+    if (lane == 0) { c8[wv] = lo; c8[wv + 4] = hi; }
   }
   // Cross-wave sum, waves in order.  Up to 4 x 4 tiles every wave has an image of its own in LDS; the wide blocks (5 or 6 tiles in ONE
   // launch: 15 / 21 pair images of 2 KB) add into one image wave after wave -- the same order of additions, a quarter of the LDS.
@@ -296,7 +308,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
 #pragma unroll
   for (int t = 0; t < TR; t++) vec[t * 64 + lane] = accr[t];
-  if (r == 0) vec[TR * 64 + q] = accc;
   __syncthreads();
   double* out = partial + (i64)blockIdx.x * pstride;
   const int npair = T * (T + 1) / 2;
@@ -324,11 +335,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       out[npair * 256 + 16 * (R0 + t) + rr_] = sacc;
     }
     if (R0 == 0 && threadIdx.x == 0) {
-      double sacc = 0.0;
+      double sacc = c8[0];
 #pragma unroll
-      for (int w = 0; w < 4; w++)
-#pragma unroll
-        for (int qq = 0; qq < 4; qq++) sacc += (WIDE ? sv[w] : sm[WIDE ? 0 : w] + NACC * 256)[TR * 64 + qq];
+      for (int w = 1; w < 8; w++) sacc += c8[w];
       out[npair * 256 + 16 * T] = sacc;
     }
   }

@@ -47,6 +47,8 @@ bool uses_fused_kernel(const gfh_ctx* c) { return use_fused(c); }
 // in order -- gfh_k_chi2's map and order at its 8 waves per workgroup -- and k_reduce_partials / k_gather_sum are the order gfh_k_chi2's
 // tail restates; the residuals themselves agree bit for bit (same value expressions; the quadrature's final pass rounds its panel
 // sums like the value-only pass).  Pinned by test_chi2_is_bitwise_the_sweeps_sum_of_squares*.
+// (Beyond 128 active parameters k_gram_block adds r^2 in gfh_k_chi2's order as well -- tests/test_gpu_gram_layouts.py holds it --; the
+// look-ahead schedule is not extended to them here.)
 bool sweep_chi2_is_bitwise(const gfh_ctx* c) {
   if (use_fused(c)) return true;
   return c->cur && c->cur_active.size() <= 8 && fused_waves_for((int)c->cur_active.size()) == 8 && !c->gen.finite_diff;

@@ -157,6 +157,7 @@ static int sweep_pass(gfh_ctx* c, const double* pars, const int32_t* active, int
   // ranks all-reduce, so it may only depend on quantities every rank shares (not on whether THIS rank has points).
   const bool sparse = c->sparse && !small;
   const size_t packed_n = sparse ? (size_t)c->nnz + dim + 1 : (size_t)dim * dim + dim + 1;
+  c->last_sweep = {fused ? 1 : 0, fused ? fused_waves_for(na) : 0, tail ? (c->comm ? 1 : 2) : 0, sparse ? 1 : 0};
   // (level 1 samples: every 8th launch since gfh_reset_timers is bracketed)
   const int tl_ = timed_launch(c, c->timers.n_sweep) ? c->timers.detail : 0;
   const int td = fused ? tl_ : (tl_ ? 2 : 0);

@@ -226,6 +226,10 @@ int  gfh_device_memory(gfh_ctx* ctx, int64_t* out3);
 int64_t gfh_model_source(gfh_ctx* ctx, int n_act, const int32_t* active_pars, char* buf, int64_t cap);
 /* Compile (or load from cache) without launching; usable without a GPU. */
 int  gfh_model_prepare(gfh_ctx* ctx, int n_act, const int32_t* active_pars);
+/* One translation unit into the kernel cache without loading it: the kernels a context that holds n_datasets datasets would load for
+ * this active set (the parameter block by value while n_datasets * n_pars <= 480 doubles, else by pointer), with the Jacobian store
+ * (store_jacobian != 0) or without it.  Usable without a GPU; not on a group handle. */
+int  gfh_model_prepare_form(gfh_ctx* ctx, int n_act, const int32_t* active_pars, int n_datasets, int store_jacobian);
 
 /* Selects the active set / column map ahead of the first sweep (gadfit.F90:586-631): loads
  * the kernels for it and sizes the device work arrays (re_initialize STEP 3, 1004-1011). */
@@ -312,6 +316,14 @@ int  gfh_set_keep_jacobian(gfh_ctx* ctx, int mode);
  * out4[1] = sweeps inside fits that wrote it, out4[2] = launches that materialised an owed Jacobian (not counted as sweeps by
  * gfh_get_timers), out4[3] = 1 while a Jacobian is owed.  A group handle reports member 0. */
 int  gfh_debug_deferred(gfh_ctx* ctx, long long* out4);
+/* Where the points lie and how the most recent gfh_sweep was dispatched (read-only; for tests that must know which path a case took):
+ * out8[0] = padded slots on this rank, out8[1] = its gram workgroups, out8[2] = datasets that have at least one of them; of the most
+ * recent sweep since the data were set (-1 each while there is none): out8[3] = 1 the fused sweep + Gram kernel, 0 the plain sweep and the
+ * Gram launches, out8[4] = waves per workgroup of the fused kernel (0 when not fused), out8[5] = the tail mode it was handed (0: workgroup
+ * partials and the reduce / assemble launches, 1: in-kernel tail into the packed image, 2: and into the host mailbox), out8[6] = 1 the
+ * pattern-only image of a global fit, 0 the dense one, out8[7] = doubles of the parameter block passed by value as a kernel argument (0:
+ * by pointer).  A group handle reports member 0. */
+int  gfh_debug_layout(gfh_ctx* ctx, int64_t* out8);
 
 /* load_balancing of gadf_fit -- "adaptive parallelism" (gadfit.F90:672-673, re_initialize 935-983): with more than
  * one rank (processes with a communicator, or the members of a device group) gfh_fit re-cuts the contiguous ranges
