@@ -105,6 +105,9 @@ SYMBOLS = {
     'gfh_batch_pass': (_i, [_vp, _dp, _i, _ip, _dp, _dp, _dp]),
     'gfh_batch_source': (_i64, [_vp, _i, _ip, C.c_char_p, _i64]),
     'gfh_batch_prepare': (_i, [_vp, _i, _ip]),
+    'gfh_set_batch_lanes': (_i, [_vp, _i]),
+    'gfh_batch_auto_lanes': (_i, [_i, _i64]),
+    'gfh_debug_batch_lanes': (_i, [_vp]),
     'gfh_set_lookahead': (_i, [_vp, _i]),
     'gfh_set_keep_jacobian': (_i, [_vp, _i]),
     'gfh_set_use_ad': (_i, [_vp, _i]),
@@ -507,10 +510,22 @@ class Context:
             raise GadfitHipError('%s: active parameter indices must lie in [0, %d)' % (who, self.n_pars))
         return p.reshape(n, self.n_pars), a, n
 
-    def fit_batch(self, pars, active, DTD_min=None, **kw):
-        """every spectrum of the batch fitted in one launch.  pars [n_fits][n_pars]; keyword arguments as fit().  Returns the fitted
-        parameters, a numpy record array of BatchResult [n_fits] and the device time of the launch in seconds."""
+    def set_batch_lanes(self, lanes):
+        """lanes per fit of the batch kernels from here on: 64 a wave per fit (the default), 16 a DPP row per fit and four fits per
+        wave (short spectra), 0 auto (batch_auto_lanes of the active count and the longest spectrum) -- gfh_set_batch_lanes"""
+        self._chk(lib().gfh_set_batch_lanes(self._h, int(lanes)))
+
+    def batch_lanes_used(self):
+        """64 or 16: the form of the last batch launch (0: none yet) -- gfh_debug_batch_lanes"""
+        return int(lib().gfh_debug_batch_lanes(self._h))
+
+    def fit_batch(self, pars, active, DTD_min=None, lanes_per_fit=None, **kw):
+        """every spectrum of the batch fitted in one launch.  pars [n_fits][n_pars]; keyword arguments as fit(); lanes_per_fit: as
+        set_batch_lanes (it stays set), None leaves the context's setting.  Returns the fitted parameters, a numpy record array of
+        BatchResult [n_fits] and the device time of the launch in seconds."""
         p, a, n = self._batch_args('fit_batch', pars, active)
+        if lanes_per_fit is not None:
+            self.set_batch_lanes(lanes_per_fit)
         o = FitOptions()
         for k, v in kw.items():
             if v is None:
@@ -532,9 +547,12 @@ class Context:
                                       C.cast(C.byref(sec), _dp)))
         return p, res.view(np.recarray), sec.value
 
-    def batch_pass(self, pars, active):
-        """(JTJ [n_fits][na][na], JTres [n_fits][na], chi2 [n_fits]) of every spectrum at pars [n_fits][n_pars] -- gfh_batch_pass"""
+    def batch_pass(self, pars, active, lanes_per_fit=None):
+        """(JTJ [n_fits][na][na], JTres [n_fits][na], chi2 [n_fits]) of every spectrum at pars [n_fits][n_pars] -- gfh_batch_pass;
+        lanes_per_fit as fit_batch"""
         p, a, n = self._batch_args('batch_pass', pars, active)
+        if lanes_per_fit is not None:
+            self.set_batch_lanes(lanes_per_fit)
         JTJ = np.zeros((n, a.size, a.size)); JTr = np.zeros((n, a.size)); chi2 = np.zeros(n)
         self._chk(lib().gfh_batch_pass(self._h, dp(p), a.size, ip(a), dp(JTJ), dp(JTr), dp(chi2)))
         return JTJ, JTr, chi2
@@ -667,6 +685,11 @@ class Context:
 
     def sync(self):
         self._chk(lib().gfh_sync(self._h))
+
+
+def batch_auto_lanes(n_active, longest):
+    """the auto rule of set_batch_lanes(0): 16 or 64 from the active count and the longest spectrum alone -- gfh_batch_auto_lanes"""
+    return int(lib().gfh_batch_auto_lanes(int(n_active), int(longest)))
 
 
 def read_columns(path, n_columns):

@@ -1,7 +1,8 @@
 // batch.cpp -- batched independent fits: many Levenberg-Marquardt fits of ONE model in ONE kernel launch, each with its own data,
-// start parameters, lambda history and exit (gfh_set_batch_data, gfh_fit_batch, gfh_batch_pass, gfh_batch_source, gfh_batch_prepare).
-// This file validates, uploads, compiles / loads and launches; the loop itself (gadfit.F90:670-915) is the generated kernel
-// gfh_k_fit_batch (batch_fit.hip; codegen.cpp, emit_batch_kernels), a wave per fit.  One stream, one launch and one device-to-host copy per call.
+// start parameters, lambda history and exit (gfh_set_batch_data, gfh_fit_batch, gfh_batch_pass, gfh_batch_source, gfh_batch_prepare,
+// gfh_set_batch_lanes).  This file validates, uploads, compiles / loads and launches; the loop itself (gadfit.F90:670-915) is the
+// generated kernel gfh_k_fit_batch (batch_fit.hip; codegen.cpp, emit_batch_kernels), a wave per fit or -- gfh_set_batch_lanes(16) -- a
+// DPP row of 16 lanes per fit and four fits per wave.  One stream, one launch and one device-to-host copy per call.
 // Everything the kernels do not carry is refused here with its own message, before anything touches the device.
 #include "context_internal.h"
 #include <algorithm>
@@ -19,6 +20,11 @@ struct BatchOpts {
   int lam_incs, max_iter, has_max_iter, use_accth, has_chi2_abs, has_chi2_rel, has_rel_error, damp_plain;
 };
 static_assert(sizeof(gfh_batch_result) == 40 && sizeof(BatchOpts) == 7 * 8 + 8 * kValuGramMax + 8 * 4, "layout shared with the generated kernels");
+
+// The auto rule's two numbers: the largest measured spectrum length at which the row form was faster than the wave form, on the same
+// card in the same run, by more than the two forms' own min-max spread (profiles/batch_rows.json; 0: nowhere).
+// Measured at 4 and at 8 active parameters; 1 ... 4 take the first, 5 ... 8 the second.
+constexpr int64_t kRowUpTo4 = 128, kRowUpTo8 = 256;
 
 // what a batch cannot be: refused on any context, with or without a GPU
 int check_context(gfh_ctx* c, const char* who) {
@@ -57,19 +63,26 @@ int check_geometry(gfh_ctx* c, const char* who, int na) {
 
 // the translation unit of an active set with the two batch kernels: generated, compiled and (load) loaded once per context, kept
 // in the context's kernel cache under a key no plain active set has, so that a new model or gfh_destroy releases it with the rest
-GenConfig batch_config(const gfh_ctx* c) {
-  GenConfig cfg;                    // the defaults, not the context's current switches: one form per (model, active set)
+GenConfig batch_config(const gfh_ctx* c, int lanes) {
+  GenConfig cfg;                    // the defaults, not the context's current switches: one form per (model, active set, lanes per fit)
   cfg.fast_div = c->gen.fast_div;
   cfg.batch = true;
+  cfg.batch_lanes = lanes;
   return cfg;
 }
-int batch_kernels(gfh_ctx* c, const std::vector<int32_t>& active, bool load, ModelKernels** out) {
+// the form a call uses: the context's setting, under auto what the rule gives for the geometry held (64 when the context holds none)
+int batch_lanes(const gfh_ctx* c, int na) {
+  if (c->batch.lanes != 0) return c->batch.lanes;
+  return c->batch.n_fits < 1 ? 64 : gfh_batch_auto_lanes(na, c->batch.max_points);
+}
+int batch_kernels(gfh_ctx* c, const std::vector<int32_t>& active, int lanes, bool load, ModelKernels** out) {
   std::vector<int32_t> key = active;
-  key.push_back(-(1 << 30));
+  key.push_back(-(1 << 30));        // (no plain active set holds a negative entry)
+  key.push_back(lanes);             // both forms of one active set can be resident
   auto it = c->kernel_cache.find(key);
   if (it != c->kernel_cache.end()) { if (out) *out = &it->second; return 0; }
   std::string src, err;
-  if (!generate_source(c->model, active, batch_config(c), &src, &err)) return fail(c, err);
+  if (!generate_source(c->model, active, batch_config(c, lanes), &src, &err)) return fail(c, err);
   ModelKernels mk;
   const uint64_t skey = load ? source_key(src) : 0;
   if (!(load && acquire_loaded(c->device, skey, &mk))) {
@@ -99,15 +112,15 @@ int gfh_set_batch_data(gfh_ctx* c, int64_t n_fits, const int64_t* offsets, const
   if (n_fits > ((int64_t)1 << 31) - 4) return fail(c, "gfh_set_batch_data: more fits than one launch takes (2^31 - 4)");
   if (!offsets || !x || !y || !w) return fail(c, "gfh_set_batch_data: null argument");
   if (offsets[0] != 0) return fail(c, "gfh_set_batch_data: offsets must begin at 0");
-  int64_t shortest = offsets[1] - offsets[0];
+  int64_t shortest = offsets[1] - offsets[0], longest = shortest;
   for (int64_t f = 0; f < n_fits; f++) {
     if (offsets[f + 1] < offsets[f]) return fail(c, "gfh_set_batch_data: offsets must ascend (fit " + std::to_string((long long)f) + " ends before it begins)");
-    shortest = std::min(shortest, offsets[f + 1] - offsets[f]);
+    shortest = std::min(shortest, offsets[f + 1] - offsets[f]); longest = std::max(longest, offsets[f + 1] - offsets[f]);
   }
   if (join_pending(c)) return 1;
   if (c->device >= 0 && c->batch.on_device) { hipSetDevice(c->device); if (c->stream) hipStreamSynchronize(c->stream); }
   batch_free(c);
-  c->batch.n_fits = n_fits; c->batch.off.assign(offsets, offsets + n_fits + 1); c->batch.min_points = shortest;
+  c->batch.n_fits = n_fits; c->batch.off.assign(offsets, offsets + n_fits + 1); c->batch.min_points = shortest; c->batch.max_points = longest;
   NEED_GPU(c);
   const size_t n = (size_t)offsets[n_fits], nb = sizeof(double) * std::max<size_t>(n, 1);
   if (dev_alloc(c, c->batch.x, nb) || dev_alloc(c, c->batch.y, nb) || dev_alloc(c, c->batch.w, nb) ||
@@ -125,7 +138,8 @@ int gfh_set_batch_data(gfh_ctx* c, int64_t n_fits, const int64_t* offsets, const
 } catch (const std::exception& e) { return fail(c, std::string("gfh_set_batch_data: ") + e.what()); }
 
 // gadf_fit (gadfit.F90:502-1035) for every spectrum of the batch at once: STEP 1+2, the damped solve (potr_f08,
-// gadfit_linalg.F90:36-57), STEP 3 under accth, STEP 4 with its retrials and STEP 5 run on the device, a wave per fit.
+// gadfit_linalg.F90:36-57), STEP 3 under accth, STEP 4 with its retrials and STEP 5 run on the device, a wave or -- gfh_set_batch_lanes --
+// a row of 16 lanes per fit.
 int gfh_fit_batch(gfh_ctx* c, double* pars, int na, const int32_t* active, const gfh_fit_options* o, gfh_batch_result* results,
                   double* seconds) try {
   if (check_context(c, "gfh_fit_batch") || check_model(c, "gfh_fit_batch", na, active)) return 1;
@@ -157,7 +171,8 @@ int gfh_fit_batch(gfh_ctx* c, double* pars, int na, const int32_t* active, const
   if (!c->batch.on_device) return fail(c, "gfh_fit_batch: no batch data on the device (gfh_set_batch_data)");
   gfh::Range range("gadfit gfh_fit_batch");
   ModelKernels* mk = nullptr;
-  if (batch_kernels(c, std::vector<int32_t>(active, active + na), true, &mk)) return 1;
+  const int lanes = batch_lanes(c, na), per_wg = 256 / lanes;
+  if (batch_kernels(c, std::vector<int32_t>(active, active + na), lanes, true, &mk)) return 1;
   const int64_t nf = c->batch.n_fits; const int np = c->model.n_pars;
   const size_t pb = sizeof(double) * (size_t)nf * (size_t)np, rb = sizeof(gfh_batch_result) * (size_t)nf;
   if (dev_alloc(c, c->batch.io, pb + rb)) return 1;
@@ -168,7 +183,8 @@ int gfh_fit_batch(gfh_ctx* c, double* pars, int na, const int32_t* active, const
   void* dp = c->batch.io.p; void* recs = c->batch.io.as<char>() + pb; long long n = nf; void* stp = c->status.p;
   void* args[] = {&x, &y, &w, &off, &dp, &bo, &recs, &n, &stp};
   HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-  HIPCHK(c, hipModuleLaunchKernel(mk->fit_batch, (unsigned)((nf + 3) / 4), 1, 1, 256, 1, 1, 0, c->stream, args, nullptr));
+  HIPCHK(c, hipModuleLaunchKernel(mk->fit_batch, (unsigned)((nf + per_wg - 1) / per_wg), 1, 1, 256, 1, 1, 0, c->stream, args, nullptr));
+  c->batch.last_lanes = lanes;
   HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
   HIPCHK(c, hipMemcpyAsync(c->batch.host.data(), c->batch.io.p, pb + rb, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -187,7 +203,8 @@ int gfh_batch_pass(gfh_ctx* c, const double* pars, int na, const int32_t* active
   NEED_GPU(c);
   if (!c->batch.on_device) return fail(c, "gfh_batch_pass: no batch data on the device (gfh_set_batch_data)");
   ModelKernels* mk = nullptr;
-  if (batch_kernels(c, std::vector<int32_t>(active, active + na), true, &mk)) return 1;
+  const int lanes = batch_lanes(c, na), per_wg = 256 / lanes;
+  if (batch_kernels(c, std::vector<int32_t>(active, active + na), lanes, true, &mk)) return 1;
   const int64_t nf = c->batch.n_fits; const int np = c->model.n_pars;
   const size_t rec = (size_t)na * na + na + 1;
   const size_t pb = sizeof(double) * (size_t)nf * (size_t)np, ib = sizeof(double) * (size_t)nf * rec;
@@ -197,7 +214,8 @@ int gfh_batch_pass(gfh_ctx* c, const double* pars, int na, const int32_t* active
   void* x = c->batch.x.p; void* y = c->batch.y.p; void* w = c->batch.w.p; void* off = c->batch.off_d.p;
   void* dp = c->batch.io.p; void* img = c->batch.img.p; long long n = nf; void* stp = c->status.p;
   void* args[] = {&x, &y, &w, &off, &dp, &img, &n, &stp};
-  HIPCHK(c, hipModuleLaunchKernel(mk->batch_pass, (unsigned)((nf + 3) / 4), 1, 1, 256, 1, 1, 0, c->stream, args, nullptr));
+  HIPCHK(c, hipModuleLaunchKernel(mk->batch_pass, (unsigned)((nf + per_wg - 1) / per_wg), 1, 1, 256, 1, 1, 0, c->stream, args, nullptr));
+  c->batch.last_lanes = lanes;
   HIPCHK(c, hipMemcpyAsync(c->batch.host.data(), c->batch.img.p, ib, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const double* h = reinterpret_cast<const double*>(c->batch.host.data());
@@ -210,11 +228,12 @@ int gfh_batch_pass(gfh_ctx* c, const double* pars, int na, const int32_t* active
   return 0;
 } catch (const std::exception& e) { return fail(c, std::string("gfh_batch_pass: ") + e.what()); }
 
-// The generated source of the batch translation unit for the current model and an active set, as gfh_model_source.
+// The generated source of the batch translation unit for the current model and an active set, as gfh_model_source: in the form of
+// the context's setting (under auto: what the rule gives for the geometry held, 64 without one); gfh_batch_prepare alike.
 int64_t gfh_batch_source(gfh_ctx* c, int na, const int32_t* active, char* buf, int64_t cap) try {
   if (check_context(c, "gfh_batch_source") || check_model(c, "gfh_batch_source", na, active)) return -1;
   std::string src, err;
-  if (!generate_source(c->model, std::vector<int32_t>(active, active + na), batch_config(c), &src, &err)) { fail(c, err); return -1; }
+  if (!generate_source(c->model, std::vector<int32_t>(active, active + na), batch_config(c, batch_lanes(c, na)), &src, &err)) { fail(c, err); return -1; }
   if (buf && cap > 0) { const size_t n = std::min<size_t>((size_t)cap - 1, src.size()); memcpy(buf, src.data(), n); buf[n] = 0; }
   return (int64_t)src.size() + 1;
 } catch (const std::exception& e) { fail(c, std::string("gfh_batch_source: ") + e.what()); return -1; }
@@ -222,7 +241,26 @@ int64_t gfh_batch_source(gfh_ctx* c, int na, const int32_t* active, char* buf, i
 // Compiles the batch translation unit (or finds it in the cache) without launching, as gfh_model_prepare; needs no GPU.
 int gfh_batch_prepare(gfh_ctx* c, int na, const int32_t* active) try {
   if (check_context(c, "gfh_batch_prepare") || check_model(c, "gfh_batch_prepare", na, active)) return 1;
-  return batch_kernels(c, std::vector<int32_t>(active, active + na), false, nullptr);
+  return batch_kernels(c, std::vector<int32_t>(active, active + na), batch_lanes(c, na), false, nullptr);
 } catch (const std::exception& e) { return fail(c, std::string("gfh_batch_prepare: ") + e.what()); }
+
+// Lanes per fit of the batch kernels from here on: 64 (the default) a wave per fit, 16 a DPP row per fit and four fits per wave, 0
+// auto -- gfh_batch_auto_lanes at every call.  A setting, not a launch: needs no GPU and no model.
+int gfh_set_batch_lanes(gfh_ctx* c, int lanes) try {
+  if (check_context(c, "gfh_set_batch_lanes")) return 1;
+  if (lanes != 64 && lanes != 16 && lanes != 0)
+    return fail(c, "gfh_set_batch_lanes: " + std::to_string(lanes) + " lanes per fit are not built (64: a wave per fit, 16: a row per fit, 0: auto)");
+  c->batch.lanes = lanes;
+  return 0;
+} catch (const std::exception& e) { return fail(c, std::string("gfh_set_batch_lanes: ") + e.what()); }
+
+// The form of the last batch launch of this context (64 or 16; 0: none yet), so that a test asserts the dispatch.
+int gfh_debug_batch_lanes(gfh_ctx* c) { return c ? c->batch.last_lanes : 0; }
+
+// The auto rule: a function of the active count and the longest spectrum of the batch, never of the data.
+int gfh_batch_auto_lanes(int n_act, int64_t longest) {
+  if (n_act < 1 || n_act > kValuGramMax || longest < 1) return 64;
+  return longest <= (n_act <= 4 ? kRowUpTo4 : kRowUpTo8) ? 16 : 64;
+}
 
 }  // extern "C"

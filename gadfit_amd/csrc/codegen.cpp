@@ -1173,10 +1173,11 @@ static bool emit_batch_kernels(const Model& m, const std::vector<int32_t>& activ
   if (NA < 1 || NA > kValuGramMax) { *err = "batch kernels: 1 to " + std::to_string(kValuGramMax) + " active parameters"; return false; }
   if (m.has_integrals() || m.branching() || m.n_aux > 0) { *err = "batch kernels: models with integrate(), variant tapes or auxiliary columns are not carried"; return false; }
   if (cfg.finite_diff || cfg.loss != 0 || !cfg.omega_jt) { *err = "batch kernels: use_ad = 0, robust losses and GADFIT_HIP_OMEGA_JT=0 are not carried"; return false; }
+  if (cfg.batch_lanes != 64 && cfg.batch_lanes != 16) { *err = "batch kernels: 64 or 16 lanes per fit"; return false; }
   s << "\n#define GFH_BATCH 1\n#define GFH_BACT {";
   for (int j = 0; j < NA; j++) s << (j ? ", " : "") << active[j];
-  s << "}\n";
-  s << kBatchFit;                   // batch_fit.hip: gfh_k_fit_batch, gfh_k_batch_pass
+  s << "}\n#define GFH_BLANES " << cfg.batch_lanes << "\n";
+  s << kBatchFit;                   // batch_fit.hip: gfh_k_fit_batch, gfh_k_batch_pass, written once against GFH_BLANES
   return true;
 }
 

@@ -185,6 +185,9 @@ struct gfh_ctx {
     int64_t n_fits = 0;
     std::vector<int64_t> off;       // [n_fits + 1]
     int64_t min_points = 0;         // of the shortest spectrum
+    int64_t max_points = 0;         // of the longest: with the active count, all the auto rule of gfh_set_batch_lanes reads
+    int lanes = 64;                 // gfh_set_batch_lanes: 64 a wave per fit, 16 a DPP row per fit, 0 auto (gfh_batch_auto_lanes)
+    int last_lanes = 0;             // the form of the last batch launch (gfh_debug_batch_lanes); 0: none yet
     bool on_device = false;
     gfh::DevBuf x, y, w, off_d, io, img;
     std::vector<char> host;         // where the one device-to-host copy of a call lands

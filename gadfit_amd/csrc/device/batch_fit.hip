@@ -1,12 +1,17 @@
 
-// ---- Batched independent fits: MANY Levenberg-Marquardt fits of this model in one launch, a wave per fit from its first chi2 to
-// its exit (gadfit.F90:670-915 restated per wave; lm.cpp gfh_fit is the host form of the same lines).  256 threads = 4 waves that
-// never talk to each other: no LDS, no barrier, no atomics; fit f = global wave index.  Lane l takes points off[f] + l, + 64, ...
-// of the fit's contiguous x, y, w (coalesced 512 B rows, no padding between fits); the lanes past the end of the last row re-read
-// the fit's last point with w = 0.  STEP 1+2 is the per-lane outer product of the fused kernel's VALU form (GFH_NA <=
-// GFH_VALU_GRAM_MAX) finished by gfh_wave_sum; the sums come back as wave-uniform values (v_readfirstlane) and every lane runs the
-// damped solve and the lambda logic on them redundantly -- the same operations on the same numbers, so the same decisions -- which
-// keeps the parameter block, the saved parameters and the normal equations in registers for the whole fit.
+// ---- Batched independent fits: MANY Levenberg-Marquardt fits of this model in one launch, GFH_BLANES lanes per fit from its first
+// chi2 to its exit (gadfit.F90:670-915 restated per fit; lm.cpp gfh_fit is the host form of the same lines).  256 threads whose fits
+// never talk to each other: no LDS, no barrier, no atomics; fit f = global thread index / GFH_BLANES.  Lane l of a fit takes points
+// off[f] + l, + GFH_BLANES, ... of the fit's contiguous x, y, w (coalesced rows, no padding between fits); the lanes past the end of
+// the last row re-read the fit's last point with w = 0.  STEP 1+2 is the per-lane outer product of the fused kernel's VALU form
+// (GFH_NA <= GFH_VALU_GRAM_MAX) finished by gfh_b_sum, which leaves the same bits in every lane of the fit; every lane runs the damped
+// solve and the lambda logic on them redundantly -- the same operations on the same numbers, so the same decisions -- which keeps the
+// parameter block, the saved parameters and the normal equations in registers for the whole fit.
+//   GFH_BLANES 64: a wave per fit, 4 fits per workgroup.  The sums come back as wave-uniform values (v_readfirstlane).
+//   GFH_BLANES 16: a DPP row per fit, 4 fits per wave, 16 per workgroup -- for spectra of a few dozen points, where a wave per fit
+//     keeps 48 lanes on w = 0.  The sums are reduced inside the row alone (gfh_b_sum below) and the state is per-lane, replicated
+//     across the row; nothing crosses a row, so neighbouring fits of a wave do not see each other, and exits at different iterations
+//     or spectra of different lengths inside a wave are ordinary divergence: a row is always wholly live or wholly gone.
 #define GFH_BNP (GFH_NA * (GFH_NA + 1) / 2)
 #define GFH_BNACC (GFH_BNP + GFH_NA + 1)
 #define GFH_BIDX(a, b) ((a) * GFH_NA - (a) * ((a) - 1) / 2 + ((b) - (a)))      // packed upper triangle, a <= b
@@ -18,12 +23,36 @@ struct gfh_batch_opts {          // the options of gfh_fit that the batch carrie
 struct gfh_batch_rec { int iterations, exit_reason, n_sweeps, n_chi2, n_omega, dof; double lambda, chi2; };
 struct gfh_bdata { const double* __restrict__ x; const double* __restrict__ y; const double* __restrict__ w; i64 b, e; int lane; };
 
+#if GFH_BLANES == 64
 static __device__ __forceinline__ double gfh_uni(const double v) {      // lane 0's value as a wave-uniform one
   const long long b = __double_as_longlong(v);
   const int lo = __builtin_amdgcn_readfirstlane((int)b), hi = __builtin_amdgcn_readfirstlane((int)(b >> 32));
   return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
 }
-// the inputs of pass row i0 (wave-uniform) for this lane; past the end: the last point with w = 0
+static __device__ __forceinline__ double gfh_b_sum(const double t) { return gfh_uni(gfh_wave_sum(t)); }
+#define GFH_BFIT(tid) ((i64)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)((tid) >> 6)))
+#elif GFH_BLANES == 16
+static __device__ __forceinline__ double gfh_uni(const double v) { return v; }      // the state is per-lane, replicated across the row
+// lane l reads lane (l - N) mod 16 of its row of 16 (DPP row_ror:N): every lane has a source inside its own row
+template <int N> static __device__ __forceinline__ double gfh_row_ror(const double v) {
+  const long long b = __double_as_longlong(v);
+  const int lo = __builtin_amdgcn_update_dpp(0, (int)b, 0x120 | N, 0xf, 0xf, false);
+  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), 0x120 | N, 0xf, 0xf, false);
+  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
+}
+// the sum of a row in every lane of it: the rotation butterfly t_l += t_(l-8), (l-4), (l-2), (l-1) (indices mod 16).  After the
+// level of distance d the values have period d in l (a + b and b + a are the same bits), so every lane ends with the same bits, and
+// lane 0's are those of the row levels of gfh_wave_sum (wave_sum.hip) with some operands commuted.  gfx9 has no row_share to
+// broadcast with, and v_readlane / ds_bpermute would cross rows.
+static __device__ __forceinline__ double gfh_b_sum(double t) {
+  t += gfh_row_ror<8>(t); t += gfh_row_ror<4>(t); t += gfh_row_ror<2>(t); t += gfh_row_ror<1>(t);
+  return t;
+}
+#define GFH_BFIT(tid) ((i64)blockIdx.x * 16 + (i64)((tid) >> 4))
+#else
+#error "GFH_BLANES: 64 (a wave per fit) or 16 (a DPP row per fit)"
+#endif
+// the inputs of pass row i0 (uniform in the fit) for this lane; past the end: the last point with w = 0
 #define GFH_BLOAD(X, Y, W, i0) { const i64 i_ = (i0) + d.lane; const i64 c_ = i_ < d.e ? i_ : d.e - 1; \
   X = d.x[c_]; Y = d.y[c_]; const double w_ = d.w[c_]; W = i_ < d.e ? w_ : 0.0; }
 
@@ -34,9 +63,9 @@ static __device__ __forceinline__ void gfh_b_sweep(const gfh_bdata& d, const dou
   for (int k = 0; k < GFH_BNACC; k++) av[k] = 0.0;
   double Xc, Yc, Wc;
   GFH_BLOAD(Xc, Yc, Wc, d.b)
-  for (i64 i0 = d.b; i0 < d.e; i0 += 64) {
+  for (i64 i0 = d.b; i0 < d.e; i0 += GFH_BLANES) {
     double Xn, Yn, Wn;
-    GFH_BLOAD(Xn, Yn, Wn, i0 + 64 < d.e ? i0 + 64 : i0)       // next row's inputs (the last row re-reads its own)
+    GFH_BLOAD(Xn, Yn, Wn, i0 + GFH_BLANES < d.e ? i0 + GFH_BLANES : i0)       // next row's inputs (the last row re-reads its own)
     double F, G[GFH_NA];
     gfh_point_grad(Xc, P, F, G, status, (const double*)nullptr, 0 GFH_MESH_NONE GFH_SLOT(i0 + d.lane));
     const double R = (Yc - F) * Wc;                            // gadfit.F90:682-683
@@ -53,20 +82,20 @@ static __device__ __forceinline__ void gfh_b_sweep(const gfh_bdata& d, const dou
     Xc = Xn; Yc = Yn; Wc = Wn;
   }
 #pragma unroll
-  for (int k = 0; k < GFH_BNACC; k++) S[k] = gfh_uni(gfh_wave_sum(av[k]));
+  for (int k = 0; k < GFH_BNACC; k++) S[k] = gfh_b_sum(av[k]);
 }
 // chi2() (gadfit.F90:1015-1034): every parameter passive, value only
 static __device__ __forceinline__ double gfh_b_chi2(const gfh_bdata& d, const double* __restrict__ P, int* status) {
   double acc = 0.0, Xc, Yc, Wc;
   GFH_BLOAD(Xc, Yc, Wc, d.b)
-  for (i64 i0 = d.b; i0 < d.e; i0 += 64) {
+  for (i64 i0 = d.b; i0 < d.e; i0 += GFH_BLANES) {
     double Xn, Yn, Wn;
-    GFH_BLOAD(Xn, Yn, Wn, i0 + 64 < d.e ? i0 + 64 : i0)
+    GFH_BLOAD(Xn, Yn, Wn, i0 + GFH_BLANES < d.e ? i0 + GFH_BLANES : i0)
     const double r = (Yc - gfh_point_value(Xc, P, status, (const double*)nullptr, 0 GFH_MESH_NONE GFH_SLOT(i0 + d.lane))) * Wc;   // gadfit.F90:1024-1026
     acc += r * r;
     Xc = Xn; Yc = Yn; Wc = Wn;
   }
-  return gfh_uni(gfh_wave_sum(acc));
+  return gfh_b_sum(acc);
 }
 // STEP 3 (gadfit.F90:715-735): omega_i = -f''_delta1(x_i) w_i and J^T omega with the Jacobian row recomputed, as gfh_k_omega_jt
 static __device__ __forceinline__ void gfh_b_omega(const gfh_bdata& d, const double* __restrict__ P, const double* __restrict__ DP, int* status,
@@ -75,9 +104,9 @@ static __device__ __forceinline__ void gfh_b_omega(const gfh_bdata& d, const dou
 #pragma unroll
   for (int a = 0; a < GFH_NA; a++) acc[a] = 0.0;
   GFH_BLOAD(Xc, Yc, Wc, d.b)
-  for (i64 i0 = d.b; i0 < d.e; i0 += 64) {
+  for (i64 i0 = d.b; i0 < d.e; i0 += GFH_BLANES) {
     double Xn, Yn, Wn;
-    GFH_BLOAD(Xn, Yn, Wn, i0 + 64 < d.e ? i0 + 64 : i0)
+    GFH_BLOAD(Xn, Yn, Wn, i0 + GFH_BLANES < d.e ? i0 + GFH_BLANES : i0)
     double G[GFH_NA];
     const double om = -gfh_point_dd_grad(Xc, P, DP, G, status, (const double*)nullptr, 0 GFH_MESH_NONE GFH_SLOT(i0 + d.lane)) * Wc;   // gadfit.F90:722-723
 #pragma unroll
@@ -89,7 +118,7 @@ static __device__ __forceinline__ void gfh_b_omega(const gfh_bdata& d, const dou
   }
   (void)Yc;
 #pragma unroll
-  for (int a = 0; a < GFH_NA; a++) JTo[a] = gfh_uni(gfh_wave_sum(acc[a]));
+  for (int a = 0; a < GFH_NA; a++) JTo[a] = gfh_b_sum(acc[a]);
 }
 // (J^T J + lambda DTD) out = rhs (gadfit.F90:711-713): potrf_upper_plain and potrs_upper of lm.cpp operation for operation,
 // unrolled, without contraction (the host has none), so that this solve and the host's return the same bits from the same
@@ -151,10 +180,10 @@ void gfh_k_fit_batch(const double* __restrict__ x, const double* __restrict__ y,
                      const i64* __restrict__ off, double* __restrict__ pars, const gfh_batch_opts o,
                      gfh_batch_rec* __restrict__ recs, const i64 n_fits, int* __restrict__ status) {
 #pragma clang fp contract(off)
-  const i64 f = (i64)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const i64 f = GFH_BFIT(threadIdx.x);
   if (f >= n_fits) return;
   constexpr int act[GFH_NA] = GFH_BACT;
-  const gfh_bdata d = {x, y, w, off[f], off[f + 1], (int)(threadIdx.x & 63)};
+  const gfh_bdata d = {x, y, w, off[f], off[f + 1], (int)(threadIdx.x & (GFH_BLANES - 1))};
   double P[GFH_NP], old_pars[GFH_NA], DTD[GFH_NA], delta1[GFH_NA], delta2[GFH_NA], S[GFH_BNACC], JTr[GFH_NA];
 #pragma unroll
   for (int k = 0; k < GFH_NP; k++) P[k] = gfh_uni(pars[f * GFH_NP + k]);
@@ -247,9 +276,9 @@ extern "C" __global__ __launch_bounds__(256)
 void gfh_k_batch_pass(const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ w,
                       const i64* __restrict__ off, const double* __restrict__ pars, double* __restrict__ img,
                       const i64 n_fits, int* __restrict__ status) {
-  const i64 f = (i64)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const i64 f = GFH_BFIT(threadIdx.x);
   if (f >= n_fits) return;
-  const gfh_bdata d = {x, y, w, off[f], off[f + 1], (int)(threadIdx.x & 63)};
+  const gfh_bdata d = {x, y, w, off[f], off[f + 1], (int)(threadIdx.x & (GFH_BLANES - 1))};
   double P[GFH_NP], S[GFH_BNACC];
 #pragma unroll
   for (int k = 0; k < GFH_NP; k++) P[k] = gfh_uni(pars[f * GFH_NP + k]);

@@ -284,13 +284,14 @@ def gadf_fit(lambda_=None, lam_up=None, lam_down=None, accth=None, grad_chi2=Non
 
 
 def gadf_fit_batch(xs, ys, ws, pars, lambda_=None, lam_up=None, lam_down=None, accth=None, rel_error=None, chi2_rel=None,
-                   chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, **kw):
+                   chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, lanes_per_fit=None, **kw):
     """Many independent fits of the session's model in one kernel launch (gfh_fit_batch): gadf_fit's loop (gadfit.F90:670-915) per
     spectrum, each with its own data, start parameters, lambda history and exit.  On a session initialised with one dataset slot
     (``gadf_init(f)``); the active set is the one ``gadf_set`` left.  ``xs, ys, ws``: one array per spectrum (``ws``: the weights as
     used in (y - f) * w; None = ones); ``pars`` [n_fits][n_pars] start values, passive entries included.  The fit arguments are
     gadf_fit's; those a device-resident loop does not carry (uphill, nielsen, umnigh, grad_chi2, cos_phi, rel_error_global) are refused
-    by the library, and max_iter is required.  Returns (parameters [n_fits][n_pars], record array of per-fit results with the fields
+    by the library, and max_iter is required.  ``lanes_per_fit``: 64 a wave per fit, 16 a row of 16 lanes per fit and four fits per wave
+    (short spectra), 0 auto; None leaves the session's setting (64 unless set before).  Returns (parameters [n_fits][n_pars], record array of per-fit results with the fields
     iterations, exit_reason, n_sweeps, n_chi2, n_omega, dof, lambda_, chi2)."""
     _need_init()
     if 'lambda' in kw:
@@ -326,7 +327,7 @@ def gadf_fit_batch(xs, ys, ws, pars, lambda_=None, lam_up=None, lam_down=None, a
     np.cumsum([v.size for v in xs], out=off[1:])
     try:
         _S.ctx.set_batch_data(off, np.concatenate(xs), np.concatenate(ys), np.concatenate(ws))
-        out, res, _ = _S.ctx.fit_batch(pars, active, DTD_min=DTD_min, lambda_=_f32(lambda_), lam_up=_f32(lam_up), lam_down=_f32(lam_down),
+        out, res, _ = _S.ctx.fit_batch(pars, active, DTD_min=DTD_min, lanes_per_fit=lanes_per_fit, lambda_=_f32(lambda_), lam_up=_f32(lam_up), lam_down=_f32(lam_down),
                                        accth=_f32(accth), rel_error=_f32(rel_error), chi2_rel=_f32(chi2_rel), chi2_abs=_f32(chi2_abs),
                                        lam_incs=lam_incs, max_iter=max_iter, damp_max=None if damp_max is None else int(damp_max),
                                        **{k: v for k, v in kw.items() if v is not None})

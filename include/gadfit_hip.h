@@ -416,6 +416,17 @@ int  gfh_batch_pass(gfh_ctx* ctx, const double* pars, int n_act, const int32_t* 
  * model's point functions) as gfh_model_source, and its compilation without a launch as gfh_model_prepare (needs no GPU). */
 int64_t gfh_batch_source(gfh_ctx* ctx, int n_act, const int32_t* active_pars, char* buf, int64_t cap);
 int  gfh_batch_prepare(gfh_ctx* ctx, int n_act, const int32_t* active_pars);
+/* Lanes per fit of the batch kernels, a setting of the context read by every later gfh_fit_batch, gfh_batch_pass, gfh_batch_source
+ * and gfh_batch_prepare.  64 (the default): a wave per fit.  16: a DPP row of 16 lanes per fit, four fits per wave and sixteen per
+ * workgroup -- for short spectra, where a wave per fit keeps most lanes on padding; the sums are reduced inside the row, fits of one
+ * wave do not see each other, and every check and refusal is the same.  0: auto, gfh_batch_auto_lanes(n_act, longest spectrum of the
+ * batch held; 64 where the context holds none).  Any other value is refused.  Both forms of an active set stay loaded side by side.
+ * The two forms add a fit's point sums in different orders once a spectrum has more than 16 points; up to 16 they return the same bits. */
+int  gfh_set_batch_lanes(gfh_ctx* ctx, int lanes);
+/* The auto rule: 16 or 64 from the active count and the longest spectrum alone, as measured (profiles/batch_rows.json). */
+int  gfh_batch_auto_lanes(int n_act, int64_t longest_spectrum);
+/* 64 or 16: the form of the last batch launch of this context (0: none yet).  For tests that assert the dispatch. */
+int  gfh_debug_batch_lanes(gfh_ctx* ctx);
 
 /* ---- Jacobian_indices / dim (gadfit.F90:615-631) as a helper for callers */
 int  gfh_jacobian_indices(int n_datasets, int n_act, const int32_t* active_pars,

@@ -2,7 +2,9 @@
 profiles/r05_small_fits.txt: 1000 points, a Gaussian on a background, 4 parameters, lambda0 = 1, max_iter = 30.
 
     python tools/bench_batch.py [--sizes 1024,16384,131072] [--launches 7] [--warmup 2] [--one-at-a-time 200]
-                                [--observed FILE [--observed-only]] [--out profiles/batch_fits.json]
+                                [--points 1000] [--lanes 64] [--observed FILE [--observed-only]] [--out profiles/batch_fits.json]
+    python tools/bench_batch.py --rows [--points 8,16,32,64,128,256,1000] [--lanes 64,16] [--sizes 131072] [--registers]
+                                [--observed FILE [--observed-only]] [--out profiles/batch_rows.json]
 
 Per batch size: warm-up launches, then the median of the timed launches -- device time from the HIP events around the kernel
 (gfh_fit_batch's `seconds`) and wall time around the whole call (parameters down, launch, results back).  Two yardsticks, neither of
@@ -14,7 +16,16 @@ them the code under test:
     the batch kernel's time for the same passes (whose spectra stay in cache from one pass of a fit to the next).
 Needs a GPU; there is no fallback.  --observed: a JSON file of observed parity maxima copied into the record, written under
 GADFIT_BATCH_OBSERVE by tests/test_gpu_batch_shapes.py and tests/test_gpu_batch.py run in ONE pytest process (the maxima are kept per
-process, so a module run alone writes its own keys only).  --observed-only: the record's timings stay, its maxima are replaced."""
+process, so a module run alone writes its own keys only).  --observed-only: the record's timings stay, its maxima are replaced.
+
+--points, --lanes: the spectrum length and the lanes per fit (gfh_set_batch_lanes) of the measurement above.
+--rows: the two forms of the batch kernels against each other, the table the auto rule of gfh_set_batch_lanes(0) is written from.
+Per model (this file's 4-parameter Gaussian; exp4, four exponentials with all 8 parameters active), spectrum length and form:
+--sizes[0] fits per launch, the median and the min-max of the timed launches, device and wall time per fit.  The yardstick of the row
+form is the wave form on the same card in the same run, never the row form's own time: `row_wins` is tests/batch_row_cases.row_wins
+(the medians differ by more than the sum of the two forms' min-max spreads), and `auto_rule` is the largest measured length with
+row_wins per active-count class.  --registers: the compiler's register, scratch and occupancy figures of the four kernels
+(hipcc -Rpass-analysis=kernel-resource-usage on the generated source; needs hipcc, no GPU)."""
 import argparse
 import json
 import os
@@ -30,7 +41,7 @@ sys.path.insert(0, ROOT)
 from gadfit_amd import _lib                       # noqa: E402
 from gadfit_amd.ad import exp, trace_model        # noqa: E402
 
-N_POINTS, MAX_ITER, LAMBDA0 = 1000, 30, 1.0
+N_POINTS, MAX_ITER, LAMBDA0 = 1000, 30, 1.0          # (N_POINTS: --points)
 START = np.array([2.5, 4.3, 1.0, 0.3])
 ACTIVE = [0, 1, 2, 3]
 
@@ -39,30 +50,193 @@ def model(p, x):
     return p[0] * exp(-((x - p[1]) / p[2]) ** 2) + p[3]
 
 
-def spectra(n_fits):
+def spectra(n_fits, n_points=None):
     """bench_many_small_fits.F90's spectrum k, with the peak position spread over [4, 5) so that a large batch holds no two alike"""
-    x = 10.0 * (np.arange(N_POINTS) + 0.5) / N_POINTS
+    n_points = n_points or N_POINTS
+    x = 10.0 * (np.arange(n_points) + 0.5) / n_points
     k = np.arange(1, n_fits + 1, dtype=np.float64)
     pos = 4.0 + np.mod(k * 0.6180339887498949, 1.0)
-    y = np.empty((n_fits, N_POINTS))
+    y = np.empty((n_fits, n_points))
     for lo in range(0, n_fits, 8192):
         hi = min(n_fits, lo + 8192)
         y[lo:hi] = 3.0 * np.exp(-((x[None, :] - pos[lo:hi, None]) / 0.8) ** 2) + 0.5 + 1.0e-3 * np.sin(977.0 * x[None, :] + k[lo:hi, None])
     return x, y, pos
 
 
+def model_exp4(p, x):
+    y = p[0] * exp(-(x / p[1]))
+    for k in range(1, 4):
+        y = y + p[2 * k] * exp(-(x / p[2 * k + 1]))
+    return y
+
+
+EXP4_TRUTH = np.array([5.0, 0.5, 3.0, 2.0, 2.0, 8.0, 1.0, 30.0])
+
+
+def spectra_exp4(n_fits, n_points):
+    """four exponentials on x in (0.05, 100): the amplitudes spread by +-10 % from fit to fit, a ripple of 1e-3 as in spectra()"""
+    x = 0.05 + 99.95 * (np.arange(n_points) + 0.5) / n_points
+    k = np.arange(1, n_fits + 1, dtype=np.float64)
+    y = np.empty((n_fits, n_points))
+    for lo in range(0, n_fits, 8192):
+        hi = min(n_fits, lo + 8192)
+        amp = 0.9 + 0.2 * np.mod(k[lo:hi, None] * 0.6180339887498949 + 0.25 * np.arange(4)[None, :], 1.0)
+        y[lo:hi] = 1.0e-3 * np.sin(977.0 * x[None, :] + k[lo:hi, None])
+        for j in range(4):
+            y[lo:hi] += (EXP4_TRUTH[2 * j] * amp[:, j:j + 1]) * np.exp(-x[None, :] / EXP4_TRUTH[2 * j + 1])
+    return x, y
+
+
+ROW_MODELS = {
+    'gauss4': dict(model=model, n_pars=4, active=ACTIVE, start=START, what='gaussian on a background, 4 of 4 parameters active'),
+    'exp4': dict(model=model_exp4, n_pars=8, active=list(range(8)), start=EXP4_TRUTH * np.where(np.arange(8) % 2 == 0, 1.05, 0.95),
+                 what='four exponentials, 8 of 8 parameters active'),
+}
+
+
+def kernel_registers(src):
+    """{kernel: {vgprs, agprs, sgprs, scratch_bytes_per_lane, waves_per_simd}} of the two batch kernels of a generated source"""
+    import re
+    import subprocess
+    import tempfile
+    with tempfile.TemporaryDirectory() as d:
+        f = os.path.join(d, 'unit.hip')
+        with open(f, 'w') as fh:
+            fh.write('#include <hip/hip_runtime.h>\n' + src)
+        r = subprocess.run([os.path.join(os.environ.get('ROCM_PATH', '/opt/rocm'), 'bin', 'hipcc'), '-O3', '-std=c++17', '--offload-arch=gfx950',
+                            '-ffp-contract=on', '--cuda-device-only', '-c', f, '-o', os.path.join(d, 'unit.o'),
+                            '-Rpass-analysis=kernel-resource-usage'], capture_output=True, text=True, check=True)
+    out, name = {}, None
+    keys = {'VGPRs': 'vgprs', 'AGPRs': 'agprs', 'TotalSGPRs': 'sgprs', 'ScratchSize [bytes/lane]': 'scratch_bytes_per_lane',
+            'Occupancy [waves/SIMD]': 'waves_per_simd'}
+    for line in r.stderr.splitlines():
+        m = re.search(r'remark:\s+(.*?): (\S+) \[-Rpass', line)
+        if not m:
+            continue
+        if m.group(1) == 'Function Name':
+            name = m.group(2) if m.group(2) in ('gfh_k_fit_batch', 'gfh_k_batch_pass') else None
+            if name:
+                out[name] = {}
+        elif name and m.group(1) in keys:
+            out[name][keys[m.group(1)]] = int(m.group(2))
+    return out
+
+
+def registers_record():
+    rec = {}
+    c = _lib.Context(-1)
+    exp2 = dict(model=lambda p, x: p[0] * exp(-(x / p[1])) + p[2] * exp(-(x / p[3])), n_pars=4, active=ACTIVE)      # (tests/models.py: model_exp2)
+    for name, m in list(ROW_MODELS.items()) + [('exp2', exp2)]:
+        c.set_model(trace_model(m['model'], m['n_pars']))
+        for lanes in (64, 16):
+            c.set_batch_lanes(lanes)
+            rec['%s_lanes%d' % (name, lanes)] = kernel_registers(c.batch_source(m['active']))
+    c.close()
+    return rec
+
+
+def rows_main(a, points, lanes_list):
+    """the two forms against each other over spectrum lengths (see the module's text)"""
+    from tests import batch_row_cases as RC
+    nf = int(a.sizes.split(',')[0])
+    rec = dict(method='%d fits per launch; per (model, length, form) the median and the min-max of %d launches after %d warm-up launches; device = HIP '
+                      'events around the kernel, wall = around the call; lambda0 = %g, max_iter = %d and no other exit, so both forms run the same passes up to the accept / reject decisions that rounding takes past convergence (the totals are in each record); '
+                      'the forms alternate on one context, one card, one run' % (nf, a.launches, a.warmup, LAMBDA0, MAX_ITER),
+               n_fits=nf, measurements=[])
+    if os.path.exists(a.out):          # (--registers and --observed of earlier calls stay)
+        old = json.load(open(a.out))
+        for k in ('registers', 'observed_maxima_against_the_oracle'):
+            if k in old:
+                rec[k] = old[k]
+    kw = dict(lambda_=LAMBDA0, max_iter=MAX_ITER)
+    for name, m in ROW_MODELS.items():
+        ctx = _lib.Context(0)
+        ctx.set_model(trace_model(m['model'], m['n_pars']))
+        for n in points:
+            if name == 'gauss4':
+                x, y, _ = spectra(nf, n)
+            else:
+                x, y = spectra_exp4(nf, n)
+            off = np.arange(nf + 1, dtype=np.int64) * n
+            ctx.set_batch_data(off, np.tile(x, nf), y.ravel(), np.ones(nf * n))
+            del y
+            start = np.tile(m['start'], (nf, 1))
+            entry = dict(model=name, what=m['what'], n_active=len(m['active']), points=n, lanes={})
+            times = {l: ([], []) for l in lanes_list}
+            out = {}
+            for it in range(a.warmup + a.launches):
+                for l in lanes_list:          # the forms alternate launch by launch: a drift of the card's clock meets both alike
+                    t0 = time.perf_counter()
+                    p, r, sec = ctx.fit_batch(start, m['active'], lanes_per_fit=l, **kw)
+                    t1 = time.perf_counter()
+                    if ctx.batch_lanes_used() != l:
+                        sys.exit('the launch did not take the form asked for')
+                    if it >= a.warmup:
+                        times[l][0].append(sec); times[l][1].append(t1 - t0)
+                    out[l] = (p, r)
+            for l in lanes_list:
+                dev, wall = times[l]
+                p, r = out[l]
+                d = statistics.median(dev); w = statistics.median(wall)
+                entry['lanes'][str(l)] = dict(
+                    device_ms=1e3 * d, device_ms_min=1e3 * min(dev), device_ms_max=1e3 * max(dev), wall_ms=1e3 * w, wall_ms_min=1e3 * min(wall),
+                    wall_ms_max=1e3 * max(wall), device_us_per_fit=1e6 * d / nf, wall_us_per_fit=1e6 * w / nf,
+                    passes=dict(sweeps=int(r['n_sweeps'].sum()), chi2=int(r['n_chi2'].sum()), omega=int(r['n_omega'].sum())),
+                    exit_reasons={str(int(v)): int(np.sum(r['exit_reason'] == v)) for v in sorted(set(r['exit_reason'].tolist()))},
+                    finite=bool(np.all(np.isfinite(p))))
+            if '16' in entry['lanes'] and '64' in entry['lanes']:
+                a16, a64 = out[16], out[64]
+                entry['fits_with_equal_counts_in_both_forms'] = int(np.sum((a16[1]['n_sweeps'] == a64[1]['n_sweeps']) & (a16[1]['n_chi2'] == a64[1]['n_chi2']) &
+                                                                           (a16[1]['exit_reason'] == a64[1]['exit_reason'])))
+                entry['row_over_wave_device_time'] = entry['lanes']['16']['device_ms'] / entry['lanes']['64']['device_ms']
+                entry['row_wins'] = bool(RC.row_wins(entry['lanes']['16'], entry['lanes']['64']))
+            rec['measurements'].append(entry)
+            print('%-6s %5d points: %s%s' % (name, n, ', '.join('%s lanes %9.3f ms [%.3f, %.3f] (%.4f us per fit)' % (
+                l, e['device_ms'], e['device_ms_min'], e['device_ms_max'], e['device_us_per_fit']) for l, e in sorted(entry['lanes'].items())),
+                ' -> row form wins' if entry.get('row_wins') else ''), flush=True)
+        ctx.close()
+    if all('row_wins' in m for m in rec['measurements']):
+        rule = RC.implied_rule(rec)
+        rec['auto_rule'] = dict(sixteen_lanes_up_to={str(k): v for k, v in rule.items()},
+                                text='per active-count class (measured at 4 and at 8 active parameters; 1 ... 4 take the first, 5 ... 8 the second): 16 lanes '
+                                     'up to the largest measured length at which the row form beat the wave form by more than the two min-max spreads; '
+                                     '0: nowhere, auto stays at 64 lanes')
+    if a.observed:
+        rec['observed_maxima_against_the_oracle'] = json.load(open(a.observed))
+    with open(a.out, 'w') as fh:
+        json.dump(rec, fh, indent=1, sort_keys=True)
+        fh.write('\n')
+    print('wrote', a.out)
+
+
 def main():
+    global N_POINTS
     ap = argparse.ArgumentParser()
+    ap.add_argument('--points', default=None, help='points per spectrum (default 1000); with --rows a list (default 8,16,32,64,128,256,1000)')
+    ap.add_argument('--lanes', default=None, help='lanes per fit, 64 or 16 (default 64); with --rows a list (default 64,16)')
+    ap.add_argument('--rows', action='store_true', help='the two forms of the batch kernels against each other, into profiles/batch_rows.json')
+    ap.add_argument('--registers', action='store_true', help='with --rows: only the register figures of the four kernels into the record; no GPU is needed')
     ap.add_argument('--sizes', default='1024,16384,131072')
     ap.add_argument('--launches', type=int, default=7)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--one-at-a-time', type=int, default=200)
     ap.add_argument('--rate-fits', type=int, default=16384)
     ap.add_argument('--observed', default=None)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'batch_fits.json'))
+    ap.add_argument('--out', default=None)
     ap.add_argument('--observed-only', action='store_true', help='replace observed_maxima_against_the_oracle of the record at --out by --observed; '
                                                                  'nothing is timed, no GPU is needed')
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, 'profiles', 'batch_rows.json' if a.rows else 'batch_fits.json')
+    if a.rows and a.registers:
+        rec = json.load(open(a.out)) if os.path.exists(a.out) else {}
+        rec['registers'] = registers_record()
+        with open(a.out, 'w') as fh:
+            json.dump(rec, fh, indent=1, sort_keys=True)
+            fh.write('\n')
+        print(json.dumps(rec['registers'], indent=1, sort_keys=True))
+        print('wrote', a.out)
+        return
     sizes = [int(s) for s in a.sizes.split(',')]
     if a.observed and not os.path.exists(a.observed):
         sys.exit('--observed %s: no such file (run tests/test_gpu_batch_shapes.py tests/test_gpu_batch.py in one pytest process under GADFIT_BATCH_OBSERVE first)' % a.observed)
@@ -78,6 +252,12 @@ def main():
         return
     if a.launches < 5:
         sys.exit('at least 5 timed launches')
+    if a.rows:
+        if a.sizes == '1024,16384,131072':
+            a.sizes = '131072'
+        return rows_main(a, [int(v) for v in (a.points or '8,16,32,64,128,256,1000').split(',')], [int(v) for v in (a.lanes or '64,16').split(',')])
+    N_POINTS = int(a.points or 1000)
+    lanes = int(a.lanes or 64)
     tape = trace_model(model, 4)
     x, y, pos = spectra(max(sizes + [a.one_at_a_time, a.rate_fits if a.rate_fits else 0]))
     rec = dict(problem=dict(points=N_POINTS, parameters=4, max_iter=MAX_ITER, lambda0=LAMBDA0, model='gaussian on a background',
@@ -87,6 +267,8 @@ def main():
     kw = dict(lambda_=LAMBDA0, max_iter=MAX_ITER)
     ctx = _lib.Context(0)
     ctx.set_model(tape)
+    ctx.set_batch_lanes(lanes)
+    rec['problem']['lanes_per_fit'] = lanes
     batch_out = {}
     for nf in sizes:
         xs = np.tile(x, nf); ys = np.ascontiguousarray(y[:nf]).ravel(); ws = np.ones(nf * N_POINTS)
