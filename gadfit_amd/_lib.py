@@ -512,11 +512,12 @@ class Context:
 
     def set_batch_lanes(self, lanes):
         """lanes per fit of the batch kernels from here on: 64 a wave per fit (the default), 16 a DPP row per fit and four fits per
-        wave (short spectra), 0 auto (batch_auto_lanes of the active count and the longest spectrum) -- gfh_set_batch_lanes"""
+        wave (short spectra), 256 a workgroup of four waves per fit (few, long spectra), 0 auto (batch_auto_lanes of the active count
+        and the longest spectrum: 16 or 64, never 256) -- gfh_set_batch_lanes"""
         self._chk(lib().gfh_set_batch_lanes(self._h, int(lanes)))
 
     def batch_lanes_used(self):
-        """64 or 16: the form of the last batch launch (0: none yet) -- gfh_debug_batch_lanes"""
+        """64, 16 or 256: the form of the last batch launch (0: none yet) -- gfh_debug_batch_lanes"""
         return int(lib().gfh_debug_batch_lanes(self._h))
 
     def fit_batch(self, pars, active, DTD_min=None, lanes_per_fit=None, **kw):
@@ -688,7 +689,7 @@ class Context:
 
 
 def batch_auto_lanes(n_active, longest):
-    """the auto rule of set_batch_lanes(0): 16 or 64 from the active count and the longest spectrum alone -- gfh_batch_auto_lanes"""
+    """the auto rule of set_batch_lanes(0): 16 or 64 (never 256) from the active count and the longest spectrum alone -- gfh_batch_auto_lanes"""
     return int(lib().gfh_batch_auto_lanes(int(n_active), int(longest)))
 
 

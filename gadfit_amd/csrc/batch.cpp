@@ -2,7 +2,7 @@
 // start parameters, lambda history and exit (gfh_set_batch_data, gfh_fit_batch, gfh_batch_pass, gfh_batch_source, gfh_batch_prepare,
 // gfh_set_batch_lanes).  This file validates, uploads, compiles / loads and launches; the loop itself (gadfit.F90:670-915) is the
 // generated kernel gfh_k_fit_batch (batch_fit.hip; codegen.cpp, emit_batch_kernels), a wave per fit or -- gfh_set_batch_lanes(16) -- a
-// DPP row of 16 lanes per fit and four fits per wave.  One stream, one launch and one device-to-host copy per call.
+// DPP row of 16 lanes per fit and four fits per wave, or -- gfh_set_batch_lanes(256) -- a workgroup of four waves per fit.  One stream, one launch and one device-to-host copy per call.
 // Everything the kernels do not carry is refused here with its own message, before anything touches the device.
 #include "context_internal.h"
 #include <algorithm>
@@ -139,7 +139,7 @@ int gfh_set_batch_data(gfh_ctx* c, int64_t n_fits, const int64_t* offsets, const
 
 // gadf_fit (gadfit.F90:502-1035) for every spectrum of the batch at once: STEP 1+2, the damped solve (potr_f08,
 // gadfit_linalg.F90:36-57), STEP 3 under accth, STEP 4 with its retrials and STEP 5 run on the device, a wave or -- gfh_set_batch_lanes --
-// a row of 16 lanes per fit.
+// a row of 16 lanes or a workgroup of 256 per fit.
 int gfh_fit_batch(gfh_ctx* c, double* pars, int na, const int32_t* active, const gfh_fit_options* o, gfh_batch_result* results,
                   double* seconds) try {
   if (check_context(c, "gfh_fit_batch") || check_model(c, "gfh_fit_batch", na, active)) return 1;
@@ -244,20 +244,22 @@ int gfh_batch_prepare(gfh_ctx* c, int na, const int32_t* active) try {
   return batch_kernels(c, std::vector<int32_t>(active, active + na), batch_lanes(c, na), false, nullptr);
 } catch (const std::exception& e) { return fail(c, std::string("gfh_batch_prepare: ") + e.what()); }
 
-// Lanes per fit of the batch kernels from here on: 64 (the default) a wave per fit, 16 a DPP row per fit and four fits per wave, 0
-// auto -- gfh_batch_auto_lanes at every call.  A setting, not a launch: needs no GPU and no model.
+// Lanes per fit of the batch kernels from here on: 64 (the default) a wave per fit, 16 a DPP row per fit and four fits per wave, 256
+// a workgroup per fit (few, long spectra), 0 auto -- gfh_batch_auto_lanes at every call, which chooses between 16 and 64 only.  A setting, not a launch: needs no GPU and no model.
 int gfh_set_batch_lanes(gfh_ctx* c, int lanes) try {
   if (check_context(c, "gfh_set_batch_lanes")) return 1;
-  if (lanes != 64 && lanes != 16 && lanes != 0)
-    return fail(c, "gfh_set_batch_lanes: " + std::to_string(lanes) + " lanes per fit are not built (64: a wave per fit, 16: a row per fit, 0: auto)");
+  if (lanes != 64 && lanes != 16 && lanes != 256 && lanes != 0)
+    return fail(c, "gfh_set_batch_lanes: " + std::to_string(lanes) + " lanes per fit are not built (64: a wave per fit, 16: a row per fit, 256: a workgroup per fit, 0: auto)");
   c->batch.lanes = lanes;
   return 0;
 } catch (const std::exception& e) { return fail(c, std::string("gfh_set_batch_lanes: ") + e.what()); }
 
-// The form of the last batch launch of this context (64 or 16; 0: none yet), so that a test asserts the dispatch.
+// The form of the last batch launch of this context (64, 16 or 256; 0: none yet), so that a test asserts the dispatch.
 int gfh_debug_batch_lanes(gfh_ctx* c) { return c ? c->batch.last_lanes : 0; }
 
-// The auto rule: a function of the active count and the longest spectrum of the batch, never of the data.
+// The auto rule: a function of the active count and the longest spectrum of the batch, never of the data.  16 or 64: the workgroup
+// form (256) is the caller's choice alone (it wins where the fits are fewer than the card's SIMDs, which the rule does not see;
+// profiles/batch_workgroup.json).
 int gfh_batch_auto_lanes(int n_act, int64_t longest) {
   if (n_act < 1 || n_act > kValuGramMax || longest < 1) return 64;
   return longest <= (n_act <= 4 ? kRowUpTo4 : kRowUpTo8) ? 16 : 64;

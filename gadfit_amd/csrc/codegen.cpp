@@ -18,7 +18,7 @@
 //
 // Only what depends on the tape is generated here: the point functions, the quadrature call sites, the selector and the
 // #defines in front of them.  The kernels themselves are hand-written HIP that no tape changes; they are plain files under
-// device/ (sweep.hip, fused_sweep_gram.hip, chi2.hip, omega.hip, omega_jt.hip, batch_fit.hip, ...), embedded by
+// device/ (sweep.hip, fused_sweep_gram.hip, chi2.hip, omega.hip, omega_jt.hip, batch_fit.hip, batch_wg_sum.hip, ...), embedded by
 // device_text.cpp and streamed into the translation unit by generate_source as they are.  Loading and validating a tape is
 // model.cpp.
 #include "model.h"
@@ -1173,10 +1173,11 @@ static bool emit_batch_kernels(const Model& m, const std::vector<int32_t>& activ
   if (NA < 1 || NA > kValuGramMax) { *err = "batch kernels: 1 to " + std::to_string(kValuGramMax) + " active parameters"; return false; }
   if (m.has_integrals() || m.branching() || m.n_aux > 0) { *err = "batch kernels: models with integrate(), variant tapes or auxiliary columns are not carried"; return false; }
   if (cfg.finite_diff || cfg.loss != 0 || !cfg.omega_jt) { *err = "batch kernels: use_ad = 0, robust losses and GADFIT_HIP_OMEGA_JT=0 are not carried"; return false; }
-  if (cfg.batch_lanes != 64 && cfg.batch_lanes != 16) { *err = "batch kernels: 64 or 16 lanes per fit"; return false; }
+  if (cfg.batch_lanes != 64 && cfg.batch_lanes != 16 && cfg.batch_lanes != 256) { *err = "batch kernels: 64, 16 or 256 lanes per fit"; return false; }
   s << "\n#define GFH_BATCH 1\n#define GFH_BACT {";
   for (int j = 0; j < NA; j++) s << (j ? ", " : "") << active[j];
   s << "}\n#define GFH_BLANES " << cfg.batch_lanes << "\n";
+  if (cfg.batch_lanes == 256) s << kBatchWgSum;          // batch_wg_sum.hip: LDS and a barrier, in the text of the workgroup form alone
   s << kBatchFit;                   // batch_fit.hip: gfh_k_fit_batch, gfh_k_batch_pass, written once against GFH_BLANES
   return true;
 }

@@ -186,7 +186,7 @@ struct gfh_ctx {
     std::vector<int64_t> off;       // [n_fits + 1]
     int64_t min_points = 0;         // of the shortest spectrum
     int64_t max_points = 0;         // of the longest: with the active count, all the auto rule of gfh_set_batch_lanes reads
-    int lanes = 64;                 // gfh_set_batch_lanes: 64 a wave per fit, 16 a DPP row per fit, 0 auto (gfh_batch_auto_lanes)
+    int lanes = 64;                 // gfh_set_batch_lanes: 64 a wave per fit, 16 a DPP row per fit, 256 a workgroup per fit, 0 auto (gfh_batch_auto_lanes: 16 or 64)
     int last_lanes = 0;             // the form of the last batch launch (gfh_debug_batch_lanes); 0: none yet
     bool on_device = false;
     gfh::DevBuf x, y, w, off_d, io, img;

@@ -1,7 +1,7 @@
 
 // ---- Batched independent fits: MANY Levenberg-Marquardt fits of this model in one launch, GFH_BLANES lanes per fit from its first
 // chi2 to its exit (gadfit.F90:670-915 restated per fit; lm.cpp gfh_fit is the host form of the same lines).  256 threads whose fits
-// never talk to each other: no LDS, no barrier, no atomics; fit f = global thread index / GFH_BLANES.  Lane l of a fit takes points
+// never talk to each other: no atomics and, up to 64 lanes per fit, no LDS and no barrier; fit f = global thread index / GFH_BLANES.  Lane l of a fit takes points
 // off[f] + l, + GFH_BLANES, ... of the fit's contiguous x, y, w (coalesced rows, no padding between fits); the lanes past the end of
 // the last row re-read the fit's last point with w = 0.  STEP 1+2 is the per-lane outer product of the fused kernel's VALU form
 // (GFH_NA <= GFH_VALU_GRAM_MAX) finished by gfh_b_sum, which leaves the same bits in every lane of the fit; every lane runs the damped
@@ -12,6 +12,13 @@
 //     keeps 48 lanes on w = 0.  The sums are reduced inside the row alone (gfh_b_sum below) and the state is per-lane, replicated
 //     across the row; nothing crosses a row, so neighbouring fits of a wave do not see each other, and exits at different iterations
 //     or spectra of different lengths inside a wave are ordinary divergence: a row is always wholly live or wholly gone.
+//   GFH_BLANES 256: a workgroup per fit (fit f = blockIdx.x, grid = n_fits) -- for few, long spectra, where a wave per fit walks a
+//     spectrum 64 points at a time on a quarter of the card.  A pass row is 256 points.  Each wave reduces its lanes' accumulators with
+//     gfh_wave_sum as the wave form does; lane 0 of each wave writes the wave's partials to an LDS image [4][n], and after ONE workgroup
+//     barrier every lane adds the four partials of each value in wave order, ((p0 + p1) + p2) + p3 (gfh_b_sum_n, batch_wg_sum.hip).  All four waves
+//     then hold the same bits as wave-uniform values, and each runs the solve and the lambda logic redundantly, as every lane of a wave
+//     does in the other forms.  Up to 64 points waves 1 ... 3 contribute exact +0.0 and the fit returns the wave form's bits.
+//     What keeps the barriers matched is the BARRIER INVARIANT above gfh_k_fit_batch.
 #define GFH_BNP (GFH_NA * (GFH_NA + 1) / 2)
 #define GFH_BNACC (GFH_BNP + GFH_NA + 1)
 #define GFH_BIDX(a, b) ((a) * GFH_NA - (a) * ((a) - 1) / 2 + ((b) - (a)))      // packed upper triangle, a <= b
@@ -49,15 +56,30 @@ static __device__ __forceinline__ double gfh_b_sum(double t) {
   return t;
 }
 #define GFH_BFIT(tid) ((i64)blockIdx.x * 16 + (i64)((tid) >> 4))
+#elif GFH_BLANES == 256
+// gfh_uni and the cross-wave reducer gfh_b_sum_n (LDS, one barrier) are batch_wg_sum.hip, emitted in front of this file in this form
+// alone: the text of the other forms holds no LDS and no barrier
+#define GFH_BFIT(tid) ((i64)blockIdx.x)
 #else
-#error "GFH_BLANES: 64 (a wave per fit) or 16 (a DPP row per fit)"
+#error "GFH_BLANES: 64 (a wave per fit), 16 (a DPP row per fit) or 256 (a workgroup per fit)"
+#endif
+// `img`, the LDS image of the next reduction, travels from the kernel to the three reducers in the workgroup form alone
+#if GFH_BLANES == 256
+static_assert(GFH_BWG_NACC == GFH_BNACC, "batch_wg_sum.hip sizes its LDS images for the sweep's accumulators");
+#define GFH_BIMG_DECL , int& img
+#define GFH_BIMG , lds_img
+#define GFH_BIMG_INIT int lds_img = 0;
+#else
+#define GFH_BIMG_DECL
+#define GFH_BIMG
+#define GFH_BIMG_INIT
 #endif
 // the inputs of pass row i0 (uniform in the fit) for this lane; past the end: the last point with w = 0
 #define GFH_BLOAD(X, Y, W, i0) { const i64 i_ = (i0) + d.lane; const i64 c_ = i_ < d.e ? i_ : d.e - 1; \
   X = d.x[c_]; Y = d.y[c_]; const double w_ = d.w[c_]; W = i_ < d.e ? w_ : 0.0; }
 
 // STEP 1 + 2 (gadfit.F90:675-699) of one fit: S = [J^T J upper triangle, packed | J^T r | sum r^2]
-static __device__ __forceinline__ void gfh_b_sweep(const gfh_bdata& d, const double* __restrict__ P, int* status, double (&S)[GFH_BNACC]) {
+static __device__ __forceinline__ void gfh_b_sweep(const gfh_bdata& d, const double* __restrict__ P, int* status, double (&S)[GFH_BNACC] GFH_BIMG_DECL) {
   double av[GFH_BNACC];
 #pragma unroll
   for (int k = 0; k < GFH_BNACC; k++) av[k] = 0.0;
@@ -81,11 +103,15 @@ static __device__ __forceinline__ void gfh_b_sweep(const gfh_bdata& d, const dou
     av[GFH_BNP + GFH_NA] += R * R;
     Xc = Xn; Yc = Yn; Wc = Wn;
   }
+#if GFH_BLANES == 256
+  gfh_b_sum_n(av, S, img);
+#else
 #pragma unroll
   for (int k = 0; k < GFH_BNACC; k++) S[k] = gfh_b_sum(av[k]);
+#endif
 }
 // chi2() (gadfit.F90:1015-1034): every parameter passive, value only
-static __device__ __forceinline__ double gfh_b_chi2(const gfh_bdata& d, const double* __restrict__ P, int* status) {
+static __device__ __forceinline__ double gfh_b_chi2(const gfh_bdata& d, const double* __restrict__ P, int* status GFH_BIMG_DECL) {
   double acc = 0.0, Xc, Yc, Wc;
   GFH_BLOAD(Xc, Yc, Wc, d.b)
   for (i64 i0 = d.b; i0 < d.e; i0 += GFH_BLANES) {
@@ -95,11 +121,18 @@ static __device__ __forceinline__ double gfh_b_chi2(const gfh_bdata& d, const do
     acc += r * r;
     Xc = Xn; Yc = Yn; Wc = Wn;
   }
+#if GFH_BLANES == 256
+  const double part[1] = {acc};
+  double sum[1];
+  gfh_b_sum_n(part, sum, img);
+  return sum[0];
+#else
   return gfh_b_sum(acc);
+#endif
 }
 // STEP 3 (gadfit.F90:715-735): omega_i = -f''_delta1(x_i) w_i and J^T omega with the Jacobian row recomputed, as gfh_k_omega_jt
 static __device__ __forceinline__ void gfh_b_omega(const gfh_bdata& d, const double* __restrict__ P, const double* __restrict__ DP, int* status,
-                                                   double (&JTo)[GFH_NA]) {
+                                                   double (&JTo)[GFH_NA] GFH_BIMG_DECL) {
   double acc[GFH_NA], Xc, Yc, Wc;
 #pragma unroll
   for (int a = 0; a < GFH_NA; a++) acc[a] = 0.0;
@@ -117,8 +150,12 @@ static __device__ __forceinline__ void gfh_b_omega(const gfh_bdata& d, const dou
     Xc = Xn; Yc = Yn; Wc = Wn;
   }
   (void)Yc;
+#if GFH_BLANES == 256
+  gfh_b_sum_n(acc, JTo, img);
+#else
 #pragma unroll
   for (int a = 0; a < GFH_NA; a++) JTo[a] = gfh_b_sum(acc[a]);
+#endif
 }
 // (J^T J + lambda DTD) out = rhs (gadfit.F90:711-713): potrf_upper_plain and potrs_upper of lm.cpp operation for operation,
 // unrolled, without contraction (the host has none), so that this solve and the host's return the same bits from the same
@@ -175,6 +212,21 @@ static __device__ __forceinline__ double gfh_b_dtd(const double (&a)[GFH_NA], co
 // 7 lambda raised lam_incs + 1 times in a row), and 8: the damped matrix was not positive definite -- that fit ends with the
 // parameters of its last accepted step, its neighbours go on.  uphill is 0 in a batch, so the acceptance test of gadfit.F90:761 is
 // new_chi2 < old_chi2 and old_delta1 (read only by its factor (1 - beta)**uphill) is not kept.
+//
+// BARRIER INVARIANT (GFH_BLANES 256; the other forms have no barrier).  The barriers are those of gfh_b_sum_n: one at the end of
+// gfh_b_chi2, of gfh_b_sweep and of gfh_b_omega, none inside their point loops.  The four waves of the workgroup must make the same
+// sequence of these calls, so every branch or loop that encloses one is decided only by
+//   (K) kernel arguments (o.*, n_fits),
+//   (O) the fit's off[f], off[f + 1] (d.b, d.e; f = blockIdx.x is the workgroup's), or
+//   (S) values that came out of gfh_b_sum_n -- the same LDS words added in the same order in every lane -- or were computed from such
+//       values and (K), (O) by the same instruction sequence under contract(off): S, DTD, JTr, delta1, delta2, lambda, P, old_pars,
+//       the chi2 values and the iteration count.  No per-lane quantity (d.lane, x, y, w, the accumulators before the sum) and nothing
+//       read back from global memory that another wave wrote (status is write-only here) enters them.
+// Line by line: the f >= n_fits return is per workgroup (K); for (;;) is left by gfh_b_solve's ok (S), by STEP 4's quit (S) and by
+// STEP 5's exits (K, O: dof, S); `if (o.use_accth)` is (K); the STEP 4 loop's bound is (K) and its three arms are chosen by new_chi2 <
+// old_chi2 (S) and i <= o.lam_incs (K).  `lds_img` is toggled once per gfh_b_sum_n and nowhere else, so it is the same in the four waves.
+// A NaN or Inf in a spectrum therefore ends the fit with reason 8 at the same solve in all four waves.  The branches on d.lane == 0
+// and on the lane inside gfh_b_sum_n enclose no barrier.  Lane 0 of wave 0 writes the parameters and the record.
 extern "C" __global__ __launch_bounds__(256)
 void gfh_k_fit_batch(const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ w,
                      const i64* __restrict__ off, double* __restrict__ pars, const gfh_batch_opts o,
@@ -193,10 +245,11 @@ void gfh_k_fit_batch(const double* __restrict__ x, const double* __restrict__ y,
   const double dof = dof_ == 0 ? 1.0 : (double)dof_;
   double lambda = o.lambda;
   int iterations = 0, exit_reason = -1, n_sweeps = 0, n_chi2 = 0, n_omega = 0;
-  double old_chi2 = gfh_b_chi2(d, P, status), new_chi2 = 0.0, old_old_chi2 = 0.0;             // gadfit.F90:670
+  GFH_BIMG_INIT
+  double old_chi2 = gfh_b_chi2(d, P, status GFH_BIMG), new_chi2 = 0.0, old_old_chi2 = 0.0;             // gadfit.F90:670
   n_chi2++;
   for (;;) {
-    gfh_b_sweep(d, P, status, S);                                                             // STEP 1 + 2, gadfit.F90:675-701
+    gfh_b_sweep(d, P, status, S GFH_BIMG);                                                     // STEP 1 + 2, gadfit.F90:675-701
     n_sweeps++;
 #pragma unroll
     for (int j = 0; j < GFH_NA; j++) {                                                        // gadfit.F90:702-710
@@ -211,7 +264,7 @@ void gfh_k_fit_batch(const double* __restrict__ x, const double* __restrict__ y,
       for (int k = 0; k < GFH_NP; k++) DP[k] = 0.0;
 #pragma unroll
       for (int j = 0; j < GFH_NA; j++) DP[act[j]] = delta1[j];
-      gfh_b_omega(d, P, DP, status, JTo);
+      gfh_b_omega(d, P, DP, status, JTo GFH_BIMG);
       n_omega++;
       if (!gfh_b_solve(S, DTD, lambda, JTo, delta2)) { exit_reason = 8; break; }              // gadfit.F90:736-738 (the same matrix: the same factor)
       const double acc_ratio = __builtin_sqrt(gfh_b_dtd(delta2, DTD, delta2) / gfh_b_dtd(delta1, DTD, delta1));
@@ -224,7 +277,7 @@ void gfh_k_fit_batch(const double* __restrict__ x, const double* __restrict__ y,
     for (int j = 0; j < GFH_NA; j++) P[act[j]] = P[act[j]] + delta1[j] + 0.5 * delta2[j];    // gadfit.F90:745-750
     bool quit = false;
     for (int i = 1; i <= o.lam_incs + 1; i++) {                                               // STEP 4, gadfit.F90:752-819
-      new_chi2 = gfh_b_chi2(d, P, status);
+      new_chi2 = gfh_b_chi2(d, P, status GFH_BIMG);
       n_chi2++;
       if (new_chi2 < old_chi2) {                                                              // gadfit.F90:761
         lambda = lambda / o.lam_down;                                                         // gadfit.F90:780-782
@@ -282,7 +335,8 @@ void gfh_k_batch_pass(const double* __restrict__ x, const double* __restrict__ y
   double P[GFH_NP], S[GFH_BNACC];
 #pragma unroll
   for (int k = 0; k < GFH_NP; k++) P[k] = gfh_uni(pars[f * GFH_NP + k]);
-  gfh_b_sweep(d, P, status, S);
+  GFH_BIMG_INIT
+  gfh_b_sweep(d, P, status, S GFH_BIMG);      // (256 lanes per fit: one barrier, reached by all four waves -- the return above is per workgroup)
   if (d.lane == 0) {
     double* __restrict__ out = img + f * (GFH_NA * GFH_NA + GFH_NA + 1);
 #pragma unroll

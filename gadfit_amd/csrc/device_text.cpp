@@ -31,6 +31,9 @@ const char kOmega[] = {
 const char kOmegaJt[] = {
 #embed "device/omega_jt.hip"
 , 0};
+const char kBatchWgSum[] = {
+#embed "device/batch_wg_sum.hip"
+, 0};
 const char kBatchFit[] = {
 #embed "device/batch_fit.hip"
 , 0};

@@ -82,7 +82,8 @@ struct GenConfig {
   int waves_per_eu = 0;   // > 0: the plain sweep / chi2 / omega kernels are compiled for at least this many waves per SIMD (register cap)
   bool batch = false;     // two more kernels behind the point functions: gfh_k_fit_batch (a whole LM fit per wave) and gfh_k_batch_pass
                           // (batch.cpp).  A translation unit of its own: the default one does not change by a byte
-  int batch_lanes = 64;   // ... lanes per fit of those two (GFH_BLANES): 64, a wave per fit, or 16, a DPP row per fit and four fits per wave
+  int batch_lanes = 64;   // ... lanes per fit of those two (GFH_BLANES): 64, a wave per fit, 16, a DPP row per fit and four fits per wave,
+                          // or 256, a workgroup per fit
 };
 
 // Where the quadrature workspaces of a translation unit live (numerical_integration.F90:40-51, 128-134: the reference's are heap arrays

@@ -291,7 +291,7 @@ def gadf_fit_batch(xs, ys, ws, pars, lambda_=None, lam_up=None, lam_down=None, a
     used in (y - f) * w; None = ones); ``pars`` [n_fits][n_pars] start values, passive entries included.  The fit arguments are
     gadf_fit's; those a device-resident loop does not carry (uphill, nielsen, umnigh, grad_chi2, cos_phi, rel_error_global) are refused
     by the library, and max_iter is required.  ``lanes_per_fit``: 64 a wave per fit, 16 a row of 16 lanes per fit and four fits per wave
-    (short spectra), 0 auto; None leaves the session's setting (64 unless set before).  Returns (parameters [n_fits][n_pars], record array of per-fit results with the fields
+    (short spectra), 256 a workgroup of four waves per fit (few, long spectra), 0 auto (16 or 64); None leaves the session's setting (64 unless set before).  Returns (parameters [n_fits][n_pars], record array of per-fit results with the fields
     iterations, exit_reason, n_sweeps, n_chi2, n_omega, dof, lambda_, chi2)."""
     _need_init()
     if 'lambda' in kw:

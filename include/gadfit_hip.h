@@ -419,13 +419,17 @@ int  gfh_batch_prepare(gfh_ctx* ctx, int n_act, const int32_t* active_pars);
 /* Lanes per fit of the batch kernels, a setting of the context read by every later gfh_fit_batch, gfh_batch_pass, gfh_batch_source
  * and gfh_batch_prepare.  64 (the default): a wave per fit.  16: a DPP row of 16 lanes per fit, four fits per wave and sixteen per
  * workgroup -- for short spectra, where a wave per fit keeps most lanes on padding; the sums are reduced inside the row, fits of one
- * wave do not see each other, and every check and refusal is the same.  0: auto, gfh_batch_auto_lanes(n_act, longest spectrum of the
- * batch held; 64 where the context holds none).  Any other value is refused.  Both forms of an active set stay loaded side by side.
- * The two forms add a fit's point sums in different orders once a spectrum has more than 16 points; up to 16 they return the same bits. */
+ * wave do not see each other, and every check and refusal is the same.  256: a workgroup of four waves per fit (grid = number of
+ * fits) -- for few, long spectra, where a wave per fit walks each spectrum 64 points at a time and a batch of fewer fits than the card
+ * has SIMDs leaves most of it idle; each wave sums its lanes, the four partial sums meet in LDS and are added in wave order, and every
+ * check and refusal is again the same.  0: auto, gfh_batch_auto_lanes(n_act, longest spectrum of the
+ * batch held; 64 where the context holds none).  Auto never chooses 256.  Any other value is refused.  All forms of an active set stay loaded side by side.
+ * The forms add a fit's point sums in different orders: 16 and 64 return the same bits up to 16 points per spectrum, 64 and 256 up
+ * to 64 points.  Measured against each other in profiles/batch_rows.json and profiles/batch_workgroup.json. */
 int  gfh_set_batch_lanes(gfh_ctx* ctx, int lanes);
 /* The auto rule: 16 or 64 from the active count and the longest spectrum alone, as measured (profiles/batch_rows.json). */
 int  gfh_batch_auto_lanes(int n_act, int64_t longest_spectrum);
-/* 64 or 16: the form of the last batch launch of this context (0: none yet).  For tests that assert the dispatch. */
+/* 64, 16 or 256: the form of the last batch launch of this context (0: none yet).  For tests that assert the dispatch. */
 int  gfh_debug_batch_lanes(gfh_ctx* ctx);
 
 /* ---- Jacobian_indices / dim (gadfit.F90:615-631) as a helper for callers */

@@ -5,6 +5,8 @@ profiles/r05_small_fits.txt: 1000 points, a Gaussian on a background, 4 paramete
                                 [--points 1000] [--lanes 64] [--observed FILE [--observed-only]] [--out profiles/batch_fits.json]
     python tools/bench_batch.py --rows [--points 8,16,32,64,128,256,1000] [--lanes 64,16] [--sizes 131072] [--registers]
                                 [--observed FILE [--observed-only]] [--out profiles/batch_rows.json]
+    python tools/bench_batch.py --workgroup [--points 1000,4096,16384,65536] [--sizes 64,256,1024,16384] [--models gauss4,exp4]
+                                [--registers] [--observed FILE [--observed-only]] [--out profiles/batch_workgroup.json]
 
 Per batch size: warm-up launches, then the median of the timed launches -- device time from the HIP events around the kernel
 (gfh_fit_batch's `seconds`) and wall time around the whole call (parameters down, launch, results back).  Two yardsticks, neither of
@@ -25,7 +27,12 @@ Per model (this file's 4-parameter Gaussian; exp4, four exponentials with all 8 
 form is the wave form on the same card in the same run, never the row form's own time: `row_wins` is tests/batch_row_cases.row_wins
 (the medians differ by more than the sum of the two forms' min-max spreads), and `auto_rule` is the largest measured length with
 row_wins per active-count class.  --registers: the compiler's register, scratch and occupancy figures of the four kernels
-(hipcc -Rpass-analysis=kernel-resource-usage on the generated source; needs hipcc, no GPU)."""
+(hipcc -Rpass-analysis=kernel-resource-usage on the generated source; needs hipcc, no GPU).
+--workgroup: the 256-lane form (a workgroup of four waves per fit) against the 64-lane form by the recipe of --rows, over points per
+spectrum AND fits per launch, since what the workgroup form buys is occupancy when the fits are fewer than the card's SIMDs: per
+(model, fits, points) both forms alternating launch by launch on one context; cells above 2^30 points in total are dropped.  The
+yardstick of the 256-lane form is the 64-lane form of the same run; `workgroup_wins` is tests/batch_row_cases.row_wins.  With
+--registers: the compiler's figures (LDS included) of the 256-lane kernels of the three units of the --rows table."""
 import argparse
 import json
 import os
@@ -55,12 +62,21 @@ def spectra(n_fits, n_points=None):
     n_points = n_points or N_POINTS
     x = 10.0 * (np.arange(n_points) + 0.5) / n_points
     k = np.arange(1, n_fits + 1, dtype=np.float64)
-    pos = 4.0 + np.mod(k * 0.6180339887498949, 1.0)
+    pos = _gauss_pos(k)
     y = np.empty((n_fits, n_points))
     for lo in range(0, n_fits, 8192):
         hi = min(n_fits, lo + 8192)
-        y[lo:hi] = 3.0 * np.exp(-((x[None, :] - pos[lo:hi, None]) / 0.8) ** 2) + 0.5 + 1.0e-3 * np.sin(977.0 * x[None, :] + k[lo:hi, None])
+        y[lo:hi] = _gauss_rows(x, k[lo:hi])
     return x, y, pos
+
+
+def _gauss_pos(k):
+    return 4.0 + np.mod(k * 0.6180339887498949, 1.0)
+
+
+def _gauss_rows(x, k):
+    """spectra k (numbered from 1, as float64) of spectra() on the abscissae x"""
+    return 3.0 * np.exp(-((x[None, :] - _gauss_pos(k)[:, None]) / 0.8) ** 2) + 0.5 + 1.0e-3 * np.sin(977.0 * x[None, :] + k[:, None])
 
 
 def model_exp4(p, x):
@@ -80,11 +96,37 @@ def spectra_exp4(n_fits, n_points):
     y = np.empty((n_fits, n_points))
     for lo in range(0, n_fits, 8192):
         hi = min(n_fits, lo + 8192)
-        amp = 0.9 + 0.2 * np.mod(k[lo:hi, None] * 0.6180339887498949 + 0.25 * np.arange(4)[None, :], 1.0)
-        y[lo:hi] = 1.0e-3 * np.sin(977.0 * x[None, :] + k[lo:hi, None])
-        for j in range(4):
-            y[lo:hi] += (EXP4_TRUTH[2 * j] * amp[:, j:j + 1]) * np.exp(-x[None, :] / EXP4_TRUTH[2 * j + 1])
+        y[lo:hi] = _exp4_rows(x, k[lo:hi])
     return x, y
+
+
+def _exp4_rows(x, k):
+    """spectra k (numbered from 1, as float64) of spectra_exp4() on the abscissae x"""
+    amp = 0.9 + 0.2 * np.mod(k[:, None] * 0.6180339887498949 + 0.25 * np.arange(4)[None, :], 1.0)
+    y = 1.0e-3 * np.sin(977.0 * x[None, :] + k[:, None])
+    for j in range(4):
+        y += (EXP4_TRUTH[2 * j] * amp[:, j:j + 1]) * np.exp(-x[None, :] / EXP4_TRUTH[2 * j + 1])
+    return y
+
+
+def spectra_flat(name, n_fits, n_points):
+    """(x, y, w) back to back as set_batch_data takes them: the spectra of spectra() ('gauss4') or spectra_exp4() ('exp4'), computed
+    in blocks of at most 2^22 points on up to 16 threads, so that a batch of 2^30 points costs no temporaries of its own size"""
+    from concurrent.futures import ThreadPoolExecutor
+    if name == 'gauss4':
+        x, rows = 10.0 * (np.arange(n_points) + 0.5) / n_points, _gauss_rows
+    else:
+        x, rows = 0.05 + 99.95 * (np.arange(n_points) + 0.5) / n_points, _exp4_rows
+    y = np.empty((n_fits, n_points)); xs = np.empty((n_fits, n_points))
+    step = max(1, (1 << 22) // n_points)
+
+    def block(lo):
+        hi = min(n_fits, lo + step)
+        y[lo:hi] = rows(x, np.arange(lo + 1, hi + 1, dtype=np.float64))
+        xs[lo:hi] = x[None, :]
+    with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
+        list(pool.map(block, range(0, n_fits, step)))
+    return xs.reshape(-1), y.reshape(-1), np.ones(n_fits * n_points)
 
 
 ROW_MODELS = {
@@ -95,7 +137,7 @@ ROW_MODELS = {
 
 
 def kernel_registers(src):
-    """{kernel: {vgprs, agprs, sgprs, scratch_bytes_per_lane, waves_per_simd}} of the two batch kernels of a generated source"""
+    """{kernel: {vgprs, agprs, sgprs, scratch_bytes_per_lane, waves_per_simd, lds_bytes_per_block}} of the two batch kernels of a generated source"""
     import re
     import subprocess
     import tempfile
@@ -108,7 +150,7 @@ def kernel_registers(src):
                             '-Rpass-analysis=kernel-resource-usage'], capture_output=True, text=True, check=True)
     out, name = {}, None
     keys = {'VGPRs': 'vgprs', 'AGPRs': 'agprs', 'TotalSGPRs': 'sgprs', 'ScratchSize [bytes/lane]': 'scratch_bytes_per_lane',
-            'Occupancy [waves/SIMD]': 'waves_per_simd'}
+            'Occupancy [waves/SIMD]': 'waves_per_simd', 'LDS Size [bytes/block]': 'lds_bytes_per_block'}
     for line in r.stderr.splitlines():
         m = re.search(r'remark:\s+(.*?): (\S+) \[-Rpass', line)
         if not m:
@@ -122,13 +164,13 @@ def kernel_registers(src):
     return out
 
 
-def registers_record():
+def registers_record(forms=(64, 16)):
     rec = {}
     c = _lib.Context(-1)
     exp2 = dict(model=lambda p, x: p[0] * exp(-(x / p[1])) + p[2] * exp(-(x / p[3])), n_pars=4, active=ACTIVE)      # (tests/models.py: model_exp2)
     for name, m in list(ROW_MODELS.items()) + [('exp2', exp2)]:
         c.set_model(trace_model(m['model'], m['n_pars']))
-        for lanes in (64, 16):
+        for lanes in forms:
             c.set_batch_lanes(lanes)
             rec['%s_lanes%d' % (name, lanes)] = kernel_registers(c.batch_source(m['active']))
     c.close()
@@ -209,13 +251,89 @@ def rows_main(a, points, lanes_list):
     print('wrote', a.out)
 
 
+def workgroup_main(a, points, sizes, models):
+    """the 256-lane form against the 64-lane form over points per spectrum and fits per launch (see the module's text)"""
+    from tests import batch_row_cases as RC
+    lanes_list = [64, 256]
+    rec = dict(method='per (model, fits per launch, points per spectrum, form) the median and the min-max of %d launches after %d warm-up launches; device = HIP '
+                      'events around the kernel, wall = around the call; lambda0 = %g, max_iter = %d and no other exit, so both forms run the same passes up to the '
+                      'accept / reject decisions that rounding takes past convergence (the totals are in each record); the forms alternate launch by launch on one '
+                      'context, one card, one run; cells above 2^30 points in total are dropped; no counter pass was made' % (a.launches, a.warmup, LAMBDA0, MAX_ITER),
+               measurements=[])
+    if os.path.exists(a.out):          # (--registers and --observed of earlier calls stay, and the models this call does not measure)
+        old = json.load(open(a.out))
+        for k in ('registers', 'observed_maxima_against_the_oracle'):
+            if k in old:
+                rec[k] = old[k]
+        rec['measurements'] = [m for m in old.get('measurements', []) if m['model'] not in models]
+    kw = dict(lambda_=LAMBDA0, max_iter=MAX_ITER)
+    for name in models:
+        m = ROW_MODELS[name]
+        ctx = _lib.Context(0)
+        ctx.set_model(trace_model(m['model'], m['n_pars']))
+        for nf in sizes:
+            for n in points:
+                if nf * n > 2 ** 30:
+                    continue
+                t0 = time.perf_counter()
+                x, y, w = spectra_flat(name, nf, n)
+                ctx.set_batch_data(np.arange(nf + 1, dtype=np.int64) * n, x, y, w)
+                del x, y, w
+                print('%-6s %5d fits x %5d points: data in %.1f s' % (name, nf, n, time.perf_counter() - t0), flush=True)
+                start = np.tile(m['start'], (nf, 1))
+                entry = dict(model=name, what=m['what'], n_active=len(m['active']), fits=nf, points=n, lanes={})
+                times = {l: ([], []) for l in lanes_list}
+                out = {}
+                for it in range(a.warmup + a.launches):
+                    for l in lanes_list:          # the forms alternate launch by launch: a drift of the card's clock meets both alike
+                        t0 = time.perf_counter()
+                        p, r, sec = ctx.fit_batch(start, m['active'], lanes_per_fit=l, **kw)
+                        t1 = time.perf_counter()
+                        if ctx.batch_lanes_used() != l:
+                            sys.exit('the launch did not take the form asked for')
+                        if it >= a.warmup:
+                            times[l][0].append(sec); times[l][1].append(t1 - t0)
+                        out[l] = (p, r)
+                for l in lanes_list:
+                    dev, wall = times[l]
+                    p, r = out[l]
+                    d = statistics.median(dev); wl = statistics.median(wall)
+                    entry['lanes'][str(l)] = dict(
+                        device_ms=1e3 * d, device_ms_min=1e3 * min(dev), device_ms_max=1e3 * max(dev), wall_ms=1e3 * wl, wall_ms_min=1e3 * min(wall),
+                        wall_ms_max=1e3 * max(wall), device_us_per_fit=1e6 * d / nf, wall_us_per_fit=1e6 * wl / nf,
+                        passes=dict(sweeps=int(r['n_sweeps'].sum()), chi2=int(r['n_chi2'].sum()), omega=int(r['n_omega'].sum())),
+                        exit_reasons={str(int(v)): int(np.sum(r['exit_reason'] == v)) for v in sorted(set(r['exit_reason'].tolist()))},
+                        finite=bool(np.all(np.isfinite(p))))
+                a256, a64 = out[256], out[64]
+                entry['fits_with_equal_counts_in_both_forms'] = int(np.sum((a256[1]['n_sweeps'] == a64[1]['n_sweeps']) & (a256[1]['n_chi2'] == a64[1]['n_chi2']) &
+                                                                           (a256[1]['exit_reason'] == a64[1]['exit_reason'])))
+                entry['workgroup_over_wave_device_time'] = entry['lanes']['256']['device_ms'] / entry['lanes']['64']['device_ms']
+                entry['workgroup_wins'] = bool(RC.row_wins(entry['lanes']['256'], entry['lanes']['64']))
+                rec['measurements'].append(entry)
+                print('%-6s %5d fits x %5d points: %s%s' % (name, nf, n, ', '.join('%s lanes %9.3f ms [%.3f, %.3f]' % (
+                    l, e['device_ms'], e['device_ms_min'], e['device_ms_max']) for l, e in sorted(entry['lanes'].items(), key=lambda it: int(it[0]))),
+                    ' -> workgroup form wins' if entry['workgroup_wins'] else ''), flush=True)
+                with open(a.out, 'w') as fh:          # (after every cell: a run that is cut short leaves what it measured)
+                    json.dump(rec, fh, indent=1, sort_keys=True)
+                    fh.write('\n')
+        ctx.close()
+    if a.observed:
+        rec['observed_maxima_against_the_oracle'] = json.load(open(a.observed))
+    with open(a.out, 'w') as fh:
+        json.dump(rec, fh, indent=1, sort_keys=True)
+        fh.write('\n')
+    print('wrote', a.out)
+
+
 def main():
     global N_POINTS
     ap = argparse.ArgumentParser()
     ap.add_argument('--points', default=None, help='points per spectrum (default 1000); with --rows a list (default 8,16,32,64,128,256,1000)')
-    ap.add_argument('--lanes', default=None, help='lanes per fit, 64 or 16 (default 64); with --rows a list (default 64,16)')
+    ap.add_argument('--lanes', default=None, help='lanes per fit, 64, 16 or 256 (default 64); with --rows a list (default 64,16)')
     ap.add_argument('--rows', action='store_true', help='the two forms of the batch kernels against each other, into profiles/batch_rows.json')
-    ap.add_argument('--registers', action='store_true', help='with --rows: only the register figures of the four kernels into the record; no GPU is needed')
+    ap.add_argument('--workgroup', action='store_true', help='the 256-lane form of the batch kernels against the 64-lane form, into profiles/batch_workgroup.json')
+    ap.add_argument('--models', default='gauss4,exp4', help='with --workgroup: the models measured by this call (the record keeps the others)')
+    ap.add_argument('--registers', action='store_true', help='with --rows or --workgroup: only the register figures of the four kernels into the record; no GPU is needed')
     ap.add_argument('--sizes', default='1024,16384,131072')
     ap.add_argument('--launches', type=int, default=7)
     ap.add_argument('--warmup', type=int, default=2)
@@ -227,10 +345,10 @@ def main():
                                                                  'nothing is timed, no GPU is needed')
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'batch_rows.json' if a.rows else 'batch_fits.json')
-    if a.rows and a.registers:
+        a.out = os.path.join(ROOT, 'profiles', 'batch_workgroup.json' if a.workgroup else 'batch_rows.json' if a.rows else 'batch_fits.json')
+    if (a.rows or a.workgroup) and a.registers:
         rec = json.load(open(a.out)) if os.path.exists(a.out) else {}
-        rec['registers'] = registers_record()
+        rec['registers'] = registers_record((256,) if a.workgroup else (64, 16))
         with open(a.out, 'w') as fh:
             json.dump(rec, fh, indent=1, sort_keys=True)
             fh.write('\n')
@@ -252,6 +370,10 @@ def main():
         return
     if a.launches < 5:
         sys.exit('at least 5 timed launches')
+    if a.workgroup:
+        if a.sizes == '1024,16384,131072':
+            a.sizes = '64,256,1024,16384'
+        return workgroup_main(a, [int(v) for v in (a.points or '1000,4096,16384,65536').split(',')], [int(v) for v in a.sizes.split(',')], a.models.split(','))
     if a.rows:
         if a.sizes == '1024,16384,131072':
             a.sizes = '131072'
