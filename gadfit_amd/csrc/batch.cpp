@@ -5,6 +5,7 @@
 // DPP row of 16 lanes per fit and four fits per wave, or -- gfh_set_batch_lanes(256) -- a workgroup of four waves per fit.  One stream, one launch and one device-to-host copy per call.
 // Everything the kernels do not carry is refused here with its own message, before anything touches the device.
 #include "context_internal.h"
+#include "lm_options.h"
 #include <algorithm>
 #include <cstring>
 #include <exception>
@@ -153,19 +154,18 @@ int gfh_fit_batch(gfh_ctx* c, double* pars, int na, const int32_t* active, const
   if (o->has_grad_chi2) return fail(c, "gfh_fit_batch: the grad_chi2 test is not carried by the batch kernel");
   if (o->has_cos_phi) return fail(c, "gfh_fit_batch: the cos_phi test is not carried by the batch kernel");
   if (o->has_rel_error_global) return fail(c, "gfh_fit_batch: rel_error_global has no meaning for independent fits");
-  if (o->has_lam_incs && o->lam_incs < 1) return fail(c, "Input parameter lam_incs must be at least 1.");      // gadfit.F90:575-578
+  LmOptions lo;
+  if (const char* refusal = resolve_lm_options(*o, &lo)) return fail(c, refusal);                        // gadfit.F90:575-578
   if (!o->has_max_iter || o->max_iter < 0) return fail(c, "gfh_fit_batch: max_iter is required (a loop that runs on the device must be bounded)");
   if (check_geometry(c, "gfh_fit_batch", na)) return 1;
   BatchOpts bo; memset(&bo, 0, sizeof bo);
-  bo.lambda = o->has_lambda ? o->lambda : 1.0;                                                          // gadfit.F90:568-584
-  bo.lam_up = o->has_lam_up ? o->lam_up : 10.0; bo.lam_down = o->has_lam_down ? o->lam_down : 10.0;
-  bo.lam_incs = o->has_lam_incs ? o->lam_incs : 2;
-  bo.use_accth = o->has_accth && o->accth > 1.17549435e-38; bo.accth = o->accth;
+  bo.lambda = lo.lambda; bo.lam_up = lo.lam_up; bo.lam_down = lo.lam_down; bo.lam_incs = lo.lam_incs;      // gadfit.F90:568-584 (lm_options.h)
+  bo.use_accth = lo.use_accth; bo.accth = o->accth;
   bo.has_chi2_abs = o->has_chi2_abs != 0; bo.chi2_abs = o->chi2_abs;
   bo.has_chi2_rel = o->has_chi2_rel != 0; bo.chi2_rel = o->chi2_rel;
   bo.has_rel_error = o->has_rel_error != 0; bo.rel_error = o->rel_error;
   bo.has_max_iter = 1; bo.max_iter = o->max_iter;
-  bo.damp_plain = o->has_damp_max && !o->damp_max;
+  bo.damp_plain = lo.damp_plain;
   if (o->DTD_min) for (int j = 0; j < na; j++) bo.dtd_min[j] = o->DTD_min[j];                            // gadfit.F90:641-646 (the same for every fit)
   NEED_GPU(c);
   if (!c->batch.on_device) return fail(c, "gfh_fit_batch: no batch data on the device (gfh_set_batch_data)");

@@ -1,6 +1,6 @@
 
 // ---- Batched independent fits: MANY Levenberg-Marquardt fits of this model in one launch, GFH_BLANES lanes per fit from its first
-// chi2 to its exit (gadfit.F90:670-915 restated per fit; lm.cpp gfh_fit is the host form of the same lines).  256 threads whose fits
+// chi2 to its exit (gadfit.F90:670-915 restated per fit; lm.cpp gfh_fit is the host form of the same lines, lm_options.h the defaults of both).  256 threads whose fits
 // never talk to each other: no atomics and, up to 64 lanes per fit, no LDS and no barrier; fit f = global thread index / GFH_BLANES.  Lane l of a fit takes points
 // off[f] + l, + GFH_BLANES, ... of the fit's contiguous x, y, w (coalesced rows, no padding between fits); the lanes past the end of
 // the last row re-read the fit's last point with w = 0.  STEP 1+2 is the per-lane outer product of the fused kernel's VALU form
@@ -157,7 +157,7 @@ static __device__ __forceinline__ void gfh_b_omega(const gfh_bdata& d, const dou
   for (int a = 0; a < GFH_NA; a++) JTo[a] = gfh_b_sum(acc[a]);
 #endif
 }
-// (J^T J + lambda DTD) out = rhs (gadfit.F90:711-713): potrf_upper_plain and potrs_upper of lm.cpp operation for operation,
+// (J^T J + lambda DTD) out = rhs (gadfit.F90:711-713): potrf_upper_plain and potrs_upper of normal_eq.cpp operation for operation,
 // unrolled, without contraction (the host has none), so that this solve and the host's return the same bits from the same
 // sums.  false: a pivot that is not positive, or -- the one test the host's '!(ajj > 0.0)' does not make -- not finite: this fit's
 // normal equations are not positive definite.

@@ -193,7 +193,11 @@ def test_finite_differences_over_column_sets_offset_the_aux_pointer_per_evaluati
         ctx.close()
 
 
-@pytest.mark.parametrize('nd,nl,ng', [(64, 4, 3), (2, 2, 1), (5, 3, 0), (3, 0, 4), (40, 6, 5), (1, 8, 0), (7, 1, 2)])
+@pytest.mark.parametrize('nd,nl,ng', [(64, 4, 3), (2, 2, 1), (5, 3, 0), (3, 0, 4), (40, 6, 5), (1, 8, 0), (7, 1, 2),
+                                      # the edges of the blocked factorisation (normal_eq.cpp: plain up to dim 64, blocks of 48): the last plain
+                                      # and the first blocked size, two whole blocks and one row over (an odd block height), three blocks
+                                      # and one row, and dim 97 with the arrow form on
+                                      (1, 0, 64), (1, 0, 65), (1, 0, 96), (1, 0, 97), (1, 0, 145), (2, 48, 1)])
 def test_damped_solve_block_arrow_equals_dense(nd, nl, ng):
     """gfh_solve_damped: the structure-exploiting solve of a global fit's normal equations (local blocks one by
     one, dense Schur complement of the global parameters) against the dense Cholesky and numpy, on matrices
@@ -213,6 +217,8 @@ def test_damped_solve_block_arrow_equals_dense(nd, nl, ng):
     xd = _lib.solve_damped(jac, dim, JTJ, DTD, lam, rhs, False)
     sc = np.max(np.abs(ref))
     assert np.max(np.abs(xa - ref)) <= 1e-12 * sc and np.max(np.abs(xd - ref)) <= 1e-12 * sc
+    # the dense arm is gfh_potr on the damped matrix, bit for bit (both are the one factorisation of normal_eq.cpp)
+    assert np.array_equal(xd, _lib.potr(JTJ + lam * np.diag(DTD), rhs))
     # a matrix that is not positive definite is reported, not solved
     bad = JTJ.copy(); bad[0, 0] = -1.0
     for use in (True, False):
