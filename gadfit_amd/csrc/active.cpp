@@ -132,7 +132,7 @@ static int compute_layout(gfh_ctx* c, int nd, int na, const int32_t* jac, int di
 
 // the buffer of the quadrature meshes (context.h): one record per slot and outermost integrate() call site of the model
 int gfh::ensure_mesh(gfh_ctx* c) {
-  const int sites = (c->has_model && c->disp.mesh_on && c->gen.fast_div && !c->gen.finite_diff) ? mesh_sites(c->model) : 0;
+  const int sites = (c->has_model && c->disp.mesh_on && c->gen.fast_div && unit_takes_mesh_args(c->model, c->gen)) ? mesh_sites(c->model) : 0;
   const int stride = sites * kMeshRecord;
   if (stride != c->disp.mesh_stride) { c->disp.mesh_stride = stride; c->disp.mesh_valid = false; }
   if (stride) {

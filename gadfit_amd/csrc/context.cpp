@@ -52,7 +52,7 @@ int join_pending(gfh_ctx* c) {
 // choose whether the next sweeps write the Jacobian (only the fused kernel can do without it)
 // does STEP 3 (J^T omega) read the Jacobian back from HBM for the current model and options?
 bool omega_needs_jacobian(const gfh_ctx* c, int n_active) {
-  return !(c->gen.omega_jt && !c->gen.finite_diff && c->has_model && !c->model.has_integrals() && c->gen.loss == 0 && n_active <= kOmegaJtMaxActive);
+  return !(c->has_model && unit_carries_omega_jt(c->model, c->gen, n_active));
 }
 
 void set_store_j(gfh_ctx* c, bool on) {

@@ -8,7 +8,8 @@
 #include <vector>
 #include "../../include/gadfit_hip.h"
 #include "kernels.h"
-#include "model.h"
+#include "codegen.h"
+#include "unseen_report.h"
 #include "rtc.h"
 
 namespace gfh {
@@ -18,11 +19,9 @@ constexpr int kPadGranule = 512;    // dataset segments are padded to this many 
 // The status buffer of a context: [0] the kernels' status word (0 ok, 1 quadrature workspace exhausted, 2 not lowered, 3 a data point
 // took a branch of eval() no recorded variant covers), [16] and [24] arrival counters of k_publish / gfh_k_chi2, and from byte 64 the
 // report of unseen branches: an arrival counter, then from byte 128 up to kUnseenCap entries {slot, guard outcomes so far (bit k = guard k
-// taken), their number} -- layout shared with the generated source (codegen.cpp, gfh_report_unseen).
+// taken), their number} -- layout shared with the generated source (unseen_report.h; device/unseen.hip, gfh_report_unseen).
 constexpr size_t kPlacedJacobianBytes = (size_t)256 << 20;   // a Jacobian buffer from this size on is placed (placement.cpp) and its store deferred inside fits
-constexpr int kUnseenCap = 120;
-constexpr size_t kStatusBytes = 128 + (size_t)kUnseenCap * 24;
-struct UnseenEntry { long long slot; unsigned long long path; int n_guards; int pad; };
+constexpr size_t kStatusBytes = 128 + (size_t)kUnseenCap * sizeof(UnseenEntry);
 
 struct Group;                       // group.h: single-process device group
 
@@ -72,7 +71,7 @@ struct gfh_ctx {
   bool jtj_prezeroed = false;       // gfh_fit: the caller's JTJ buffer holds zeros off the pattern already
   gfh::DevBuf owner;                // [dim] the one dataset using a column, or -1 (k_assemble)
   gfh::DevBuf aux; int n_aux = 0;   // auxiliary per-point columns [n_aux][n_slots] (gfh_set_aux)
-  // Mesh hand-over of quadrature models (codegen.cpp, mesh_build): per slot and outermost integrate() call site the record of the
+  // Mesh hand-over of quadrature models (emit_quadrature.cpp, mesh_build): per slot and outermost integrate() call site the record of the
   // bisections the last recording pass made, and the parameter block it made them at.  A pass at exactly those parameters replays
   // them instead of bisecting again: the sweep of an accepted step after the trial chi2() there, STEP 3 after the sweep.  (launch.cpp)
   struct Dispatch {

@@ -13,6 +13,9 @@ const char kPowLn[] = {
 const char kParsBlock[] = {
 #embed "device/pars_block.hip"
 , 0};
+const char kUnseen[] = {
+#embed "device/unseen.hip"
+, 0};
 const char kSweep[] = {
 #embed "device/sweep.hip"
 , 0};

@@ -7,6 +7,7 @@ namespace gfh {
 extern const char kExp[];              // exp.hip: gfh_exp
 extern const char kPowLn[];            // pow_ln.hip: gfh_pow_ln (models with x ** a, GFH_FAST_DIV)
 extern const char kParsBlock[];        // pars_block.hip: the parameter block as kernel argument or device array
+extern const char kUnseen[];           // unseen.hip: struct gfh_unseen, gfh_report_unseen (branching models; behind GFH_UNSEEN_CAP, unseen_report.h)
 extern const char kSweep[];            // sweep.hip: layout, GFH_ROBUST, gfh_store64, gfh_k_sweep, the hand-off macros
 extern const char kWaveSum[];          // wave_sum.hip: gfh_row_down, gfh_wave_sum (kernels.hip includes the same file)
 extern const char kFusedSweepGram[];   // fused_sweep_gram.hip: the fused STEP 1 + STEP 2 kernel in all its forms

@@ -116,7 +116,7 @@ static int wsg_grid(gfh_ctx* c, hipFunction_t f, int threads, int64_t blocks, in
 }
 // (the generated kernels take the mesh / order arguments and the pool's address only where the model has them: codegen.cpp,
 // GFH_MESH_KPARAMS, GFH_ORDER_KPARAMS, GFH_WSG_KPARAMS)
-static bool takes_mesh_args(const gfh_ctx* c) { return !c->gen.finite_diff && mesh_sites(c->model) > 0; }
+static bool takes_mesh_args(const gfh_ctx* c) { return unit_takes_mesh_args(c->model, c->gen); }
 
 int gfh::launch_model_sweep(gfh_ctx* c, int mesh_mode) {
   if (!c->n_tiles) return 0;
@@ -125,7 +125,7 @@ int gfh::launch_model_sweep(gfh_ctx* c, int mesh_mode) {
   void* ax = c->aux.p; long long lda = c->n_slots; void* mesh = c->disp.mesh.p;
   // (mesh ... cost: kernels of models with integrate() only.  The sweep that bisects measures the cost of its tiles when an order
   // of dispatch is wanted: build_orders)
-  const bool ordered = c->disp.order_on && !c->gen.finite_diff && mesh_sites(c->model) > 0;      // (kernels that take the arguments: codegen.cpp, GFH_ORDER_KPARAMS)
+  const bool ordered = c->disp.order_on && takes_mesh_args(c);      // (kernels that take the arguments: codegen.cpp, GFH_ORDER_KPARAMS)
   void* ord = ordered && c->disp.order_ready ? c->disp.tile_order.p : nullptr;
   void* cst = nullptr;
   if (ordered && c->disp.order_ready && ++c->disp.order_age >= 64) c->disp.order_want = true;      // (the profile moves with the parameters: measured again now and then)
@@ -241,7 +241,7 @@ int gfh::launch_model_chi2(gfh_ctx* c, int tail_mode, unsigned long long seq, in
   void* ax = c->aux.p; long long lda = c->n_slots; void* dfg = c->ds_first_gb.p; int nd = c->nd;
   void* out = c->vec.p; void* hout = c->h_pinned; void* hflag = c->h_flag; void* cnt = c->status.as<char>() + 24;
   void* mesh = c->disp.mesh.p;
-  void* ord = c->disp.order_on && c->disp.order_ready && !c->gen.finite_diff && mesh_sites(c->model) > 0 ? c->disp.gb_order.p : nullptr; void* cst = nullptr;
+  void* ord = c->disp.order_on && c->disp.order_ready && takes_mesh_args(c) ? c->disp.gb_order.p : nullptr; void* cst = nullptr;
   const int cw = c->cur->n_active <= kFusedMaxActive ? fused_waves_for(c->cur->n_active) : 8;     // GFH_CW of the generated source
   int grid; if (wsg_grid(c, c->cur->chi2, 64 * cw, c->n_gb, &grid)) return 1;
   void* pool = c->ws.wsg.p;
@@ -258,7 +258,7 @@ int gfh::launch_model_omega(gfh_ctx* c, int mesh_mode) {
   int nt = c->n_tiles; void* stp = c->status.p;
   void* ax = c->aux.p; long long lda = c->n_slots;
   void* mesh = c->disp.mesh.p;
-  void* ord = c->disp.order_on && c->disp.order_ready && !c->gen.finite_diff && mesh_sites(c->model) > 0 ? c->disp.tile_order.p : nullptr; void* cst = nullptr;
+  void* ord = c->disp.order_on && c->disp.order_ready && takes_mesh_args(c) ? c->disp.tile_order.p : nullptr; void* cst = nullptr;
   // (quadrature models: uneven cost per point -- one tile per workgroup, dealt out as workgroups retire)
   if (!c->cur->omega_grid) c->cur->omega_grid = c->model.has_integrals() ? (1 << 30) : resident_grid(c, c->cur->omega, c->gen.block);
   int grid; if (wsg_grid(c, c->cur->omega, c->gen.block, std::min(c->n_tiles, c->cur->omega_grid), &grid)) return 1;

@@ -1,6 +1,6 @@
 // model.cpp -- the host-side copy of a gfh_tape: validation of what a front end hands over, the pooling of further recorded
 // paths of the same eval() (variants, and further recordings of an integrand) and their bookkeeping.  No code generation here:
-// codegen.cpp lowers a loaded Model to HIP source.
+// codegen.cpp and the emit_*.cpp files lower a loaded Model to HIP source.
 #include "model.h"
 #include "../../include/gadfit_gk_tables.h"
 #include <cstring>
@@ -237,23 +237,26 @@ std::vector<int> Model::tapes_of_variant(int v) const {
   return out;
 }
 
+GkRule gk_rule(int points) {
+  switch (points) {
+    case 15: return {gk15_roots, gk15_wg, gk15_wk, 15};
+    case 21: return {gk21_roots, gk21_wg, gk21_wk, 21};
+    case 31: return {gk31_roots, gk31_wg, gk31_wk, 31};
+    case 41: return {gk41_roots, gk41_wg, gk41_wk, 41};
+    case 51: return {gk51_roots, gk51_wg, gk51_wk, 51};
+    case 61: return {gk61_roots, gk61_wg, gk61_wk, 61};
+  }
+  return {nullptr, nullptr, nullptr, 0};
+}
+
 }  // namespace gfh
 
 // The Gauss-Kronrod rule the kernels are generated with, for the Fortran layer's host-side integrate() (gadf_print and calls of
 // eval() outside gadf_fit: numerical_integration.F90, host_integral): reference node order, even 1-based positions = Gauss nodes.
 extern "C" __attribute__((visibility("default"))) int gfh_gk_rule(int points, double* roots, double* wg, double* wk) {
-  const double *r = nullptr, *g = nullptr, *k = nullptr;
-  if (!roots || !wg || !wk) return 1;
-  switch (points) {
-    case 15: r = gk15_roots; g = gk15_wg; k = gk15_wk; break;
-    case 21: r = gk21_roots; g = gk21_wg; k = gk21_wk; break;
-    case 31: r = gk31_roots; g = gk31_wg; k = gk31_wk; break;
-    case 41: r = gk41_roots; g = gk41_wg; k = gk41_wk; break;
-    case 51: r = gk51_roots; g = gk51_wg; k = gk51_wk; break;
-    case 61: r = gk61_roots; g = gk61_wg; k = gk61_wk; break;
-    default: return 1;
-  }
-  for (int i = 0; i < points; i++) { roots[i] = r[i]; wk[i] = k[i]; }
-  for (int i = 0; i < points / 2; i++) wg[i] = g[i];
+  const gfh::GkRule rule = gfh::gk_rule(points);
+  if (!roots || !wg || !wk || !rule.n) return 1;
+  for (int i = 0; i < points; i++) { roots[i] = rule.roots[i]; wk[i] = rule.wk[i]; }
+  for (int i = 0; i < points / 2; i++) wg[i] = rule.wg[i];
   return 0;
 }

@@ -1,4 +1,4 @@
-// model.h -- host-side copy of a gfh_tape plus the device code generator interface.
+// model.h -- host-side copy of a gfh_tape: the recordings of a model as the generator and the host read them.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -25,7 +25,7 @@ struct Model {
   std::vector<int32_t> ipar_nodes;
   // alts[I]: further recordings (sub-tape indices) of the integrand of call site I -- an integrand that compares AD variables takes
   // its branch anew at every abscissa of the quadrature (AD:315-395), a recording follows one path through it; the recordings of a
-  // call site that differ only in that path are pooled here and the device picks per evaluation (codegen.cpp, emit_family)
+  // call site that differ only in that path are pooled here and the device picks per evaluation (emit_branching.cpp, emit_family)
   std::vector<std::vector<int32_t>> alts;
   int32_t n_tapes = 1;          // recordings handed over (gfh_set_model_variants): variants of eval() + further recordings of integrands
   int32_t gk_points = 15;
@@ -35,7 +35,7 @@ struct Model {
   // Round 5: one such column PER SET OF OUTCOMES.  hint_cols[t] (per tape; empty: hint_aux for all): the column that holds, per data
   // point, the tape the point follows when the comparisons of AD variables on tape t's own path come out as on tape t -- a function of
   // the abscissa alone (the comparisons are given, only plain-real control flow is left), so it is tabulated once and a point that
-  // changes sides at a comparison finds its leaf behind a fork without the host (gfh_set_variant_hint_columns, codegen.cpp emit_selector).
+  // changes sides at a comparison finds its leaf behind a fork without the host (gfh_set_variant_hint_columns, emit_branching.cpp emit_selector).
   std::vector<int32_t> hint_cols;
   std::vector<int32_t> tape_variant;      // tape t of the hand-over -> the variant of eval() it became (pooled integrand recordings join an earlier one)
   int32_t ws_size = 1000, ws_size_inner = 1000;   // quadrature workspaces the user asked for (NI:40, 128-134)
@@ -59,111 +59,10 @@ inline bool is_guard_op(int op) { return op == GFH_GUARD_GT || op == GFH_GUARD_L
 // same operation (guards: whatever their recorded outcome)
 bool same_node(const Node& a, const Node& b);
 
-// Options of the generated kernels (kept in the source text so the cache key sees them).
-struct GenConfig {
-  int block = 256;        // threads per workgroup of the plain sweep / chi2 / omega kernels = slots per tile
-  bool fd_col_sets = false; // ... with the auxiliary columns in 1 + n_active sets (gfh_set_fd_column_sets): evaluation j of the forward differences reads set 1 + j
-  bool finite_diff = false; // use_ad = .false.: gradient / second directional derivative by the reference's finite differences (fitfunction.F90:155-203)
-  bool omega_jt = true;   // STEP 3 kernel that recomputes the Jacobian row instead of reading J (gfh_k_omega_jt)
-  int kernarg_pars = 0;   // > 0: the parameter block (this many doubles) is a by-value kernel argument
-  int ws_size = 100;      // per-lane quadrature workspace (intervals) per nesting level that is compiled in: the fast form carries 100; a
-                          // pass that exhausts it is repeated with the user's size (Model::ws_size, reference default 1000) before the reference's error is raised
-  int ws_size_inner = 100;
-  bool ws_global = false; // the interval workspaces live in a pool in GLOBAL memory, [wave slot][level][interval][lo|hi|err|sum][64 lanes] (a
-                          // wave's access to one field of one interval is one coalesced 512 B row), handed to the kernels as an argument, instead
-                          // of per-lane scratch: every workspace too large for kScratchBudget bytes of scratch per lane (plan_workspaces)
-  bool store_j = true;    // fused kernel writes the Jacobian to HBM (gfh_set_keep_jacobian).  Without the store a wave runs its AD phase at
-                          // s_setprio 3 and its matrix phase at 0 (GFH_AD_PRIO).  The two waves of a SIMD share one FP64 pipe; the wave in its AD phase issues short
-                          // instructions between the other wave's 64- and 17-cycle matrix instructions when it goes first: 0.327 -> 0.314 ms at the headline
-                          // size (profiles/r04_nostore.md); the stored form (waves of a workgroup in phase, store-bound) does not move and is left alone
-  bool store_res = true;  // chi2 kernel writes the residual vector (the reference's chi2() side effect, gadfit.F90:1024-1026)
-  int loss = 0;           // robust cost (gfh_set_loss): 0 linear, 1 cauchy, 2 huber
-  bool fast_div = true;   // share one reciprocal per denominator (<= 1 ulp from the reference's r/v)
-  int waves_per_eu = 0;   // > 0: the plain sweep / chi2 / omega kernels are compiled for at least this many waves per SIMD (register cap)
-  bool batch = false;     // two more kernels behind the point functions: gfh_k_fit_batch (a whole LM fit per wave) and gfh_k_batch_pass
-                          // (batch.cpp).  A translation unit of its own: the default one does not change by a byte
-  int batch_lanes = 64;   // ... lanes per fit of those two (GFH_BLANES): 64, a wave per fit, 16, a DPP row per fit and four fits per wave,
-                          // or 256, a workgroup per fit
-};
+// The Gauss-Kronrod rule of a point count (Model::gk_points; include/gadfit_gk_tables.h): n roots and Kronrod weights in the
+// reference's node order, n / 2 Gauss weights.  n = 0: no such rule.
+struct GkRule { const double *roots, *wg, *wk; int n; };
+GkRule gk_rule(int points);
 
-// Where the quadrature workspaces of a translation unit live (numerical_integration.F90:40-51, 128-134: the reference's are heap arrays
-// of the user's size).  Up to kScratchBudget bytes per lane they are private scratch (the fast form: the user's sizes capped at `fast`
-// intervals and at what the budget holds once the per-interval gradients the bisection carries are counted); anything larger is the
-// global pool (GenConfig::ws_global), which the context allocates with hipMalloc and frees with itself -- private scratch of tens of
-// KB per lane is reserved by the runtime for the whole device until the process ends, and two queues asking for it at once can end
-// the process (HSA_STATUS_ERROR_OUT_OF_RESOURCES).  grown: a pass has exhausted the fast form, carry the user's sizes.
-constexpr int kScratchBudget = 7936;      // 8 KB per lane less 256 B for the register spills of the bodies
-struct WsPlan { int ws_size, ws_size_inner; bool global; };
-WsPlan plan_workspaces(const Model& m, int fast, bool grown);
-bool carries_gradients(int n_ipars, int ws, bool global);      // does the bisection of a call site keep its panels' gradients per interval?
-// The global pool's row of one interval at nesting level 1 or 2: [lo|hi|err|sum] and, where the level's call sites carry their panels'
-// gradients (round 5: the pool form as well -- up to kWsgCarryMax integrand parameters), one more field per parameter; x 64 lanes.
-constexpr int kWsgCarryMax = 8;
-int wsg_row_fields(const Model& m, int level);
-inline long wsg_wave_doubles(const Model& m, int ws1, int ws2) {
-  bool nested = false; for (const Integral& in : m.integrals) if (in.depth >= 2) nested = true;
-  return 64L * wsg_row_fields(m, 1) * ws1 + (nested ? 64L * wsg_row_fields(m, 2) * ws2 : 0L);
-}
-inline bool nested_integrals(const Model& m) { for (const Integral& in : m.integrals) if (in.depth >= 2) return true; return false; }
-
-// Mesh hand-over between passes at the same parameters (codegen.cpp, emit_integral_site): per data point and outermost
-// integrate() call site one record of kMeshRecord bytes -- [0] the number of bisections (255: not recorded), [1..] which interval
-// each bisection split.  mesh_sites: records per point the model's kernels use (0: none).
-constexpr int kMeshRecord = 64, kMeshSitesMax = 4;
-int mesh_sites(const Model& m);
-
-// Up to this many active parameters the fused kernel forms J^T J / J^T r in per-lane VALU accumulators
-// (n (n + 1) / 2 + n + 1 of them) instead of on the matrix cores (fused_sweep_gram.hip, GFH_K_SWEEP_GRAM).  Measured at N = 1e7: 8 parameters
-// 0.166 ms against 0.179 ms with one matrix tile; 12 parameters 0.258 ms (252 VGPRs) against 0.188 ms: the boundary stays at 8.
-constexpr int kValuGramMax = 8;
-// ... and how many passes ahead that form loads its inputs: ONE.  Two (three rotating register sets) were built
-// and measured in round 6 on the theory that two waves per SIMD leave too few bytes in flight: in-process A/B over six fresh contexts
-// each, configs 2 and 3 -- 0.1496 / 0.0925 ms against 0.1498 / 0.0896 (profiles/r06_valu_form_ab.txt): nothing at 8 parameters, a
-// loss at 7 (126 -> 136 VGPRs costs the fourth wave per SIMD).  What the short kernels had been losing was their epilogue.
-
-// The fused STEP 1 + STEP 2 kernel exists for up to this many active parameters (8 tiles of 16); beyond it gfh_k_sweep writes J and
-// k_gram_block forms the Gram image from it.  Up to 4 tiles every wave keeps all tile pairs of its own points; round 5 took 5 tiles
-// that way on a half stage (21 accumulator tiles at 6 spilled 150-200 registers and lost to the two-kernel path: profiles/r05_fused_tiles.md);
-// round 6: from 6 tiles on (81 ... 128 parameters) the waves of a workgroup share the tile pairs out and read each other's stages
-// (GFH_COOP, codegen.cpp).
-// gfh_k_omega_jt (STEP 3 without the stored Jacobian) stops at kOmegaJtMaxActive.
-constexpr int kFusedMaxActive = 128, kFusedMaxActiveNoCoop = 80, kOmegaJtMaxActive = 64;
-// Does the fused kernel's matrix path stage 32 points per wave (two half-passes) instead of 64?  Measured at 32 parameters
-// (profiles/r05_halfstage.md): the half-passes themselves cost 18 % at equal occupancy (twice the stage-write instructions, a
-// bubble at the half boundary) and the gradient that waits in registers keeps three waves per SIMD out of reach (55 spills at 168
-// registers), so up to 4 tiles the full stage stays.  With 5 and 6 tiles four full stages do not fit the 160 KB of a CU: there
-// the half stage is what makes the fused kernel possible at all (against a Jacobian written and read back: 4.6 x the traffic).
-// (5 tiles stay with round 5's per-wave form: 0.76 against 0.89 ms at p = 80, N = 4e6 -- there the 15 accumulator tiles still fit and
-// its diagonal tiles run as 4x4x4 blocks: profiles/r06_coop.md)
-inline bool fused_coop(int n_active) { return n_active > kFusedMaxActiveNoCoop; }
-inline bool fused_half_stage(int n_active) { return n_active > 64; }
-// 5 tiles: ONE cross-wave reduction image per workgroup that the waves add into in order (the same order of additions as one
-// image per wave, a quarter of the LDS), laid over the stages once they are dead.
-inline bool fused_single_image(int n_active) { return !fused_coop(n_active) && n_active > 64; }
-inline int fused_stage_stride(int n_active) { return fused_half_stage(n_active) ? 34 : 66; }
-// LDS of one workgroup of the fused kernel's matrix path with fw waves (the generated source declares exactly this: GFH_LDS_DOUBLES)
-inline long fused_lds_bytes_for(int n_active, int fw) {
-  const long T = (n_active + 15) / 16, npair = T * (T + 1) / 2;
-  const long stage = (16 * T + 1) * fused_stage_stride(n_active);
-  const long img = npair * 256 + 16 * T + 1;                          // the workgroup's own sums, kept for the single-workgroup tail
-  if (fused_coop(n_active)) return std::max(fw * stage, T * 64 + 8 + img) * 8;      // (the epilogue lies over the stages)
-  if (fused_single_image(n_active)) return std::max(fw * stage, npair * 256 + fw * (T * 64 + 4) + img) * 8;
-  const long red = npair * 256 + T * 64 + 4;                          // cross-wave reduction image, one per wave, shares the stages' buffer
-  return fw * std::max(stage, red) * 8 + img * 8 + 64;
-}
-// Waves per workgroup of the fused kernel: 8 (one workgroup per CU at 32 parameters), fewer where 8 stages of
-// [(16T+1) rows][stride] fp64 do not fit the 160 KB LDS.
-inline int fused_waves_for(int n_active) {
-  int fw = fused_coop(n_active) ? 4 : 8;      // (cooperative form: one wave per SIMD -- the gradient alone is 2 NA registers)
-  while (fw > 1 && fused_lds_bytes_for(n_active, fw) > 160L * 1024) fw /= 2;
-  return fw;
-}
-
-// Generates one HIP translation unit with three kernels for (model, active set):
-//   gfh_k_sweep : residual + Jacobian columns (reverse mode, statically unrolled)
-//   gfh_k_chi2  : residual only, all parameters passive, per-block sum of squares
-//   gfh_k_omega : second directional derivative (forward mode val/d/dd)
-bool generate_source(const Model& m, const std::vector<int32_t>& active, const GenConfig& cfg,
-                     std::string* src, std::string* err);
 
 }  // namespace gfh

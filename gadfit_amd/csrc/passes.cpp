@@ -34,7 +34,7 @@ int gfh::status_check(gfh_ctx* c, int st) {
   return fail(c, "device kernel reported status " + std::to_string(st));
 }
 
-// A point has left the recorded decision tree of a branching eval() (status 3; codegen.cpp, gfh_select): read the report, hand
+// A point has left the recorded decision tree of a branching eval() (status 3; emit_branching.cpp, gfh_select): read the report, hand
 // the points to the handler -- which records eval() there and extends the model -- and let the caller repeat the pass.  In a
 // multi-rank run every rank comes here (the status word is part of the cross-rank sum); a rank whose own points were all covered
 // has an empty report and simply repeats its pass, so the collectives stay in step.

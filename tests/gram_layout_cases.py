@@ -7,7 +7,7 @@ below cover what this text claims, and that every translation unit compiles.  Ev
 
 THE DISPATCH RULES are restated here from the sources -- data.cpp: build_layout (padding, gram blocks), passes.cpp: sweep_pass (small,
 tail, pattern-only), launch.cpp (tail_one_workgroup_per_cu, tail mode), active.cpp (get_kernels: the parameter block by value up to
-480 doubles; compute_layout: the pattern) and model.h (fused_waves_for and the LDS of a workgroup) -- and the GPU tests hold
+480 doubles; compute_layout: the pattern) and codegen.h (fused_waves_for and the LDS of a workgroup) -- and the GPU tests hold
 Context.debug_layout() against expect(): a threshold that moves fails there instead of moving a case off the path it is here for.
 
 Part A: one dataset of 1501 points at the first active count of every form and at one below every full tile.
@@ -86,7 +86,7 @@ def gaussK_rows(K, p, x):
 
 # ---- the dispatch rules -----------------------------------------------------------------------------------------------------------
 PAD_GRANULE = PASS_GRANULE = GRAM_TARGET = 512          # context.h: kPadGranule; data.cpp: kPassGranule, kGramTarget
-VALU_GRAM_MAX, FUSED_MAX_NO_COOP, FUSED_MAX = 8, 80, 128      # model.h: kValuGramMax, kFusedMaxActiveNoCoop, kFusedMaxActive
+VALU_GRAM_MAX, FUSED_MAX_NO_COOP, FUSED_MAX = 8, 80, 128      # codegen.h: kValuGramMax, kFusedMaxActiveNoCoop, kFusedMaxActive
 KERNARG_MAX = 480                                      # active.cpp: kMaxKernargPars
 SMALL_MAX = 65536                                      # passes.cpp: dim * dim * nd <= 65536
 LDS_BYTES = 160 * 1024

@@ -110,7 +110,7 @@ def test_models_are_what_the_case_module_says():
 
 
 def test_forms_by_hand():
-    """model.h: the waves per workgroup and the form at every active count of Part A and Part B, and where the forms switch"""
+    """codegen.h: the waves per workgroup and the form at every active count of Part A and Part B, and where the forms switch"""
     waves = {9: 8, 15: 8, 16: 8, 17: 8, 31: 8, 32: 8, 47: 4, 48: 4, 49: 4, 63: 4, 65: 4, 79: 4, 80: 4, 81: 4, 96: 4, 113: 4, 127: 4, 128: 4}
     for na, fw in waves.items():
         assert GL.fused_waves_for(na) == fw, na

@@ -435,7 +435,7 @@ def _kinked(n, rel):
 def test_integrand_that_compares_ad_variables(ctx):
     """a comparison INSIDE the function handed to integrate() (t > q(2): the integrand has a kink at a fitted position): the reference
     takes the branch anew at every abscissa of the quadrature, and so does the device -- the recordings of the integrand's two paths are
-    pooled into one call site and every evaluation picks its own (codegen.cpp emit_family; oracle eval_integrand).  Sweep, chi2, STEP 3,
+    pooled into one call site and every evaluation picks its own (emit_branching.cpp emit_family; oracle eval_integrand).  Sweep, chi2, STEP 3,
     mesh hand-over and a fit that moves the kink, against the oracle"""
     x, y, s, V = _kinked(1201, 1e-10)
     p0 = B.KINKED_TRUTH * np.array([1.05, 0.93, 1.06, 0.8])

@@ -259,7 +259,7 @@ def test_large_workspaces_from_several_contexts_of_one_card():
     """Kernels compiled at the user's workspace size used to carry 32 KB of private scratch per lane, which the runtime provides per
     hardware queue for a whole device (15.8 GB): two queues asking for it at once ended the process (HSA_STATUS_ERROR_OUT_OF_RESOURCES,
     no HIP error to catch).  The user-sized workspaces now live in a pool in global memory that each context allocates itself
-    (codegen.cpp GFH_WSG, launch.cpp wsg_grid): plain contexts on two host threads and device groups of two and three members
+    (emit_quadrature.cpp GFH_WSG, launch.cpp wsg_grid): plain contexts on two host threads and device groups of two and three members
     sharing the card escalate side by side, each stops with the reference's message, and a fit that NEEDS the large workspace gives
     the same numbers from two threads at once as alone."""
     import threading

@@ -1523,7 +1523,7 @@ def test_unfused_gram_kernels_every_tile_count_vs_oracle(K, monkeypatch):
 @pytest.mark.gpu
 def test_forward_mode_square_at_zero_base(monkeypatch):
     """x**2 in forward mode at x == 0: the reference's formula (AD:1051-1054) is 0/0 there; GADFIT_HIP_FAST_DIV=0 and the oracle
-    reproduce the NaN, the default device form (polynomial identity, codegen.cpp GFH_POWI) returns the derivative's value."""
+    reproduce the NaN, the default device form (polynomial identity, emit_ad.cpp GFH_POWI) returns the derivative's value."""
     t = trace_model(lambda p, x: p[0] * (x - p[1]) ** 2, 2)
     xs = np.array([1.0, 2.0, 3.0]); ys = np.zeros(3); ws = np.ones(3)
     pars = np.array([[1.5, 2.0]])                       # the second point has x - p[1] == 0

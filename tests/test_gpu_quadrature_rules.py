@@ -169,7 +169,7 @@ def test_workspace_size_is_the_users(ws):
 def test_workspace_beyond_any_scratch_lives_in_the_pool_and_goes_with_the_context():
     """ws_size = 5000 (160 KB per lane: beyond any private scratch) is the user's to ask for (NI:128-134: a heap array there).  The
     fast form carries 100 intervals in scratch; the pass that exhausts them is repeated with kernels whose workspaces are the
-    context's pool in global memory (codegen.cpp GFH_WSG; launch.cpp wsg_grid): every pass meets the oracle, the pool is an
+    context's pool in global memory (emit_quadrature.cpp GFH_WSG; launch.cpp wsg_grid): every pass meets the oracle, the pool is an
     allocation the library owns -- reported by gfh_device_memory, gone after gfh_destroy -- and an absurd size is an error."""
     from gadfit_amd import _lib
     from gadfit_amd.ad import trace_model
@@ -357,7 +357,7 @@ def test_value_of_an_advar_inside_an_integrand():
         c.close()
 
 
-# ---- mesh hand-over between passes at the same parameters (codegen.cpp mesh_build; launch.cpp mesh_mode_for) ------------------------
+# ---- mesh hand-over between passes at the same parameters (emit_quadrature.cpp mesh_build; launch.cpp mesh_mode_for) ------------------------
 def _fresh_context(mesh):
     old = os.environ.get('GADFIT_HIP_MESH')
     os.environ['GADFIT_HIP_MESH'] = '1' if mesh else '0'
