@@ -108,6 +108,8 @@ SYMBOLS = {
     'gfh_set_batch_lanes': (_i, [_vp, _i]),
     'gfh_batch_auto_lanes': (_i, [_i, _i64]),
     'gfh_debug_batch_lanes': (_i, [_vp]),
+    'gfh_set_batch_cube': (_i, [_vp, _i64, _i64, _dp, _vp, _i, _i, _dp]),
+    'gfh_debug_batch_form': (_i, [_vp]),
     'gfh_set_lookahead': (_i, [_vp, _i]),
     'gfh_set_keep_jacobian': (_i, [_vp, _i]),
     'gfh_set_use_ad': (_i, [_vp, _i]),
@@ -144,6 +146,8 @@ SYMBOLS = {
 }
 
 
+# the sample types of a cube (Context.set_batch_cube): gfh_set_batch_cube's y_type by numpy dtype
+_CUBE_TYPES = {np.dtype(np.float64): 0, np.dtype(np.float32): 1, np.dtype(np.uint16): 2}
 # gfh_batch_result as a numpy record (Context.fit_batch returns an array of them)
 BATCH_RESULT_DTYPE = np.dtype([(n, np.int32) for n in ('iterations', 'exit_reason', 'n_sweeps', 'n_chi2', 'n_omega', 'dof')] +
                               [('lambda_', np.float64), ('chi2', np.float64)], align=True)
@@ -498,12 +502,44 @@ class Context:
             raise
         self.n_fits = off.size - 1
 
+    def set_batch_cube(self, x, Y, error_type=0, w=None):
+        """a batch as a cube: every spectrum on the one grid x [n_points], Y [n_fits][n_points] C-contiguous in float64, float32 or
+        uint16 (uploaded as it is; any other dtype is refused, nothing is converted), the weights formed on the device by
+        error_type's rule (init_weights' numbers: 0 NONE, 1 SQRT_Y, 2 PROPTO_Y, 3 INVERSE_Y) or, under 4 (USER), w [n_fits][n_points],
+        the weights as used in (y - f) * w -- gfh_set_batch_cube"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if not isinstance(Y, np.ndarray) or Y.dtype not in _CUBE_TYPES:
+            raise GadfitHipError('set_batch_cube: Y must be a numpy array of float64, float32 or uint16 (it is uploaded as it is), got %s'
+                                 % (Y.dtype if isinstance(Y, np.ndarray) else type(Y).__name__))
+        if Y.ndim != 2 or not Y.flags['C_CONTIGUOUS']:
+            raise GadfitHipError('set_batch_cube: Y must be 2-D [n_fits][n_points] and C-contiguous')
+        if x.ndim != 1 or x.size != Y.shape[1]:
+            raise GadfitHipError('set_batch_cube: x must hold one abscissa per column of Y (%d), got %d' % (Y.shape[1], x.size))
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float64)
+            if w.shape != Y.shape:
+                raise GadfitHipError('set_batch_cube: w must have the shape of Y %s, got %s' % (Y.shape, w.shape))
+        self.n_fits = 0
+        try:
+            self._chk(lib().gfh_set_batch_cube(self._h, Y.shape[0], Y.shape[1], dp(x), Y.ctypes.data_as(_vp), _CUBE_TYPES[Y.dtype],
+                                               int(error_type), None if w is None else dp(w)))
+        except GadfitHipError as e:
+            if 'no GPU bound' in str(e):       # (a compile-only context keeps the geometry and the form, as under set_batch_data)
+                self.n_fits = Y.shape[0]
+            raise
+        self.n_fits = Y.shape[0]
+
+    def batch_form_used(self):
+        """the data form of the last batch launch: None (none yet), 'ragged', or ('cube', y_type, error_type) -- gfh_debug_batch_form"""
+        f = int(lib().gfh_debug_batch_form(self._h))
+        return None if f < 0 else 'ragged' if f == 0 else ('cube', (f - 1) % 3, (f - 1) // 3)
+
     def _batch_args(self, who, pars, active):
         p = np.ascontiguousarray(pars, dtype=np.float64).copy()
         a = np.ascontiguousarray(active, dtype=np.int32)
         n = getattr(self, 'n_fits', 0)
         if n < 1:
-            raise GadfitHipError(who + ': no batch data (set_batch_data)')
+            raise GadfitHipError(who + ': no batch data (set_batch_data, set_batch_cube)')
         if p.size != n * self.n_pars:
             raise GadfitHipError('%s: pars must hold n_fits x n_pars = %d x %d values, got %d' % (who, n, self.n_pars, p.size))
         if a.size < 1 or a.min() < 0 or a.max() >= self.n_pars:

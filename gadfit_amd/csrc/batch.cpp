@@ -1,6 +1,6 @@
 // batch.cpp -- batched independent fits: many Levenberg-Marquardt fits of ONE model in ONE kernel launch, each with its own data,
 // start parameters, lambda history and exit (gfh_set_batch_data, gfh_fit_batch, gfh_batch_pass, gfh_batch_source, gfh_batch_prepare,
-// gfh_set_batch_lanes).  This file validates, uploads, compiles / loads and launches; the loop itself (gadfit.F90:670-915) is the
+// gfh_set_batch_lanes; gfh_set_batch_cube: the same batch as a cube on one grid with narrow samples).  This file validates, uploads, compiles / loads and launches; the loop itself (gadfit.F90:670-915) is the
 // generated kernel gfh_k_fit_batch (batch_fit.hip; codegen.cpp, emit_batch_kernels), a wave per fit or -- gfh_set_batch_lanes(16) -- a
 // DPP row of 16 lanes per fit and four fits per wave, or -- gfh_set_batch_lanes(256) -- a workgroup of four waves per fit.  One stream, one launch and one device-to-host copy per call.
 // Everything the kernels do not carry is refused here with its own message, before anything touches the device.
@@ -56,7 +56,7 @@ int check_model(gfh_ctx* c, const char* who, int na, const int32_t* active) {
 }
 int check_geometry(gfh_ctx* c, const char* who, int na) {
   const std::string w(who);
-  if (c->batch.n_fits < 1) return fail(c, w + ": no batch data (gfh_set_batch_data)");
+  if (c->batch.n_fits < 1) return fail(c, w + ": no batch data (gfh_set_batch_data, gfh_set_batch_cube)");
   if (c->batch.min_points < na) return fail(c, "More independent fitting parameters than data points (a fit of the batch has " +
                                               std::to_string((long long)c->batch.min_points) + " points).");      // gadfit.F90:648-657, per fit
   return 0;
@@ -69,8 +69,12 @@ GenConfig batch_config(const gfh_ctx* c, int lanes) {
   cfg.fast_div = c->gen.fast_div;
   cfg.batch = true;
   cfg.batch_lanes = lanes;
+  cfg.batch_cube = c->batch.cube;   // the data form held: a cube's sample type and weight rule are part of the text (batch_cube.hip)
+  if (c->batch.cube) { cfg.batch_y_type = c->batch.y_type; cfg.batch_error_type = c->batch.error_type; }
   return cfg;
 }
+// 0 ragged, 1 ... 15 a cube by sample type and weight rule: what gfh_debug_batch_form reports and the kernel cache keys on
+int data_form(const gfh_ctx* c) { return c->batch.cube ? 1 + c->batch.y_type + 3 * c->batch.error_type : 0; }
 // the form a call uses: the context's setting, under auto what the rule gives for the geometry held (64 when the context holds none)
 int batch_lanes(const gfh_ctx* c, int na) {
   if (c->batch.lanes != 0) return c->batch.lanes;
@@ -80,6 +84,7 @@ int batch_kernels(gfh_ctx* c, const std::vector<int32_t>& active, int lanes, boo
   std::vector<int32_t> key = active;
   key.push_back(-(1 << 30));        // (no plain active set holds a negative entry)
   key.push_back(lanes);             // both forms of one active set can be resident
+  if (c->batch.cube) key.push_back(data_form(c));      // ... and so can its cube forms beside the ragged one (whose key stays what it was)
   auto it = c->kernel_cache.find(key);
   if (it != c->kernel_cache.end()) { if (out) *out = &it->second; return 0; }
   std::string src, err;
@@ -121,6 +126,7 @@ int gfh_set_batch_data(gfh_ctx* c, int64_t n_fits, const int64_t* offsets, const
   if (join_pending(c)) return 1;
   if (c->device >= 0 && c->batch.on_device) { hipSetDevice(c->device); if (c->stream) hipStreamSynchronize(c->stream); }
   batch_free(c);
+  c->batch.cube = false; c->batch.y_type = c->batch.error_type = 0;
   c->batch.n_fits = n_fits; c->batch.off.assign(offsets, offsets + n_fits + 1); c->batch.min_points = shortest; c->batch.max_points = longest;
   NEED_GPU(c);
   const size_t n = (size_t)offsets[n_fits], nb = sizeof(double) * std::max<size_t>(n, 1);
@@ -137,6 +143,41 @@ int gfh_set_batch_data(gfh_ctx* c, int64_t n_fits, const int64_t* offsets, const
   c->batch.on_device = true;
   return 0;
 } catch (const std::exception& e) { return fail(c, std::string("gfh_set_batch_data: ") + e.what()); }
+
+// The same batch as a cube (include/gadfit_hip.h): one grid x [n_points] for every spectrum, the samples y [n_fits][n_points] in
+// y_type (0 double, 1 float, 2 uint16_t), the weights formed in the kernels' load by error_type's rule -- no weight array anywhere --
+// or, under USER (4), w [n_fits][n_points] as used.  Replaces the batch the context held; geometry AND form are kept before the device
+// is asked for.  The launches below work on whichever data is held: a cube's kernels are translation units of their own.
+int gfh_set_batch_cube(gfh_ctx* c, int64_t n_fits, int64_t n_points, const double* x, const void* y, int y_type, int error_type,
+                       const double* w) try {
+  if (check_context(c, "gfh_set_batch_cube")) return 1;
+  if (!x || !y) return fail(c, "gfh_set_batch_cube: null argument (x and y are required)");
+  if (n_fits < 1) return fail(c, "gfh_set_batch_cube: a batch holds at least one fit");
+  if (n_points < 1) return fail(c, "gfh_set_batch_cube: a spectrum holds at least one point");
+  if (n_fits > ((int64_t)1 << 31) - 4) return fail(c, "gfh_set_batch_cube: more fits than one launch takes (2^31 - 4)");
+  if (y_type < 0 || y_type > 2) return fail(c, "gfh_set_batch_cube: unknown y_type " + std::to_string(y_type) + " (0 double, 1 float, 2 uint16_t)");
+  if (error_type < 0 || error_type > 4)
+    return fail(c, "gfh_set_batch_cube: unknown error_type " + std::to_string(error_type) + " (0 NONE, 1 SQRT_Y, 2 PROPTO_Y, 3 INVERSE_Y, 4 USER)");
+  if (error_type == 4 && !w) return fail(c, "gfh_set_batch_cube: error_type USER needs the weights w");
+  if (error_type != 4 && w) return fail(c, "gfh_set_batch_cube: w is taken under error_type USER alone (the other types form the weights from y on the device)");
+  if (n_points > INT64_MAX / 8 / n_fits) return fail(c, "gfh_set_batch_cube: n_fits x n_points overflows");
+  if (join_pending(c)) return 1;
+  if (c->device >= 0 && c->batch.on_device) { hipSetDevice(c->device); if (c->stream) hipStreamSynchronize(c->stream); }
+  batch_free(c);
+  c->batch.cube = true; c->batch.y_type = y_type; c->batch.error_type = error_type;
+  c->batch.n_fits = n_fits; c->batch.off.clear(); c->batch.min_points = c->batch.max_points = n_points;
+  NEED_GPU(c);
+  const size_t n = (size_t)n_fits * (size_t)n_points, yb = n * (y_type == 0 ? 8 : y_type == 1 ? 4 : 2);
+  if (dev_alloc(c, c->batch.x, sizeof(double) * (size_t)n_points) || dev_alloc(c, c->batch.y, yb)) return 1;
+  if (w && dev_alloc(c, c->batch.w, sizeof(double) * n)) return 1;
+  copy_path_ready();
+  HIPCHK(c, hipMemcpyAsync(c->batch.x.p, x, sizeof(double) * (size_t)n_points, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->batch.y.p, y, yb, hipMemcpyHostToDevice, c->stream));
+  if (w) HIPCHK(c, hipMemcpyAsync(c->batch.w.p, w, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->batch.on_device = true;
+  return 0;
+} catch (const std::exception& e) { return fail(c, std::string("gfh_set_batch_cube: ") + e.what()); }
 
 // gadf_fit (gadfit.F90:502-1035) for every spectrum of the batch at once: STEP 1+2, the damped solve (potr_f08,
 // gadfit_linalg.F90:36-57), STEP 3 under accth, STEP 4 with its retrials and STEP 5 run on the device, a wave or -- gfh_set_batch_lanes --
@@ -168,7 +209,7 @@ int gfh_fit_batch(gfh_ctx* c, double* pars, int na, const int32_t* active, const
   bo.damp_plain = lo.damp_plain;
   if (o->DTD_min) for (int j = 0; j < na; j++) bo.dtd_min[j] = o->DTD_min[j];                            // gadfit.F90:641-646 (the same for every fit)
   NEED_GPU(c);
-  if (!c->batch.on_device) return fail(c, "gfh_fit_batch: no batch data on the device (gfh_set_batch_data)");
+  if (!c->batch.on_device) return fail(c, "gfh_fit_batch: no batch data on the device (gfh_set_batch_data, gfh_set_batch_cube)");
   gfh::Range range("gadfit gfh_fit_batch");
   ModelKernels* mk = nullptr;
   const int lanes = batch_lanes(c, na), per_wg = 256 / lanes;
@@ -180,11 +221,12 @@ int gfh_fit_batch(gfh_ctx* c, double* pars, int na, const int32_t* active, const
   harvest_events(c);
   HIPCHK(c, hipMemcpyAsync(c->batch.io.p, pars, pb, hipMemcpyHostToDevice, c->stream));
   void* x = c->batch.x.p; void* y = c->batch.y.p; void* w = c->batch.w.p; void* off = c->batch.off_d.p;
+  long long npts = c->batch.max_points;      // a cube's kernels take n_points where the ragged ones take the offsets (GFH_BARGS)
   void* dp = c->batch.io.p; void* recs = c->batch.io.as<char>() + pb; long long n = nf; void* stp = c->status.p;
-  void* args[] = {&x, &y, &w, &off, &dp, &bo, &recs, &n, &stp};
+  void* args[] = {&x, &y, &w, c->batch.cube ? (void*)&npts : (void*)&off, &dp, &bo, &recs, &n, &stp};
   HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
   HIPCHK(c, hipModuleLaunchKernel(mk->fit_batch, (unsigned)((nf + per_wg - 1) / per_wg), 1, 1, 256, 1, 1, 0, c->stream, args, nullptr));
-  c->batch.last_lanes = lanes;
+  c->batch.last_lanes = lanes; c->batch.last_form = data_form(c);
   HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
   HIPCHK(c, hipMemcpyAsync(c->batch.host.data(), c->batch.io.p, pb + rb, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -201,7 +243,7 @@ int gfh_batch_pass(gfh_ctx* c, const double* pars, int na, const int32_t* active
   if (!pars || !JTJ || !JTres || !chi2) return fail(c, "gfh_batch_pass: null argument");
   if (check_geometry(c, "gfh_batch_pass", na)) return 1;
   NEED_GPU(c);
-  if (!c->batch.on_device) return fail(c, "gfh_batch_pass: no batch data on the device (gfh_set_batch_data)");
+  if (!c->batch.on_device) return fail(c, "gfh_batch_pass: no batch data on the device (gfh_set_batch_data, gfh_set_batch_cube)");
   ModelKernels* mk = nullptr;
   const int lanes = batch_lanes(c, na), per_wg = 256 / lanes;
   if (batch_kernels(c, std::vector<int32_t>(active, active + na), lanes, true, &mk)) return 1;
@@ -212,10 +254,11 @@ int gfh_batch_pass(gfh_ctx* c, const double* pars, int na, const int32_t* active
   c->batch.host.resize(ib);
   HIPCHK(c, hipMemcpyAsync(c->batch.io.p, pars, pb, hipMemcpyHostToDevice, c->stream));
   void* x = c->batch.x.p; void* y = c->batch.y.p; void* w = c->batch.w.p; void* off = c->batch.off_d.p;
+  long long npts = c->batch.max_points;
   void* dp = c->batch.io.p; void* img = c->batch.img.p; long long n = nf; void* stp = c->status.p;
-  void* args[] = {&x, &y, &w, &off, &dp, &img, &n, &stp};
+  void* args[] = {&x, &y, &w, c->batch.cube ? (void*)&npts : (void*)&off, &dp, &img, &n, &stp};
   HIPCHK(c, hipModuleLaunchKernel(mk->batch_pass, (unsigned)((nf + per_wg - 1) / per_wg), 1, 1, 256, 1, 1, 0, c->stream, args, nullptr));
-  c->batch.last_lanes = lanes;
+  c->batch.last_lanes = lanes; c->batch.last_form = data_form(c);
   HIPCHK(c, hipMemcpyAsync(c->batch.host.data(), c->batch.img.p, ib, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const double* h = reinterpret_cast<const double*>(c->batch.host.data());
@@ -256,6 +299,8 @@ int gfh_set_batch_lanes(gfh_ctx* c, int lanes) try {
 
 // The form of the last batch launch of this context (64, 16 or 256; 0: none yet), so that a test asserts the dispatch.
 int gfh_debug_batch_lanes(gfh_ctx* c) { return c ? c->batch.last_lanes : 0; }
+// ... and its data form: -1 none yet, 0 ragged, else a cube, 1 + y_type + 3 * error_type
+int gfh_debug_batch_form(gfh_ctx* c) { return c ? c->batch.last_form : -1; }
 
 // The auto rule: a function of the active count and the longest spectrum of the batch, never of the data.  16 or 64: the workgroup
 // form (256) is the caller's choice alone (it wins where the fits are fewer than the card's SIMDs, which the rule does not see;

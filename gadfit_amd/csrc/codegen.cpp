@@ -8,7 +8,7 @@
 // Only what depends on the tape is generated here: the point functions, the quadrature call sites, the selector and the
 // #defines in front of them (emit_ad.cpp unrolls a tape, emit_quadrature.cpp and emit_branching.cpp write what integrate() and a
 // branching eval() add).  The kernels themselves are hand-written HIP that no tape changes; they are plain files under
-// device/ (sweep.hip, fused_sweep_gram.hip, chi2.hip, omega.hip, omega_jt.hip, batch_fit.hip, batch_wg_sum.hip, ...), embedded by
+// device/ (sweep.hip, fused_sweep_gram.hip, chi2.hip, omega.hip, omega_jt.hip, batch_fit.hip, batch_wg_sum.hip, batch_cube.hip, ...), embedded by
 // device_text.cpp and streamed into the translation unit by generate_source as they are.  Loading and validating a tape is
 // model.cpp.
 #include "codegen_internal.h"
@@ -70,6 +70,10 @@ static bool emit_batch_kernels(const Model& m, const std::vector<int32_t>& activ
   s << "\n#define GFH_BATCH 1\n#define GFH_BACT {";
   for (int j = 0; j < NA; j++) s << (j ? ", " : "") << active[j];
   s << "}\n#define GFH_BLANES " << cfg.batch_lanes << "\n";
+  if (cfg.batch_cube) {             // batch_cube.hip: the data form and the load of a cube, in the text of the cube forms alone
+    if (cfg.batch_y_type < 0 || cfg.batch_y_type > 2 || cfg.batch_error_type < 0 || cfg.batch_error_type > 4) { *err = "batch kernels: a cube's y_type is 0 ... 2, its error_type 0 ... 4"; return false; }
+    s << "#define GFH_BCUBE 1\n#define GFH_BYTYPE " << cfg.batch_y_type << "\n#define GFH_BERR " << cfg.batch_error_type << "\n" << kBatchCube;
+  }
   if (cfg.batch_lanes == 256) s << kBatchWgSum;          // batch_wg_sum.hip: LDS and a barrier, in the text of the workgroup form alone
   s << kBatchFit;                   // batch_fit.hip: gfh_k_fit_batch, gfh_k_batch_pass, written once against GFH_BLANES
   return true;

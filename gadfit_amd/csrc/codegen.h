@@ -30,6 +30,11 @@ struct GenConfig {
                           // (batch.cpp).  A translation unit of its own: the default one does not change by a byte
   int batch_lanes = 64;   // ... lanes per fit of those two (GFH_BLANES): 64, a wave per fit, 16, a DPP row per fit and four fits per wave,
                           // or 256, a workgroup per fit
+  bool batch_cube = false; // ... their data is a cube (gfh_set_batch_cube): one shared grid, the samples in batch_y_type, the weight formed
+                          // in the load by batch_error_type's rule (GFH_BCUBE, GFH_BYTYPE, GFH_BERR; batch_cube.hip).  Again translation
+                          // units of their own: the ragged ones carry none of the three macros
+  int batch_y_type = 0;   // 0 double, 1 float, 2 uint16_t
+  int batch_error_type = 0; // gfh_init_weights' numbers: 0 NONE, 1 SQRT_Y, 2 PROPTO_Y, 3 INVERSE_Y, 4 USER (a plain load of w)
 };
 
 // Where the quadrature workspaces of a translation unit live (numerical_integration.F90:40-51, 128-134: the reference's are heap arrays

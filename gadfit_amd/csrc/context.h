@@ -187,6 +187,11 @@ struct gfh_ctx {
     int64_t max_points = 0;         // of the longest: with the active count, all the auto rule of gfh_set_batch_lanes reads
     int lanes = 64;                 // gfh_set_batch_lanes: 64 a wave per fit, 16 a DPP row per fit, 256 a workgroup per fit, 0 auto (gfh_batch_auto_lanes: 16 or 64)
     int last_lanes = 0;             // the form of the last batch launch (gfh_debug_batch_lanes); 0: none yet
+    // gfh_set_batch_cube: every spectrum on one grid.  x holds the grid [n_points], y the samples [n_fits][n_points] in y_type
+    // (0 double, 1 float, 2 uint16_t), w the weights under error_type 4 (USER) alone, off stays empty (min_points = max_points = n_points)
+    bool cube = false;
+    int y_type = 0, error_type = 0;
+    int last_form = -1;             // the data form of the last batch launch (gfh_debug_batch_form); -1: none yet
     bool on_device = false;
     gfh::DevBuf x, y, w, off_d, io, img;
     std::vector<char> host;         // where the one device-to-host copy of a call lands

@@ -28,7 +28,6 @@ struct gfh_batch_opts {          // the options of gfh_fit that the batch carrie
   int lam_incs, max_iter, has_max_iter, use_accth, has_chi2_abs, has_chi2_rel, has_rel_error, damp_plain;
 };
 struct gfh_batch_rec { int iterations, exit_reason, n_sweeps, n_chi2, n_omega, dof; double lambda, chi2; };
-struct gfh_bdata { const double* __restrict__ x; const double* __restrict__ y; const double* __restrict__ w; i64 b, e; int lane; };
 
 #if GFH_BLANES == 64
 static __device__ __forceinline__ double gfh_uni(const double v) {      // lane 0's value as a wave-uniform one
@@ -74,9 +73,18 @@ static_assert(GFH_BWG_NACC == GFH_BNACC, "batch_wg_sum.hip sizes its LDS images 
 #define GFH_BIMG
 #define GFH_BIMG_INIT
 #endif
+// The data form: a fit's points (gfh_bdata), the four data arguments of the two kernels (GFH_BARGS), a fit's gfh_bdata from them
+// (GFH_BDATA) and the load (GFH_BLOAD), through which ALL point access goes.  Here the ragged form of gfh_set_batch_data: x, y, w
+// back to back as doubles, fit f owns [off[f], off[f + 1]).  The cube forms (GFH_BCUBE, gfh_set_batch_cube) bring their own four in
+// batch_cube.hip, emitted in front of this file: one shared grid, narrow samples, the weight formed in the load.
+#ifndef GFH_BCUBE
+struct gfh_bdata { const double* __restrict__ x; const double* __restrict__ y; const double* __restrict__ w; i64 b, e; int lane; };
+#define GFH_BARGS const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ w, const i64* __restrict__ off
+#define GFH_BDATA(f) {x, y, w, off[f], off[f + 1], (int)(threadIdx.x & (GFH_BLANES - 1))}
 // the inputs of pass row i0 (uniform in the fit) for this lane; past the end: the last point with w = 0
 #define GFH_BLOAD(X, Y, W, i0) { const i64 i_ = (i0) + d.lane; const i64 c_ = i_ < d.e ? i_ : d.e - 1; \
   X = d.x[c_]; Y = d.y[c_]; const double w_ = d.w[c_]; W = i_ < d.e ? w_ : 0.0; }
+#endif
 
 // STEP 1 + 2 (gadfit.F90:675-699) of one fit: S = [J^T J upper triangle, packed | J^T r | sum r^2]
 static __device__ __forceinline__ void gfh_b_sweep(const gfh_bdata& d, const double* __restrict__ P, int* status, double (&S)[GFH_BNACC] GFH_BIMG_DECL) {
@@ -217,7 +225,7 @@ static __device__ __forceinline__ double gfh_b_dtd(const double (&a)[GFH_NA], co
 // gfh_b_chi2, of gfh_b_sweep and of gfh_b_omega, none inside their point loops.  The four waves of the workgroup must make the same
 // sequence of these calls, so every branch or loop that encloses one is decided only by
 //   (K) kernel arguments (o.*, n_fits),
-//   (O) the fit's off[f], off[f + 1] (d.b, d.e; f = blockIdx.x is the workgroup's), or
+//   (O) the fit's off[f], off[f + 1] (d.b, d.e; f = blockIdx.x is the workgroup's; in a cube 0 and the kernel argument n_points: (K)), or
 //   (S) values that came out of gfh_b_sum_n -- the same LDS words added in the same order in every lane -- or were computed from such
 //       values and (K), (O) by the same instruction sequence under contract(off): S, DTD, JTr, delta1, delta2, lambda, P, old_pars,
 //       the chi2 values and the iteration count.  No per-lane quantity (d.lane, x, y, w, the accumulators before the sum) and nothing
@@ -227,15 +235,16 @@ static __device__ __forceinline__ double gfh_b_dtd(const double (&a)[GFH_NA], co
 // old_chi2 (S) and i <= o.lam_incs (K).  `lds_img` is toggled once per gfh_b_sum_n and nowhere else, so it is the same in the four waves.
 // A NaN or Inf in a spectrum therefore ends the fit with reason 8 at the same solve in all four waves.  The branches on d.lane == 0
 // and on the lane inside gfh_b_sum_n enclose no barrier.  Lane 0 of wave 0 writes the parameters and the record.
+// The cube's load (batch_cube.hip) adds only per-lane values -- the sample converted to double and the weight formed from it -- and
+// none of them enters a branch that encloses a barrier: its selects (the threshold of SQRT_Y / PROPTO_Y, the clamp) sit inside GFH_BLOAD.
 extern "C" __global__ __launch_bounds__(256)
-void gfh_k_fit_batch(const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ w,
-                     const i64* __restrict__ off, double* __restrict__ pars, const gfh_batch_opts o,
+void gfh_k_fit_batch(GFH_BARGS, double* __restrict__ pars, const gfh_batch_opts o,
                      gfh_batch_rec* __restrict__ recs, const i64 n_fits, int* __restrict__ status) {
 #pragma clang fp contract(off)
   const i64 f = GFH_BFIT(threadIdx.x);
   if (f >= n_fits) return;
   constexpr int act[GFH_NA] = GFH_BACT;
-  const gfh_bdata d = {x, y, w, off[f], off[f + 1], (int)(threadIdx.x & (GFH_BLANES - 1))};
+  const gfh_bdata d = GFH_BDATA(f);
   double P[GFH_NP], old_pars[GFH_NA], DTD[GFH_NA], delta1[GFH_NA], delta2[GFH_NA], S[GFH_BNACC], JTr[GFH_NA];
 #pragma unroll
   for (int k = 0; k < GFH_NP; k++) P[k] = gfh_uni(pars[f * GFH_NP + k]);
@@ -326,12 +335,11 @@ void gfh_k_fit_batch(const double* __restrict__ x, const double* __restrict__ y,
 // STEP 1 + 2 only, at given parameters: each fit's J^T J [na x na] (both triangles), J^T r [na] and chi2 -- the "one pass" of
 // callers with their own loop.  img [n_fits][na * na + na + 1].
 extern "C" __global__ __launch_bounds__(256)
-void gfh_k_batch_pass(const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ w,
-                      const i64* __restrict__ off, const double* __restrict__ pars, double* __restrict__ img,
+void gfh_k_batch_pass(GFH_BARGS, const double* __restrict__ pars, double* __restrict__ img,
                       const i64 n_fits, int* __restrict__ status) {
   const i64 f = GFH_BFIT(threadIdx.x);
   if (f >= n_fits) return;
-  const gfh_bdata d = {x, y, w, off[f], off[f + 1], (int)(threadIdx.x & (GFH_BLANES - 1))};
+  const gfh_bdata d = GFH_BDATA(f);
   double P[GFH_NP], S[GFH_BNACC];
 #pragma unroll
   for (int k = 0; k < GFH_NP; k++) P[k] = gfh_uni(pars[f * GFH_NP + k]);

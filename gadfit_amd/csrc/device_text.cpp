@@ -37,6 +37,9 @@ const char kOmegaJt[] = {
 const char kBatchWgSum[] = {
 #embed "device/batch_wg_sum.hip"
 , 0};
+const char kBatchCube[] = {
+#embed "device/batch_cube.hip"
+, 0};
 const char kBatchFit[] = {
 #embed "device/batch_fit.hip"
 , 0};

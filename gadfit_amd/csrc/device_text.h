@@ -15,6 +15,7 @@ extern const char kChi2[];             // chi2.hip: gfh_k_chi2
 extern const char kOmega[];            // omega.hip: the tangent block of STEP 3, gfh_k_omega
 extern const char kOmegaJt[];          // omega_jt.hip: gfh_k_omega_jt
 extern const char kBatchWgSum[];       // batch_wg_sum.hip: gfh_b_sum_n, the cross-wave reducer of the 256-lane form of the batch kernels
+extern const char kBatchCube[];        // batch_cube.hip: the data form and the load of the cube forms of the batch kernels (gfh_set_batch_cube)
 extern const char kBatchFit[];         // batch_fit.hip: gfh_k_fit_batch, gfh_k_batch_pass
 
 }  // namespace gfh

@@ -83,7 +83,8 @@ void gfh::dev_release(int device, DevBuf& b) {
 }
 
 // the blocks of a batch of independent fits (context.h, Batch; batch.cpp fills them): dropped together by the next
-// gfh_set_batch_data, and what gfh_device_memory reports of them
+// gfh_set_batch_data or gfh_set_batch_cube, and what gfh_device_memory reports of them (a cube holds its grid in x, its narrow
+// samples in y, w under USER alone and no offsets)
 void gfh::batch_free(gfh_ctx* c) {
   DevBuf* bufs[] = {&c->batch.x, &c->batch.y, &c->batch.w, &c->batch.off_d, &c->batch.io, &c->batch.img};
   for (DevBuf* b : bufs) dev_free(*b);

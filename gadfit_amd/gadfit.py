@@ -283,6 +283,23 @@ def gadf_fit(lambda_=None, lam_up=None, lam_down=None, accth=None, grad_chi2=Non
     return r
 
 
+def _batch_context(who):
+    """the session's context with its model current, for a batch call (gadf_fit_batch, gadf_fit_cube)"""
+    if _S.ctx is None:
+        _S.ctx = _lib.Context(_S.device)
+        if 'GADFIT_HIP_KEEP_J' not in os.environ:
+            _S.ctx.set_keep_jacobian(2)       # (as _ensure_device: a gadf_fit of this session may follow)
+    if _S.tape is None or not _tape_is_current():
+        try:
+            _S.tape = _S.fitfuncs[0].trace()
+        except TypeError as e:
+            raise GadfitError('%s: %s' % (who, e))
+        _S.ctx.set_model(_S.tape)
+        _S.uploaded = False
+    _S.ctx.set_loss(_S.loss)
+    _S.ctx.set_use_ad(True)
+
+
 def gadf_fit_batch(xs, ys, ws, pars, lambda_=None, lam_up=None, lam_down=None, accth=None, rel_error=None, chi2_rel=None,
                    chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, lanes_per_fit=None, **kw):
     """Many independent fits of the session's model in one kernel launch (gfh_fit_batch): gadf_fit's loop (gadfit.F90:670-915) per
@@ -310,23 +327,54 @@ def gadf_fit_batch(xs, ys, ws, pars, lambda_=None, lam_up=None, lam_down=None, a
         raise GadfitError('gadf_fit_batch: pars must be [n_fits][n_pars] = [%d][%d]' % (len(xs), len(_S.fitfuncs[0].pars)))
     if _S.comm is not None:
         raise GadfitError('gadf_fit_batch: the fits are independent; split the batch over the ranks instead of sharing a communicator')
-    if _S.ctx is None:
-        _S.ctx = _lib.Context(_S.device)
-        if 'GADFIT_HIP_KEEP_J' not in os.environ:
-            _S.ctx.set_keep_jacobian(2)       # (as _ensure_device: a gadf_fit of this session may follow)
-    if _S.tape is None or not _tape_is_current():
-        try:
-            _S.tape = _S.fitfuncs[0].trace()
-        except TypeError as e:
-            raise GadfitError('gadf_fit_batch: %s' % e)
-        _S.ctx.set_model(_S.tape)
-        _S.uploaded = False
-    _S.ctx.set_loss(_S.loss)
-    _S.ctx.set_use_ad(True)
+    _batch_context('gadf_fit_batch')
     off = np.zeros(len(xs) + 1, dtype=np.int64)
     np.cumsum([v.size for v in xs], out=off[1:])
     try:
         _S.ctx.set_batch_data(off, np.concatenate(xs), np.concatenate(ys), np.concatenate(ws))
+        out, res, _ = _S.ctx.fit_batch(pars, active, DTD_min=DTD_min, lanes_per_fit=lanes_per_fit, lambda_=_f32(lambda_), lam_up=_f32(lam_up), lam_down=_f32(lam_down),
+                                       accth=_f32(accth), rel_error=_f32(rel_error), chi2_rel=_f32(chi2_rel), chi2_abs=_f32(chi2_abs),
+                                       lam_incs=lam_incs, max_iter=max_iter, damp_max=None if damp_max is None else int(damp_max),
+                                       **{k: v for k, v in kw.items() if v is not None})
+    except _lib.GadfitHipError as e:
+        raise GadfitError(str(e))
+    return out, res
+
+
+def gadf_fit_cube(x, Y, pars, sigma=None, lambda_=None, lam_up=None, lam_down=None, accth=None, rel_error=None, chi2_rel=None,
+                  chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, lanes_per_fit=None, **kw):
+    """gadf_fit_batch over a data cube (gfh_set_batch_cube): every spectrum on the one grid ``x`` [n_points], ``Y`` [n_fits][n_points] a
+    C-contiguous numpy array of float64, float32 or uint16 that is uploaded as it is.  The weights follow from ``Y`` on the device by
+    the session's ``gadf_set_errors`` type (NONE, SQRT_Y, PROPTO_Y, INVERSE_Y: no weight array exists anywhere; gadf_fit_batch ignores
+    that type, this call takes it); under USER ``sigma`` [n_fits][n_points] is required and 1 / sigma is passed.  ``pars``, the fit
+    arguments, ``lanes_per_fit`` and what is returned are gadf_fit_batch's."""
+    _need_init()
+    if 'lambda' in kw:
+        lambda_ = kw.pop('lambda')
+    if _S.n_datasets != 1:
+        raise GadfitError('gadf_fit_cube needs a session with one dataset slot: gadf_init(f)')
+    active = [i for i, a in enumerate(_S.active) if a]
+    if not active:
+        raise GadfitError('There are no active parameters.')
+    x = np.asarray(x, dtype=np.float64).ravel()
+    if not isinstance(Y, np.ndarray) or Y.ndim != 2 or Y.shape[1] != x.size or Y.shape[0] < 1:
+        raise GadfitError('gadf_fit_cube: Y must be a numpy array [n_fits][n_points] with one column per abscissa of x (%d)' % x.size)
+    if _S.error_type == USER:
+        if sigma is None:
+            raise GadfitError('gadf_fit_cube: USER errors requested but no sigma was given')
+        sigma = np.asarray(sigma, dtype=np.float64)
+        if sigma.shape != Y.shape:
+            raise GadfitError('gadf_fit_cube: sigma must have the shape of Y')
+    elif sigma is not None:
+        raise GadfitError('gadf_fit_cube: sigma is taken under USER errors alone (gadf_set_errors)')
+    pars = np.asarray(pars, dtype=np.float64)
+    if pars.shape != (Y.shape[0], len(_S.fitfuncs[0].pars)):
+        raise GadfitError('gadf_fit_cube: pars must be [n_fits][n_pars] = [%d][%d]' % (Y.shape[0], len(_S.fitfuncs[0].pars)))
+    if _S.comm is not None:
+        raise GadfitError('gadf_fit_cube: the fits are independent; split the cube over the ranks instead of sharing a communicator')
+    _batch_context('gadf_fit_cube')
+    try:
+        _S.ctx.set_batch_cube(x, Y, _S.error_type, None if sigma is None else 1.0 / sigma)
         out, res, _ = _S.ctx.fit_batch(pars, active, DTD_min=DTD_min, lanes_per_fit=lanes_per_fit, lambda_=_f32(lambda_), lam_up=_f32(lam_up), lam_down=_f32(lam_down),
                                        accth=_f32(accth), rel_error=_f32(rel_error), chi2_rel=_f32(chi2_rel), chi2_abs=_f32(chi2_abs),
                                        lam_incs=lam_incs, max_iter=max_iter, damp_max=None if damp_max is None else int(damp_max),

@@ -219,7 +219,8 @@ int  gfh_debug_mesh_stats(gfh_ctx* ctx, int64_t* out4);
  * 128-134: heap arrays there) live in ONE allocation of the context, a slot per wave of a launch, once they exceed 8 KB of scratch per
  * lane; it is cut at the first pass that needs it, an error code if the card cannot provide it, and freed by gfh_destroy.  A group
  * handle reports member 0's card and the sum of the members' pools.  The blocks of a batch of independent fits (gfh_set_batch_data:
- * the spectra, their offsets, the parameter / result block and the images of gfh_batch_pass) are counted in out3[2] as well. */
+ * the spectra, their offsets, the parameter / result block and the images of gfh_batch_pass; after gfh_set_batch_cube the grid, the
+ * samples in their narrow type and, under USER, the weights -- and nothing of the batch they replaced) are counted in out3[2] as well. */
 int  gfh_device_memory(gfh_ctx* ctx, int64_t* out3);
 /* Generated HIP source for the current model and an active set (debug / AOT builds).
  * Returns bytes needed (including NUL); copies at most cap bytes. */
@@ -431,6 +432,25 @@ int  gfh_set_batch_lanes(gfh_ctx* ctx, int lanes);
 int  gfh_batch_auto_lanes(int n_act, int64_t longest_spectrum);
 /* 64, 16 or 256: the form of the last batch launch of this context (0: none yet).  For tests that assert the dispatch. */
 int  gfh_debug_batch_lanes(gfh_ctx* ctx);
+/* A batch as a data cube: n_fits spectra of n_points each on ONE abscissa grid x [n_points], the samples y [n_fits][n_points]
+ * spectrum-major in the type y_type names -- 0 double, 1 float, 2 uint16_t, each of which converts to double exactly -- and the
+ * weights formed from y on the device, inside the kernels' load, by error_type's rule (the numbers and expressions of
+ * gfh_init_weights, gadfit.F90:445-470): 0 NONE 1, 1 SQRT_Y 1 / sqrt(y), 2 PROPTO_Y 1 / y (both 0 where |y| < 100 DBL_MIN),
+ * 3 INVERSE_Y y, 4 USER.  Under 0 ... 3 no weight array exists anywhere and w must be NULL; under USER w [n_fits][n_points] is
+ * required and holds the weights as used in (y - f) * w, the meaning of gfh_set_batch_data's w (NOT sigma).  The device holds
+ * 8 n_points + (8, 4 or 2) n_fits n_points bytes (+ 8 per point under USER) against gfh_set_batch_data's 24 per point.
+ * Replaces the batch the context held, ragged or cube, as gfh_set_batch_data replaces a cube.  gfh_fit_batch, gfh_batch_pass,
+ * gfh_batch_source, gfh_batch_prepare and gfh_set_batch_lanes work on whichever data is held, with every check and refusal as it
+ * is (the auto rule reads n_points as the longest spectrum); the cube forms are translation units of their own, one per (y_type,
+ * error_type, lanes), with the LM loop's one text and another load, and return the bits of the ragged form fed x tiled, y widened
+ * and gfh_init_weights' weights.  Refused, each with its own message, before the device is asked for: NULL x or y, n_fits < 1 or
+ * n_points < 1, more fits than a launch takes, an unknown y_type or error_type, USER without w, w with another type, group handles
+ * and communicators of several ranks.  A compile-only context keeps the geometry and the form, then ends in "no GPU". */
+int  gfh_set_batch_cube(gfh_ctx* ctx, int64_t n_fits, int64_t n_points, const double* x, const void* y, int y_type,
+                        int error_type, const double* w);
+/* The data form of the last batch launch of this context: -1 none yet, 0 ragged (gfh_set_batch_data), else a cube:
+ * 1 + y_type + 3 * error_type (1 ... 15).  For tests that assert the dispatch. */
+int  gfh_debug_batch_form(gfh_ctx* ctx);
 
 /* ---- Jacobian_indices / dim (gadfit.F90:615-631) as a helper for callers */
 int  gfh_jacobian_indices(int n_datasets, int n_act, const int32_t* active_pars,

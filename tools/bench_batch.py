@@ -7,6 +7,7 @@ profiles/r05_small_fits.txt: 1000 points, a Gaussian on a background, 4 paramete
                                 [--observed FILE [--observed-only]] [--out profiles/batch_rows.json]
     python tools/bench_batch.py --workgroup [--points 1000,4096,16384,65536] [--sizes 64,256,1024,16384] [--models gauss4,exp4]
                                 [--registers] [--observed FILE [--observed-only]] [--out profiles/batch_workgroup.json]
+    python tools/bench_batch.py --cube [--cells gauss4:64:16384:1000,...] [--registers] [--out profiles/batch_cube.json]
 
 Per batch size: warm-up launches, then the median of the timed launches -- device time from the HIP events around the kernel
 (gfh_fit_batch's `seconds`) and wall time around the whole call (parameters down, launch, results back).  Two yardsticks, neither of
@@ -32,7 +33,16 @@ row_wins per active-count class.  --registers: the compiler's register, scratch 
 spectrum AND fits per launch, since what the workgroup form buys is occupancy when the fits are fewer than the card's SIMDs: per
 (model, fits, points) both forms alternating launch by launch on one context; cells above 2^30 points in total are dropped.  The
 yardstick of the 256-lane form is the 64-lane form of the same run; `workgroup_wins` is tests/batch_row_cases.row_wins.  With
---registers: the compiler's figures (LDS included) of the 256-lane kernels of the three units of the --rows table."""
+--registers: the compiler's figures (LDS included) of the 256-lane kernels of the three units of the --rows table.
+--cube: a batch as a data cube (gfh_set_batch_cube: one shared grid, narrow samples, the weight formed in the load) against the
+ragged form of the same spectra with precomputed SQRT_Y weights -- the yardstick, measured in the same run, never the cube's own time.
+The spectra are counts (the models above scaled by 1000 and rounded, so that uint16 holds them); per cell (model, lanes, fits,
+points) the five forms -- ragged, float64 / USER (the shared grid alone), float64 / SQRT_Y (against it: the price of the in-load
+weight), float32 / SQRT_Y, uint16 / SQRT_Y -- alternate launch by launch on one context of one card, each launch behind the upload
+of its own data, by the recipe of --rows; all five hold the same values, so they run the same passes (checked: the totals must be
+equal).  `upload_ms` is the wall time of the set call, median of 3.  `wins` is tests/batch_row_cases.row_wins against the ragged
+form.  With --registers: the compiler's figures of the uint16 / SQRT_Y and float64 / USER units of model_exp2 and model_exp4 at the
+three lane forms (no GPU); model_exp2's must have no scratch."""
 import argparse
 import json
 import os
@@ -175,6 +185,120 @@ def registers_record(forms=(64, 16)):
             rec['%s_lanes%d' % (name, lanes)] = kernel_registers(c.batch_source(m['active']))
     c.close()
     return rec
+
+
+CUBE_SCALE = 1000.0                  # counts = round(CUBE_SCALE * the model's spectrum): 500 ... 3500 (gauss4), 40 ... 11000 (exp4)
+CUBE_FORMS = (('ragged', None, None), ('float64_user', np.float64, 4), ('float64_sqrt_y', np.float64, 1), ('float32_sqrt_y', np.float32, 1),
+              ('uint16_sqrt_y', np.uint16, 1))
+CUBE_CELLS = 'gauss4:64:16384:1000,gauss4:64:131072:1000,gauss4:16:131072:64,gauss4:256:256:65536,exp4:64:16384:1000'
+
+
+def cube_registers_record():
+    from tests import models as M
+    rec = {}
+    c = _lib.Context(-1)
+    for name, fn, n_pars in (('exp2', M.model_exp2, 4), ('exp4', M.model_exp4, 8)):
+        c.set_model(trace_model(fn, n_pars))
+        for lanes in (64, 16, 256):
+            c.set_batch_lanes(lanes)
+            for form, dtype, et in (('uint16_sqrt_y', np.uint16, 1), ('float64_user', np.float64, 4)):
+                try:
+                    c.set_batch_cube(np.arange(8.0), np.ones((1, 8), dtype=dtype), et, np.ones((1, 8)) if et == 4 else None)
+                except _lib.GadfitHipError as e:
+                    if 'no GPU' not in str(e):
+                        raise
+                rec['%s_lanes%d_%s' % (name, lanes, form)] = r = kernel_registers(c.batch_source(list(range(n_pars))))
+                if name == 'exp2' and any(k['scratch_bytes_per_lane'] != 0 for k in r.values()):
+                    sys.exit('model_exp2 %s at %d lanes: scratch is not 0: %s' % (form, lanes, r))
+    c.close()
+    return rec
+
+
+def cube_main(a):
+    from tests import batch_row_cases as RC
+    rec = dict(method='per cell (model, lanes per fit, fits, points per spectrum) five data forms of the same spectra -- counts, round(%g x the model) -- '
+                      'alternating launch by launch on one context of one card in one run, each launch behind the upload of its own data: the median and '
+                      'the min-max of %d launches after %d warm-up launches; device = HIP events around the kernel; lambda0 = %g, max_iter = %d and no '
+                      'other exit; all forms hold the same values and run the same passes (checked); upload_ms = wall time of the set call, median of 3; '
+                      'the yardstick is the ragged form of the same run with precomputed SQRT_Y weights; wins = tests/batch_row_cases.row_wins against '
+                      'it; no counter pass was made' % (CUBE_SCALE, a.launches, a.warmup, LAMBDA0, MAX_ITER), measurements=[])
+    if os.path.exists(a.out):
+        old = json.load(open(a.out))
+        if 'registers' in old:
+            rec['registers'] = old['registers']
+    kw = dict(lambda_=LAMBDA0, max_iter=MAX_ITER)
+    for cell in a.cells.split(','):
+        name, lanes, nf, n = cell.split(':')
+        lanes, nf, n = int(lanes), int(nf), int(n)
+        m = ROW_MODELS[name]
+        t0 = time.perf_counter()
+        xs, y, _ = spectra_flat(name, nf, n)
+        x = xs[:n].copy()
+        counts = np.round(CUBE_SCALE * y).reshape(nf, n)
+        del y
+        if counts.min() < 1 or counts.max() > 65535:
+            sys.exit('the counts leave uint16')
+        w = 1.0 / np.sqrt(counts)                       # SQRT_Y on the host, as a caller of set_batch_data forms it
+        data = {'float64': counts, 'float32': counts.astype(np.float32), 'uint16': counts.astype(np.uint16)}
+        off = np.arange(nf + 1, dtype=np.int64) * n
+        amp = np.where(np.arange(m['n_pars']) % 2 == 0, CUBE_SCALE, 1.0) if name == 'exp4' else np.array([CUBE_SCALE, 1.0, 1.0, CUBE_SCALE])
+        start = np.tile(m['start'] * amp, (nf, 1))
+        print('%-6s %3d lanes %6d fits x %5d points: data in %.1f s' % (name, lanes, nf, n, time.perf_counter() - t0), flush=True)
+        ctx = _lib.Context(0)
+        ctx.set_model(trace_model(m['model'], m['n_pars']))
+        ctx.set_batch_lanes(lanes)
+
+        def upload(form, dtype, et):
+            t = time.perf_counter()
+            if dtype is None:
+                ctx.set_batch_data(off, xs, counts.reshape(-1), w.reshape(-1))
+            else:
+                ctx.set_batch_cube(x, data[np.dtype(dtype).name], et, w if et == 4 else None)
+            return time.perf_counter() - t
+        entry = dict(model=name, what=m['what'], n_active=len(m['active']), lanes=lanes, fits=nf, points=n, forms={})
+        dev = {f[0]: [] for f in CUBE_FORMS}; up = {f[0]: [] for f in CUBE_FORMS}
+        out = {}
+        for it in range(a.warmup + a.launches):
+            for form, dtype, et in CUBE_FORMS:       # the forms alternate launch by launch: a drift of the card's clock meets all alike
+                t_up = upload(form, dtype, et)
+                p, r, sec = ctx.fit_batch(start, m['active'], **kw)
+                want = 'ragged' if dtype is None else ('cube', (np.float64, np.float32, np.uint16).index(dtype), et)
+                if ctx.batch_lanes_used() != lanes or ctx.batch_form_used() != want:
+                    sys.exit('the launch did not take the form asked for')
+                if it >= a.warmup:
+                    dev[form].append(sec)
+                    if len(up[form]) < 3:
+                        up[form].append(t_up)
+                out[form] = (p, r)
+        ctx.close()
+        p0, r0 = out['ragged']
+        for form, dtype, et in CUBE_FORMS:
+            p, r = out[form]
+            if not (np.array_equal(p, p0) and all(np.array_equal(r[f], r0[f]) for f in ('n_sweeps', 'n_chi2', 'n_omega', 'exit_reason', 'iterations'))):
+                sys.exit('%s does not return what the ragged form returns' % form)
+            d = statistics.median(dev[form])
+            entry['forms'][form] = dict(device_ms=1e3 * d, device_ms_min=1e3 * min(dev[form]), device_ms_max=1e3 * max(dev[form]),
+                                        upload_ms=1e3 * statistics.median(up[form]),
+                                        bytes_per_point=24 if dtype is None else np.dtype(dtype).itemsize + (8 if et == 4 else 0))
+        entry['passes'] = dict(sweeps=int(r0['n_sweeps'].sum()), chi2=int(r0['n_chi2'].sum()), omega=int(r0['n_omega'].sum()))
+        entry['exit_reasons'] = {str(int(v)): int(np.sum(r0['exit_reason'] == v)) for v in sorted(set(r0['exit_reason'].tolist()))}
+        entry['finite'] = bool(np.all(np.isfinite(p0)))
+        for form, _, _ in CUBE_FORMS[1:]:
+            e = entry['forms'][form]
+            e['over_ragged_device_time'] = e['device_ms'] / entry['forms']['ragged']['device_ms']
+            e['over_ragged_upload_time'] = e['upload_ms'] / entry['forms']['ragged']['upload_ms']
+            e['wins'] = bool(RC.row_wins(e, entry['forms']['ragged']))
+            e['loses'] = bool(RC.row_wins(entry['forms']['ragged'], e))
+        rec['measurements'].append(entry)
+        print('\n'.join('   %-15s device %9.3f ms [%.3f, %.3f], upload %9.1f ms%s' % (
+            f, e['device_ms'], e['device_ms_min'], e['device_ms_max'], e['upload_ms'],
+            '' if f == 'ragged' else ', %.2f of ragged%s' % (e['over_ragged_device_time'], ' -> wins' if e['wins'] else ' -> loses' if e['loses'] else ''))
+            for f, e in entry['forms'].items()), flush=True)
+        with open(a.out, 'w') as fh:          # (after every cell: a run that is cut short leaves what it measured)
+            json.dump(rec, fh, indent=1, sort_keys=True)
+            fh.write('\n')
+        del xs, counts, w, data
+    print('wrote', a.out)
 
 
 def rows_main(a, points, lanes_list):
@@ -332,6 +456,8 @@ def main():
     ap.add_argument('--lanes', default=None, help='lanes per fit, 64, 16 or 256 (default 64); with --rows a list (default 64,16)')
     ap.add_argument('--rows', action='store_true', help='the two forms of the batch kernels against each other, into profiles/batch_rows.json')
     ap.add_argument('--workgroup', action='store_true', help='the 256-lane form of the batch kernels against the 64-lane form, into profiles/batch_workgroup.json')
+    ap.add_argument('--cube', action='store_true', help='a batch as a data cube against the ragged form of the same spectra, into profiles/batch_cube.json')
+    ap.add_argument('--cells', default=CUBE_CELLS, help='with --cube: model:lanes:fits:points, ...')
     ap.add_argument('--models', default='gauss4,exp4', help='with --workgroup: the models measured by this call (the record keeps the others)')
     ap.add_argument('--registers', action='store_true', help='with --rows or --workgroup: only the register figures of the four kernels into the record; no GPU is needed')
     ap.add_argument('--sizes', default='1024,16384,131072')
@@ -345,10 +471,10 @@ def main():
                                                                  'nothing is timed, no GPU is needed')
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'batch_workgroup.json' if a.workgroup else 'batch_rows.json' if a.rows else 'batch_fits.json')
-    if (a.rows or a.workgroup) and a.registers:
+        a.out = os.path.join(ROOT, 'profiles', 'batch_cube.json' if a.cube else 'batch_workgroup.json' if a.workgroup else 'batch_rows.json' if a.rows else 'batch_fits.json')
+    if (a.rows or a.workgroup or a.cube) and a.registers:
         rec = json.load(open(a.out)) if os.path.exists(a.out) else {}
-        rec['registers'] = registers_record((256,) if a.workgroup else (64, 16))
+        rec['registers'] = cube_registers_record() if a.cube else registers_record((256,) if a.workgroup else (64, 16))
         with open(a.out, 'w') as fh:
             json.dump(rec, fh, indent=1, sort_keys=True)
             fh.write('\n')
@@ -370,6 +496,8 @@ def main():
         return
     if a.launches < 5:
         sys.exit('at least 5 timed launches')
+    if a.cube:
+        return cube_main(a)
     if a.workgroup:
         if a.sizes == '1024,16384,131072':
             a.sizes = '64,256,1024,16384'
