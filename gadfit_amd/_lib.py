@@ -88,6 +88,7 @@ SYMBOLS = {
     'gfh_device_memory': (_i, [_vp, C.POINTER(_i64)]),
     'gfh_debug_deferred': (_i, [_vp, C.POINTER(C.c_longlong)]),
     'gfh_debug_layout': (_i, [_vp, C.POINTER(_i64)]),
+    'gfh_debug_chain': (_i, [_vp, C.POINTER(_i64), _i]),
     'gfh_debug_mesh_stats': (_i, [_vp, C.POINTER(_i64)]),
     'gfh_model_source': (_i64, [_vp, _i, _ip, C.c_char_p, _i64]),
     'gfh_model_prepare': (_i, [_vp, _i, _ip]),
@@ -381,6 +382,21 @@ class Context:
         out = (_i64 * 8)()
         self._chk(lib().gfh_debug_layout(self._h, out))
         return dict(zip(('n_slots', 'n_gb', 'datasets_with_blocks', 'fused', 'waves', 'tail_mode', 'sparse', 'kernarg'), (int(v) for v in out)))
+
+    def debug_chain(self):
+        """dict(gram, assemble, jtv_finish): what ran behind the model kernel of the most recent sweep -- gram: the Gram launches in
+        order, 'small<N>', 'gram<T>' or 'block<TR,TC,SYM>@(R0,C0)' (empty: the fused kernel); assemble: 'tail', 'k_gather_sum',
+        'k_assemble_sparse' or 'k_assemble' -- and of the most recent J^T v product -- jtv_finish: 'k_jtv_finish' or 'chain' (None each
+        while there is none) -- gfh_debug_chain"""
+        cap = 3 + 6 * 256
+        out = (_i64 * cap)()
+        self._chk(lib().gfh_debug_chain(self._h, out, cap))
+        assert 3 + 6 * out[2] <= cap
+        gram = []
+        for i in range(out[2]):
+            kind, a, b, sym, r0, c0 = (int(v) for v in out[3 + 6 * i:9 + 6 * i])
+            gram.append('small<%d>' % a if kind == 0 else 'gram<%d>' % a if kind == 1 else 'block<%d,%d,%s>@(%d,%d)' % (a, b, 'true' if sym else 'false', r0, c0))
+        return dict(gram=gram, assemble=(None, 'tail', 'k_gather_sum', 'k_assemble_sparse', 'k_assemble')[out[0]], jtv_finish=(None, 'k_jtv_finish', 'chain')[out[1]])
 
     def mesh_stats(self):
         """dict(integrals, bisections, unrecorded, sites) of the last recording pass of a quadrature model -- gfh_debug_mesh_stats"""

@@ -154,6 +154,11 @@ struct gfh_ctx {
   // how the most recent sweep was dispatched (sweep_pass notes it, gfh_debug_layout reports it): the fused kernel or the plain sweep,
   // its waves per workgroup, the tail mode it was handed (0: the launch chain), the pattern-only image
   struct LastSweep { int fused = 0, waves = 0, tail_mode = 0, sparse = 0; } last_sweep;
+  // which kernels the most recent sweep and the most recent J^T v product launched behind the model kernel, each noted at its launch
+  // (gfh_debug_chain reports them; nothing reads them to decide anything): the Gram launches of launch_gram (none: the fused kernel),
+  // the assembling step (0 none yet, 1 the fused kernel's tail, 2 k_gather_sum, 3 k_assemble_sparse, 4 k_assemble) and the J^T v
+  // finish (0 none yet, 1 k_jtv_finish, 2 k_reduce_partials + k_assemble_vec + the fetch)
+  struct Chain { std::vector<gfh::GramLaunch> gram; int assemble = 0, jtv_finish = 0; } chain;
 
   // timers (seconds) + counters (inspect.cpp; the passes count and bracket their launches)
   struct Timers {

@@ -253,6 +253,19 @@ int gfh_debug_layout(gfh_ctx* c, int64_t* out8) {
   out8[6] = swept ? k->last_sweep.sparse : -1; out8[7] = swept ? k->cur->kernarg_pars : -1;
   return 0;
 }
+// What ran behind the model kernel of the most recent sweep and of the most recent J^T v product, as the host noted it at each launch
+// (context.h, Chain): a report, not a rule -- the rules are launch_gram, launch_gram_chain, sweep_pass and jtv_finish.
+int gfh_debug_chain(gfh_ctx* c, int64_t* out, int cap) {
+  if (!c || !out || cap < 3) return 1;
+  const gfh_ctx* k = c->grp ? gfh::group_member(c, 0) : c;
+  out[0] = k->chain.assemble; out[1] = k->chain.jtv_finish; out[2] = (int64_t)k->chain.gram.size();
+  for (size_t i = 0; i < k->chain.gram.size() && 3 + 6 * (i + 1) <= (size_t)cap; i++) {
+    const GramLaunch& g = k->chain.gram[i];
+    int64_t* o = out + 3 + 6 * i;
+    o[0] = g.kind; o[1] = g.a; o[2] = g.b; o[3] = g.sym; o[4] = g.r0; o[5] = g.c0;
+  }
+  return 0;
+}
 int gfh_device_memory(gfh_ctx* c, int64_t* out3) {
   if (!c || !out3) return 1;
   gfh_ctx* k = c->grp ? gfh::group_member(c, 0) : c;

@@ -2,14 +2,18 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <vector>
 
 namespace gfh {
 typedef long long i64;
 
 int gram_partial_stride(int T);   // doubles per workgroup partial for T 16-row tiles
 
+// one Gram launch as launch_gram notes it where it launches (gfh_debug_chain): kind 0 = k_gram_small<a>, 1 = k_gram<a>,
+// 2 = k_gram_block<a, b, sym> at the tiles (r0, c0)
+struct GramLaunch { int kind, a, b, sym, r0, c0; };
 hipError_t launch_gram(hipStream_t st, int T, const double* J, i64 ldj, int na, const double* res,
-                       const i64* gb_start, const int* gb_slots, int n_gb, double* partial);
+                       const i64* gb_start, const int* gb_slots, int n_gb, double* partial, std::vector<GramLaunch>* note = nullptr);
 hipError_t launch_reduce_partials(hipStream_t st, const double* partial, int pstride, int width,
                                   const int* ds_first_gb, int nd, double* out);
 hipError_t launch_assemble(hipStream_t st, const double* G, int gw, int T, int nd, int dim, const int* inv, const int* owner, double* packed);

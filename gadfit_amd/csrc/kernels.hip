@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kernels.h"
+#include "codegen.h"
 
 namespace gfh {
 
@@ -220,7 +221,7 @@ template <int TR, int TC, bool SYM>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_gram_block(const double* __restrict__ J, const i64 ldj, const int na,
                                                     const double* __restrict__ res, const i64* __restrict__ gb_start,
                                                     const int* __restrict__ gb_slots, double* __restrict__ partial,
-                                                    const int pstride, const int T, const int R0, const int C0) {
+                                                    const int pstride, const int T, const int R0, const int C0, const int cw) {
   constexpr int NACC = SYM ? TR * (TR + 1) / 2 : TR * TC;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int r = lane & 15, q = lane >> 4;
@@ -265,16 +266,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       }
     }
   }
-  // sum r^2 (the launch with R0 == 0) in gfh_k_chi2's own map and order at the 8 waves it runs with beyond the fused kernel (chi2.hip,
-  // GFH_CW; a gram block is whole passes of 512 slots): this thread stands for threads tid and tid + 256 of such a workgroup -- each
-  // sums its own points pass by pass --, then the wave tree, then the eight waves in order.  With k_reduce_partials and the assembly
-  // above it that is the order of chi2(), so chi2() at a sweep's parameters is bitwise the sweep's sum here too.
+  // sum r^2 (the launch with R0 == 0) in gfh_k_chi2's own map and order at the cw waves it runs with for this number of active
+  // parameters (chi2.hip, GFH_CW: 8 beyond the fused kernel; a gram block is whole passes of 512 slots): this thread stands for threads
+  // tid and tid + 256 of such a workgroup -- each sums its own points pass by pass --, then the wave tree, then the eight waves in
+  // order.  cw == 4 (65 ... 128 active parameters, where this kernel runs for models with integrate() and under GADFIT_HIP_FUSED=0):
+  // gfh_k_chi2 has this kernel's 256 threads, each sums its own points pass by pass, then the wave tree and the four waves in order.
+  // With k_reduce_partials and the assembly above it that is the order of chi2(), so chi2() at a sweep's parameters is bitwise the
+  // sweep's sum here too.
   __shared__ double c8[8];
   if (SYM && R0 == 0) {
     double lo = 0.0, hi = 0.0;
-    for (i64 i = s + threadIdx.x; i + 256 < e; i += 512) {
-      const double r0 = res[i], r1 = res[i + 256];
-      lo += r0 * r0; hi += r1 * r1;
+    if (cw == 4) {
+      for (i64 i = s + threadIdx.x; i < e; i += 256) { const double r0 = res[i]; lo += r0 * r0; }
+    } else {
+      for (i64 i = s + threadIdx.x; i + 256 < e; i += 512) {
+        const double r0 = res[i], r1 = res[i + 256];
+        lo += r0 * r0; hi += r1 * r1;
+      }
     }
     lo = gfh_wave_sum(lo); hi = gfh_wave_sum(hi);
     if (lane == 0) { c8[wv] = lo; c8[wv + 4] = hi; }
@@ -337,7 +345,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (R0 == 0 && threadIdx.x == 0) {
       double sacc = c8[0];
 #pragma unroll
-      for (int w = 1; w < 8; w++) sacc += c8[w];
+      for (int w = 1; w < 8; w++) if (w < 4 || cw != 4) sacc += c8[w];
       out[npair * 256 + 16 * T] = sacc;
     }
   }
@@ -741,23 +749,24 @@ __global__ void k_init_weights(const int type, const i64 n, const double* __rest
 int gram_partial_stride(int T) { int n = T * (T + 1) / 2 * 256 + 16 * T + 1; return (n + 3) & ~3; }
 
 hipError_t launch_gram(hipStream_t st, int T, const double* J, i64 ldj, int na, const double* res,
-                       const i64* gb_start, const int* gb_slots, int n_gb, double* partial) {
+                       const i64* gb_start, const int* gb_slots, int n_gb, double* partial, std::vector<GramLaunch>* note) {
   const int ps = gram_partial_stride(T);
+  const int cw = na <= kFusedMaxActive ? fused_waves_for(na) : 8;          // GFH_CW of the generated source: the waves gfh_k_chi2 runs with
   if (na <= 8) {
     switch (na) {
-#define GFH_GS(N) case N: hipLaunchKernelGGL(k_gram_small<N>, dim3(n_gb), dim3(512), 0, st, J, ldj, res, gb_start, gb_slots, partial, ps); break;
+#define GFH_GS(N) case N: hipLaunchKernelGGL(k_gram_small<N>, dim3(n_gb), dim3(512), 0, st, J, ldj, res, gb_start, gb_slots, partial, ps); if (note) note->push_back({0, N, 0, 0, 0, 0}); break;
       GFH_GS(1) GFH_GS(2) GFH_GS(3) GFH_GS(4) GFH_GS(5) GFH_GS(6) GFH_GS(7) GFH_GS(8)
 #undef GFH_GS
     }
     return hipGetLastError();
   }
   switch (T) {
-    case 1: hipLaunchKernelGGL(k_gram<1>, dim3(n_gb), dim3(256), 0, st, J, ldj, na, res, gb_start, gb_slots, partial, ps); break;
-    case 2: hipLaunchKernelGGL(k_gram<2>, dim3(n_gb), dim3(256), 0, st, J, ldj, na, res, gb_start, gb_slots, partial, ps); break;
-    case 3: hipLaunchKernelGGL(k_gram<3>, dim3(n_gb), dim3(256), 0, st, J, ldj, na, res, gb_start, gb_slots, partial, ps); break;
-    case 4: hipLaunchKernelGGL(k_gram<4>, dim3(n_gb), dim3(256), 0, st, J, ldj, na, res, gb_start, gb_slots, partial, ps); break;
-    case 5: hipLaunchKernelGGL((k_gram_block<5, 5, true>), dim3(n_gb), dim3(256), 0, st, J, ldj, na, res, gb_start, gb_slots, partial, ps, T, 0, 0); break;
-    case 6: hipLaunchKernelGGL((k_gram_block<6, 6, true>), dim3(n_gb), dim3(256), 0, st, J, ldj, na, res, gb_start, gb_slots, partial, ps, T, 0, 0); break;
+    case 1: hipLaunchKernelGGL(k_gram<1>, dim3(n_gb), dim3(256), 0, st, J, ldj, na, res, gb_start, gb_slots, partial, ps); if (note) note->push_back({1, 1, 0, 0, 0, 0}); break;
+    case 2: hipLaunchKernelGGL(k_gram<2>, dim3(n_gb), dim3(256), 0, st, J, ldj, na, res, gb_start, gb_slots, partial, ps); if (note) note->push_back({1, 2, 0, 0, 0, 0}); break;
+    case 3: hipLaunchKernelGGL(k_gram<3>, dim3(n_gb), dim3(256), 0, st, J, ldj, na, res, gb_start, gb_slots, partial, ps); if (note) note->push_back({1, 3, 0, 0, 0, 0}); break;
+    case 4: hipLaunchKernelGGL(k_gram<4>, dim3(n_gb), dim3(256), 0, st, J, ldj, na, res, gb_start, gb_slots, partial, ps); if (note) note->push_back({1, 4, 0, 0, 0, 0}); break;
+    case 5: hipLaunchKernelGGL((k_gram_block<5, 5, true>), dim3(n_gb), dim3(256), 0, st, J, ldj, na, res, gb_start, gb_slots, partial, ps, T, 0, 0, cw); if (note) note->push_back({2, 5, 5, 1, 0, 0}); break;
+    case 6: hipLaunchKernelGGL((k_gram_block<6, 6, true>), dim3(n_gb), dim3(256), 0, st, J, ldj, na, res, gb_start, gb_slots, partial, ps, T, 0, 0, cw); if (note) note->push_back({2, 6, 6, 1, 0, 0}); break;
     default:
       // T > 6 (5 and 6 tiles: ONE launch that reads J once, above): blocks of up to 4 x 4 tiles over the upper triangle, diagonal blocks first.  The blocks at the edge are instantiated at
       // the number of tiles they really hold (80 parameters = 5 tiles: a 4 x 4 diagonal block, a 4 x 1 block and a 1 x 1 diagonal
@@ -766,7 +775,8 @@ hipError_t launch_gram(hipStream_t st, int T, const double* J, i64 ldj, int na, 
       for (int gi = 0; gi < T; gi += 4)
         for (int gj = gi; gj < T; gj += 4) {
           const int tr = T - gi < 4 ? T - gi : 4, tc = T - gj < 4 ? T - gj : 4;
-#define GFH_GB(TR_, TC_, SYM_) hipLaunchKernelGGL((k_gram_block<TR_, TC_, SYM_>), dim3(n_gb), dim3(256), 0, st, J, ldj, na, res, gb_start, gb_slots, partial, ps, T, gi, gj)
+#define GFH_GB(TR_, TC_, SYM_) do { hipLaunchKernelGGL((k_gram_block<TR_, TC_, SYM_>), dim3(n_gb), dim3(256), 0, st, J, ldj, na, res, gb_start, gb_slots, partial, ps, T, gi, gj, cw); \
+                                    if (note) note->push_back({2, TR_, TC_, SYM_ ? 1 : 0, gi, gj}); } while (0)
           if (gi == gj) {
             switch (tr) { case 1: GFH_GB(1, 1, true); break; case 2: GFH_GB(2, 2, true); break; case 3: GFH_GB(3, 3, true); break; default: GFH_GB(4, 4, true); }
           } else {

@@ -47,8 +47,9 @@ bool uses_fused_kernel(const gfh_ctx* c) { return use_fused(c); }
 // in order -- gfh_k_chi2's map and order at its 8 waves per workgroup -- and k_reduce_partials / k_gather_sum are the order gfh_k_chi2's
 // tail restates; the residuals themselves agree bit for bit (same value expressions; the quadrature's final pass rounds its panel
 // sums like the value-only pass).  Pinned by test_chi2_is_bitwise_the_sweeps_sum_of_squares*.
-// (Beyond 128 active parameters k_gram_block adds r^2 in gfh_k_chi2's order as well -- tests/test_gpu_gram_layouts.py holds it --; the
-// look-ahead schedule is not extended to them here.)
+// (k_gram_block adds r^2 in gfh_k_chi2's order as well, at the waves that kernel runs with for the active count: 8 beyond 128 active
+// parameters -- tests/test_gpu_gram_layouts.py holds it --, 4 at 65 ... 128 on the two-kernel path -- tests/test_gpu_gram_chain.py --;
+// the look-ahead schedule is not extended to them here.)
 bool sweep_chi2_is_bitwise(const gfh_ctx* c) {
   if (use_fused(c)) return true;
   return c->cur && c->cur_active.size() <= 8 && fused_waves_for((int)c->cur_active.size()) == 8 && !c->gen.finite_diff;
@@ -274,19 +275,24 @@ int gfh::launch_model_omega(gfh_ctx* c, int mesh_mode) {
 int gfh::launch_gram_chain(gfh_ctx* c, bool time_it, bool with_gram, bool sparse, unsigned long long publish_seq) {
   const int na = (int)c->cur_active.size(), T = c->cur_T, ps = gram_partial_stride(T);
   const int gw = ps;
+  c->chain.gram.clear();
   if (c->n_gb && with_gram) HIPCHK(c, launch_gram(c->stream, T, c->J.as<double>(), c->ldj, na, c->res.as<double>(), c->gb_start.as<i64>(),
-                                      c->gb_slots.as<int>(), c->n_gb, c->partial.as<double>()));
+                                      c->gb_slots.as<int>(), c->n_gb, c->partial.as<double>(), &c->chain.gram));
   if (time_it) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
   HIPCHK(c, launch_reduce_partials(c->stream, c->partial.as<double>(), ps, gw, c->ds_first_gb.as<int>(), c->nd, c->G.as<double>()));
-  if (c->gs_meta.p && c->gs_n && c->gs_sparse == sparse)
+  if (c->gs_meta.p && c->gs_n && c->gs_sparse == sparse) {
     HIPCHK(c, launch_gather_sum(c->stream, c->G.as<double>(), c->gs_meta.as<int>(), c->gs_list.as<int>(), c->gs_n, c->packed.as<double>(),
                                 c->status.as<int>(), publish_seq ? c->h_pinned : nullptr, reinterpret_cast<unsigned*>(c->status.as<char>() + 16),
                                 c->h_flag, publish_seq));
-  else if (sparse)
+    c->chain.assemble = 2;
+  } else if (sparse) {
     HIPCHK(c, launch_assemble_sparse(c->stream, c->G.as<double>(), gw, T, c->nd, c->cur_dim, c->inv.as<int>(), c->owner.as<int>(),
                                      c->nz_row.as<int>(), c->nz_col.as<int>(), c->nnz, c->packed.as<double>()));
-  else
+    c->chain.assemble = 3;
+  } else {
     HIPCHK(c, launch_assemble(c->stream, c->G.as<double>(), gw, T, c->nd, c->cur_dim, c->inv.as<int>(), c->owner.as<int>(), c->packed.as<double>()));
+    c->chain.assemble = 4;
+  }
   return 0;
 }
 

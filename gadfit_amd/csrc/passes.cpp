@@ -174,6 +174,7 @@ static int sweep_pass(gfh_ctx* c, const double* pars, const int32_t* active, int
   if (td >= 1) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
   if (tail) {
     // reduction, assembly and (single rank) the mailbox write happened in the fused kernel's tail
+    c->chain.gram.clear(); c->chain.assemble = 1;
     if (td >= 2) { HIPCHK(c, hipEventRecord(c->ev[2], c->stream)); HIPCHK(c, hipEventRecord(c->ev[3], c->stream)); }
     if (c->comm) {
       if (allreduce_sum(c, c->packed.as<double>(), packed_n, true)) return 1;
@@ -294,11 +295,13 @@ static int jtv_finish(gfh_ctx* c, double* out) {
                                   c->vec.as<double>(), c->status.as<int>(), c->h_pinned, c->h_flag, seq));
       PASS(await_result(c, seq, dim));
     }
+    c->chain.jtv_finish = 1;
     memcpy(out, c->h_pinned, sizeof(double) * dim);
     return 0;
   }
   HIPCHK(c, launch_reduce_partials(c->stream, c->partial.as<double>(), ps, na, c->ds_first_gb.as<int>(), c->nd, c->G.as<double>()));
   HIPCHK(c, launch_assemble_vec(c->stream, c->G.as<double>(), na, c->nd, dim, c->inv.as<int>(), c->vec.as<double>()));
+  c->chain.jtv_finish = 2;
   if (c->comm && allreduce_sum(c, c->vec.as<double>(), (size_t)dim)) return 1;
   PASS(fetch_result(c, c->vec.as<double>(), dim, c->comm != nullptr));
   memcpy(out, c->h_pinned, sizeof(double) * dim);

@@ -325,6 +325,14 @@ int  gfh_debug_deferred(gfh_ctx* ctx, long long* out4);
  * pattern-only image of a global fit, 0 the dense one, out8[7] = doubles of the parameter block passed by value as a kernel argument (0:
  * by pointer).  A group handle reports member 0. */
 int  gfh_debug_layout(gfh_ctx* ctx, int64_t* out8);
+/* Which kernels ran behind the model kernel, noted by the host at each launch (read-only; for tests that must know which instantiation
+ * a case reached).  Of the most recent gfh_sweep: out[0] = the assembling step (0: none yet, 1: the fused kernel's own tail,
+ * 2: k_gather_sum, 3: k_assemble_sparse, 4: k_assemble), out[2] = n, the number of Gram launches (0: the fused kernel formed the Gram
+ * image), and from out[3] on six numbers per launch, as many launches as fit `cap` numbers: kind (0: k_gram_small<a>, 1: k_gram<a>,
+ * 2: k_gram_block<a, b, sym>), a, b, sym, and the block's first row and column tile.  Of the most recent J^T v product (gfh_omega,
+ * gfh_aux(0)): out[1] = its finish (0: none yet, 1: k_jtv_finish, 2: k_reduce_partials + k_assemble_vec and the copy).  cap >= 3.
+ * A group handle reports member 0. */
+int  gfh_debug_chain(gfh_ctx* ctx, int64_t* out, int cap);
 
 /* load_balancing of gadf_fit -- "adaptive parallelism" (gadfit.F90:672-673, re_initialize 935-983): with more than
  * one rank (processes with a communicator, or the members of a device group) gfh_fit re-cuts the contiguous ranges

@@ -188,17 +188,23 @@ def jacobian_indices(nd, active, is_global):
     return jac, nd * na - shift
 
 
-def pattern_only(nd, active, is_global, sparse_ok=True):
-    """does the image travel as its pattern (active.cpp: compute_layout, transfer_sparse)?"""
+def pattern_nnz(nd, active, is_global):
+    """(row <= col) pairs of columns that some dataset couples (active.cpp: compute_layout)"""
     jac, dim = jacobian_indices(nd, active, is_global)
-    if dim * dim * nd <= SMALL_MAX or not sparse_ok or nd < 2:
-        return False
     keys = set()
     for d in range(nd):
         r, c = np.meshgrid(jac[d], jac[d], indexing='ij')
         m = r <= c
         keys.update((c[m].astype(np.int64) * dim + r[m]).tolist())
-    return 4 * (len(keys) + dim + 1) < dim * dim + dim + 1
+    return len(keys)
+
+
+def pattern_only(nd, active, is_global, sparse_ok=True):
+    """does the image travel as its pattern (active.cpp: compute_layout, transfer_sparse)?"""
+    dim = jacobian_indices(nd, active, is_global)[1]
+    if dim * dim * nd <= SMALL_MAX or not sparse_ok or nd < 2:
+        return False
+    return 4 * (pattern_nnz(nd, active, is_global) + dim + 1) < dim * dim + dim + 1
 
 
 class Case:
@@ -238,13 +244,15 @@ class Case:
         start = start_values(its truth), the global parameters at start_values(the first dataset's truth)"""
         return _data(self.model, self.K, tuple(self.sizes), tuple(self.is_global))
 
-    def expect(self, nranks=1, rank=0, tail_on=True, sparse_ok=True):
-        """what Context.debug_layout() reports after a sweep of this case on rank `rank` of `nranks` pseudo-ranks"""
+    def expect(self, nranks=1, rank=0, tail_on=True, sparse_ok=True, fused_on=True):
+        """what Context.debug_layout() reports after a sweep of this case on rank `rank` of `nranks` pseudo-ranks (tail_on, sparse_ok,
+        fused_on: GADFIT_HIP_TAIL, GADFIT_HIP_SPARSE, GADFIT_HIP_FUSED of the context; without the fused kernel there is no tail)"""
         n_slots, blocks = block_layout(local_sizes(self.sizes, nranks, rank))
         n_gb = sum(blocks)
-        tail = tail_on and self.fused and n_gb > 0 and self.small and (tail_one_workgroup_per_cu(self.na) or n_gb <= 256)
-        return dict(n_slots=n_slots, n_gb=n_gb, datasets_with_blocks=sum(b > 0 for b in blocks), fused=int(self.fused),
-                    waves=fused_waves_for(self.na) if self.fused else 0, tail_mode=2 if tail else 0,
+        fused = fused_on and self.fused
+        tail = tail_on and fused and n_gb > 0 and self.small and (tail_one_workgroup_per_cu(self.na) or n_gb <= 256)
+        return dict(n_slots=n_slots, n_gb=n_gb, datasets_with_blocks=sum(b > 0 for b in blocks), fused=int(fused),
+                    waves=fused_waves_for(self.na) if fused else 0, tail_mode=2 if tail else 0,
                     sparse=int(pattern_only(self.nd, self.active, self.is_global, sparse_ok)), kernarg=self.kernarg)
 
     def __repr__(self):
