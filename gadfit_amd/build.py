@@ -9,7 +9,8 @@ CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libgadfit_hip.so')
 # every source and header of csrc/ (a new file is built, and watched by the staleness check, without being listed here).  csrc/device/
-# is not compiled on its own: device_text.cpp embeds its files and kernels.hip includes one of them, so they are watched like headers.
+# is not compiled on its own: device_text.cpp embeds its files and the .hip files of csrc/ (gram, assemble, jtv, kernels) include some of
+# them, so they are watched like headers.
 SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith(('.cpp', '.hip')))
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith('.h')) + sorted('device/' + f for f in os.listdir(os.path.join(CSRC, 'device'))) + \
           ['exports.map', '../../include/gadfit_hip.h', '../../include/gadfit_tape.h']

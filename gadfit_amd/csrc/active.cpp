@@ -1,8 +1,9 @@
 // active.cpp -- model, kernels and active set: the model a context fits (gfh_set_model*), the generated kernels of an active set
-// (get_kernels: generate, compile, load, cache), the layout of the packed image the ranks sum (PackedLayout), and prepare_active, which
-// sizes every buffer a pass of that active set needs.  It launches nothing and owns no timing; buffers come from devmem.cpp.
+// (get_kernels: generate, compile, load, cache), and prepare_active, which sizes every buffer a pass of that active set needs and
+// uploads the layout of the packed image the ranks sum (packed_layout.cpp).  It launches nothing and owns no timing; buffers come from devmem.cpp.
 #include "context_internal.h"
 #include "group.h"
+#include "packed_layout.h"
 #include <algorithm>
 #include <cstring>
 #include <exception>
@@ -80,56 +81,6 @@ int gfh::check_aux(gfh_ctx* c) {
   return 0;
 }
 
-// What the ranks all-reduce after a sweep is the image `packed`: [JTJ (dim*dim, column-major) | JTres | chi2], or for global
-// fits beyond the in-kernel tail's reach the pattern-only [nnz values | JTres | chi2].  ncclAllReduce needs the same length
-// and the same meaning of every element on every rank, so the layout may depend only on what all ranks share -- the column
-// map, dim, the number of datasets -- never on which points (or whether any) THIS rank holds.  Host-only: also what
-// gfh_debug_packed_layout reports for compile-only contexts (CPU tests of the multi-rank bookkeeping).
-struct PackedLayout {
-  std::vector<int> inv, owner, nz_row, nz_col;
-  bool sparse = false;         // the pattern is a quarter of the dense image or less
-  bool small = false;          // dim*dim*n_datasets <= 65536: dense image, assembled by the fused kernel's tail where it applies
-  int nnz = 0;
-  bool transfer_sparse() const { return sparse && !small; }
-  size_t packed_n(int dim) const { return transfer_sparse() ? (size_t)nnz + dim + 1 : (size_t)dim * dim + dim + 1; }
-};
-
-static int compute_layout(gfh_ctx* c, int nd, int na, const int32_t* jac, int dim, bool sparse_ok, PackedLayout* L) {
-  L->inv.assign((size_t)nd * dim, -1);
-  for (int d = 0; d < nd; d++)
-    for (int k = 0; k < na; k++) {
-      const int col = jac[d * na + k];
-      if (col < 0 || col >= dim) return fail(c, "Jacobian index out of range");
-      L->inv[(size_t)d * dim + col] = k;
-    }
-  // owner[col]: the single dataset that uses column col (local parameter) or -1 (several: global parameter)
-  L->owner.assign(dim, -1);
-  std::vector<int> users(dim, 0);
-  for (int d = 0; d < nd; d++) for (int k = 0; k < na; k++) { const int col = jac[d * na + k]; if (users[col]++ == 0) L->owner[col] = d; }
-  for (int col = 0; col < dim; col++) if (users[col] != 1) L->owner[col] = -1;
-  if (nd == 1) std::fill(L->owner.begin(), L->owner.end(), 0);
-  // pattern of the normal equations: (row <= col) pairs of columns that share a dataset, column-major order
-  L->sparse = false; L->nnz = 0; L->nz_row.clear(); L->nz_col.clear();
-  L->small = (int64_t)dim * dim * nd <= 65536;
-  if (sparse_ok && nd > 1) {
-    // the (row <= col) pairs some dataset couples, in column-major order (sorted keys: a dim x dim map costs 16 MB and 8e6 tests
-    // per call at the 4003 columns of a 1000-curve fit)
-    std::vector<int64_t> keys;
-    keys.reserve((size_t)nd * na * (na + 1) / 2);
-    for (int d = 0; d < nd; d++)
-      for (int k = 0; k < na; k++) for (int m = 0; m < na; m++) {
-        const int r_ = jac[d * na + k], c_ = jac[d * na + m];
-        if (r_ <= c_) keys.push_back((int64_t)c_ * dim + r_);
-      }
-    std::sort(keys.begin(), keys.end());
-    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
-    for (const int64_t key : keys) { L->nz_row.push_back((int)(key % dim)); L->nz_col.push_back((int)(key / dim)); }
-    L->nnz = (int)L->nz_row.size();
-    L->sparse = 4 * ((int64_t)L->nnz + dim + 1) < (int64_t)dim * dim + dim + 1;      // worth it when the pattern is a quarter or less
-  }
-  return 0;
-}
-
 // the buffer of the quadrature meshes (context.h): one record per slot and outermost integrate() call site of the model
 int gfh::ensure_mesh(gfh_ctx* c) {
   const int sites = (c->has_model && c->disp.mesh_on && c->gen.fast_div && unit_takes_mesh_args(c->model, c->gen)) ? mesh_sites(c->model) : 0;
@@ -160,8 +111,8 @@ int gfh::prepare_active(gfh_ctx* c, const int32_t* active, int na, const int32_t
   const bool same = (a == c->cur_active) && (j == c->cur_jac) && dim == c->cur_dim;
   c->cur_T = (na + 15) / 16;
   if (!same) {
-    PackedLayout L;
-    if (compute_layout(c, c->nd, na, jac, dim, c->sparse_ok, &L)) return 1;
+    PackedLayout L; std::string lerr;
+    if (!compute_layout(c->nd, na, jac, dim, c->sparse_ok, &L, &lerr)) return fail(c, lerr);
     const std::vector<int>& inv = L.inv;
     if (dev_alloc(c, c->inv, sizeof(int) * inv.size())) return 1;
     HIPCHK(c, hipMemcpy(c->inv.p, inv.data(), sizeof(int) * inv.size(), hipMemcpyHostToDevice));
@@ -173,47 +124,15 @@ int gfh::prepare_active(gfh_ctx* c, const int32_t* active, int na, const int32_t
       HIPCHK(c, hipMemcpy(c->nz_row.p, c->h_nz_row.data(), sizeof(int) * (size_t)c->nnz, hipMemcpyHostToDevice));
       HIPCHK(c, hipMemcpy(c->nz_col.p, c->h_nz_col.data(), sizeof(int) * (size_t)c->nnz, hipMemcpyHostToDevice));
     }
-    // source lists for k_gather_sum: where in G (the per-dataset Gram images, [nd][gw]) the terms of every element of the packed
-    // image sit, in dataset order -- what k_assemble / k_assemble_sparse find through owner/inv at run time.  Built for the layout
-    // the launch chain will use: pattern-only [nnz values | JTres | chi2] or dense [JTJ column-major | JTres | chi2].
+    // source lists for k_gather_sum, for the layout the launch chain will use (none: the chain assembles through owner / inv)
     {
-      const int T = c->cur_T, gw = gram_partial_stride(T), npair = T * (T + 1) / 2;
-      const bool lay_sparse = L.transfer_sparse();
-      const int64_t n_img = (int64_t)L.packed_n(dim);
-      dev_free(c->gs_meta); c->gs_n = 0; c->gs_sparse = lay_sparse;
-      if ((int64_t)c->nd * gw < (int64_t(1) << 31) && n_img <= (int64_t(1) << 18)) {
-        std::vector<int> meta((size_t)n_img), list, terms;
-        auto put = [&](size_t idx) {
-          if (terms.empty()) meta[idx] = (int)0x80000000;
-          else if (terms.size() == 1) meta[idx] = terms[0];
-          else { meta[idx] = -((int)list.size() + 1); list.push_back((int)terms.size()); list.insert(list.end(), terms.begin(), terms.end()); }
-        };
-        auto entry = [&](int row, int col) {
-          terms.clear();
-          for (int d = 0; d < c->nd; d++) {
-            int a_ = inv[(size_t)d * dim + row], b_ = inv[(size_t)d * dim + col];
-            if (a_ < 0 || b_ < 0) continue;
-            if (a_ > b_) std::swap(a_, b_);                 // upper triangle of tile pairs is stored
-            const int ti = a_ >> 4, tj = b_ >> 4, p = ti * T - ti * (ti - 1) / 2 + (tj - ti);
-            terms.push_back(d * gw + p * 256 + (a_ & 15) * 16 + (b_ & 15));
-          }
-        };
-        const size_t nn = lay_sparse ? (size_t)c->nnz : (size_t)dim * dim;
-        if (lay_sparse) for (int k = 0; k < c->nnz; k++) { entry(c->h_nz_row[k], c->h_nz_col[k]); put((size_t)k); }
-        else for (int col = 0; col < dim; col++) for (int row = 0; row < dim; row++) { entry(row, col); put((size_t)col * dim + row); }
-        for (int row = 0; row < dim; row++) {
-          terms.clear();
-          for (int d = 0; d < c->nd; d++) { const int a_ = inv[(size_t)d * dim + row]; if (a_ >= 0) terms.push_back(d * gw + npair * 256 + a_); }
-          put(nn + row);
-        }
-        terms.clear();
-        for (int d = 0; d < c->nd; d++) terms.push_back(d * gw + npair * 256 + 16 * T);
-        put(nn + dim);
-        if (list.empty()) list.push_back(0);
+      std::vector<int> meta, list;
+      dev_free(c->gs_meta); c->gs_n = 0; c->gs_sparse = L.transfer_sparse();
+      if (build_gather_lists(L, c->nd, dim, c->cur_T, &meta, &list)) {
         if (dev_alloc(c, c->gs_meta, sizeof(int) * meta.size()) || dev_alloc(c, c->gs_list, sizeof(int) * list.size())) return 1;
         HIPCHK(c, hipMemcpy(c->gs_meta.p, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice));
         HIPCHK(c, hipMemcpy(c->gs_list.p, list.data(), sizeof(int) * list.size(), hipMemcpyHostToDevice));
-        c->gs_n = (int)n_img;
+        c->gs_n = (int)meta.size();
       }
     }
     c->cur_active = a; c->cur_jac = j; c->cur_dim = dim; c->have_sweep = false;
@@ -354,8 +273,8 @@ int gfh_debug_packed_layout(int nranks, int rank, int64_t n_total, int nd, const
   gfh_ctx c;
   c.nranks = nranks; c.rank = rank;
   if (set_geometry(&c, n_total, nd, dp)) { set_global_error(c.err); return 1; }
-  PackedLayout L;
-  if (compute_layout(&c, nd, na, jac, dim, sparse_ok != 0, &L)) { set_global_error(c.err); return 1; }
+  PackedLayout L; std::string lerr;
+  if (!compute_layout(nd, na, jac, dim, sparse_ok != 0, &L, &lerr)) { set_global_error(lerr); return 1; }
   uint64_t h = 1469598103934665603ull;
   auto mix = [&](const std::vector<int>& v) { for (int x : v) { h ^= (uint32_t)x; h *= 1099511628211ull; } h ^= 0xffu; h *= 1099511628211ull; };
   mix(L.nz_row); mix(L.nz_col); mix(L.inv); mix(L.owner);

@@ -109,6 +109,9 @@ inline int fused_waves_for(int n_active) {
   while (fw > 1 && fused_lds_bytes_for(n_active, fw) > 160L * 1024) fw /= 2;
   return fw;
 }
+// Waves per workgroup of gfh_k_chi2 (GFH_CW of the generated source): the fused kernel's while that exists, 8 beyond it.  Its launch
+// needs it, and so does k_gram_block, which adds sum r^2 in gfh_k_chi2's order.
+inline int chi2_waves_for(int n_active) { return n_active <= kFusedMaxActive ? fused_waves_for(n_active) : 8; }
 
 // ---- What the host must know about a translation unit to launch its kernels: each stated here once, used by the generator where it
 // writes the text and by the host where it builds the argument list.

@@ -13,7 +13,7 @@
 
 using namespace gfh;
 
-// End of every result-returning call: k_publish (kernels.hip) moves n doubles at `src` and the
+// End of every result-returning call: k_publish (kernels.hip; device/mailbox.hip) moves n doubles at `src` and the
 // kernels' status word into the pinned mailbox c->h_pinned and stores this call's sequence number
 // into the host flag; the host spins on the flag.  Everything queued on the stream before it has
 // finished when the flag flips (it is the last operation of the call).  hipStreamQuery is polled

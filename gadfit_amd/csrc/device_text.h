@@ -9,7 +9,7 @@ extern const char kPowLn[];            // pow_ln.hip: gfh_pow_ln (models with x 
 extern const char kParsBlock[];        // pars_block.hip: the parameter block as kernel argument or device array
 extern const char kUnseen[];           // unseen.hip: struct gfh_unseen, gfh_report_unseen (branching models; behind GFH_UNSEEN_CAP, unseen_report.h)
 extern const char kSweep[];            // sweep.hip: layout, GFH_ROBUST, gfh_store64, gfh_k_sweep, the hand-off macros
-extern const char kWaveSum[];          // wave_sum.hip: gfh_row_down, gfh_wave_sum (kernels.hip includes the same file)
+extern const char kWaveSum[];          // wave_sum.hip: gfh_row_down, gfh_wave_sum (gram.hip and jtv.hip include the same file)
 extern const char kFusedSweepGram[];   // fused_sweep_gram.hip: the fused STEP 1 + STEP 2 kernel in all its forms
 extern const char kChi2[];             // chi2.hip: gfh_k_chi2
 extern const char kOmega[];            // omega.hip: the tangent block of STEP 3, gfh_k_omega

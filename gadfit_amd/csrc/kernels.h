@@ -1,13 +1,12 @@
-// kernels.h -- launchers of the static (model-independent) kernels in kernels.hip
+// kernels.h -- launchers of the static (model-independent) kernels: gram.hip, assemble.hip, jtv.hip, kernels.hip
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <vector>
+#include "gram_image.h"   // gram_partial_stride(T): doubles per workgroup partial for T 16-row tiles
 
 namespace gfh {
 typedef long long i64;
-
-int gram_partial_stride(int T);   // doubles per workgroup partial for T 16-row tiles
 
 // one Gram launch as launch_gram notes it where it launches (gfh_debug_chain): kind 0 = k_gram_small<a>, 1 = k_gram<a>,
 // 2 = k_gram_block<a, b, sym> at the tiles (r0, c0)

@@ -243,7 +243,7 @@ int gfh::launch_model_chi2(gfh_ctx* c, int tail_mode, unsigned long long seq, in
   void* out = c->vec.p; void* hout = c->h_pinned; void* hflag = c->h_flag; void* cnt = c->status.as<char>() + 24;
   void* mesh = c->disp.mesh.p;
   void* ord = c->disp.order_on && c->disp.order_ready && takes_mesh_args(c) ? c->disp.gb_order.p : nullptr; void* cst = nullptr;
-  const int cw = c->cur->n_active <= kFusedMaxActive ? fused_waves_for(c->cur->n_active) : 8;     // GFH_CW of the generated source
+  const int cw = chi2_waves_for(c->cur->n_active);
   int grid; if (wsg_grid(c, c->cur->chi2, 64 * cw, c->n_gb, &grid)) return 1;
   void* pool = c->ws.wsg.p;
   std::vector<void*> args{&x, &y, &w, parg, &gs, &gn, &gd, &res, &part, &stp, &ax, &lda, &dfg, &nd, &out, &hout, &hflag, &cnt, &seq, &tail_mode};

@@ -6,8 +6,8 @@ rules are those of tests/gram_layout_cases.py (Case, expK, form_active, expect);
 GPU, that the oracle is a sound reference on every new input, that the expectations below cover what this text claims, and that
 every new translation unit compiles.
 
-THE DISPATCH RULES of the chain are restated here from the sources -- kernels.hip: launch_gram (which Gram instantiation, which
-blocks), launch.cpp: launch_gram_chain and active.cpp: prepare_active (source lists for k_gather_sum up to 2^18 entries of the packed
+THE DISPATCH RULES of the chain are restated here from the sources -- gram.hip: launch_gram (which Gram instantiation, which
+blocks), launch.cpp: launch_gram_chain and packed_layout.cpp: build_gather_lists (source lists for k_gather_sum up to 2^18 entries of the packed
 image, else k_assemble_sparse or k_assemble), passes.cpp: sweep_pass (the tail) and jtv_finish (one launch up to 4096 per-dataset
 entries) -- and the GPU tests hold Context.debug_chain(), which reports what the host launched, against expect_chain().
 
@@ -18,13 +18,13 @@ Part H: 48 and 49 datasets of the 128-parameter form: the pattern-only image on 
 from tests import gram_layout_cases as GL
 from tests.gram_layout_cases import Case
 
-GATHER_MAX = 1 << 18          # active.cpp: prepare_active, n_img <= 1 << 18
-JTV_FINISH_MAX = 4096         # passes.cpp: jtv_finish, n_datasets * na <= 4096 (kernels.hip: k_jtv_finish, V[4096])
+GATHER_MAX = 1 << 18          # packed_layout.cpp: build_gather_lists, n_img <= 1 << 18
+JTV_FINISH_MAX = 4096         # passes.cpp: jtv_finish, n_datasets * na <= 4096 (jtv.hip: k_jtv_finish, V[4096])
 
 
 # ---- the dispatch rules of the chain ----------------------------------------------------------------------------------------------
 def gram_launches(na):
-    """kernels.hip: launch_gram, in launch order"""
+    """gram.hip: launch_gram, in launch order"""
     if na <= 8:
         return ['small<%d>' % na]
     T = GL.tiles(na)
@@ -41,7 +41,7 @@ def gram_launches(na):
 
 
 def image_entries(c, sparse_ok=True):
-    """doubles of the packed image [J^T J or its pattern | J^T r | chi2] (active.cpp: PackedLayout::packed_n)"""
+    """doubles of the packed image [J^T J or its pattern | J^T r | chi2] (packed_layout.h: PackedLayout::packed_n)"""
     if GL.pattern_only(c.nd, c.active, c.is_global, sparse_ok):
         return GL.pattern_nnz(c.nd, c.active, c.is_global) + c.dim + 1
     return c.dim * c.dim + c.dim + 1
@@ -61,7 +61,7 @@ def expect_chain(c, tail_on=True, sparse_ok=True, fused_on=True, merge_small=Tru
 
 
 def partial_stride(T):
-    """kernels.hip: gram_partial_stride"""
+    """gram_image.h: gram_partial_stride"""
     return (T * (T + 1) // 2 * 256 + 16 * T + 1 + 3) & ~3
 
 

@@ -7,7 +7,7 @@ below cover what this text claims, and that every translation unit compiles.  Ev
 
 THE DISPATCH RULES are restated here from the sources -- data.cpp: build_layout (padding, gram blocks), passes.cpp: sweep_pass (small,
 tail, pattern-only), launch.cpp (tail_one_workgroup_per_cu, tail mode), active.cpp (get_kernels: the parameter block by value up to
-480 doubles; compute_layout: the pattern) and codegen.h (fused_waves_for and the LDS of a workgroup) -- and the GPU tests hold
+480 doubles), packed_layout.cpp (compute_layout: the pattern) and codegen.h (fused_waves_for and the LDS of a workgroup) -- and the GPU tests hold
 Context.debug_layout() against expect(): a threshold that moves fails there instead of moving a case off the path it is here for.
 
 Part A: one dataset of 1501 points at the first active count of every form and at one below every full tile.
@@ -189,7 +189,7 @@ def jacobian_indices(nd, active, is_global):
 
 
 def pattern_nnz(nd, active, is_global):
-    """(row <= col) pairs of columns that some dataset couples (active.cpp: compute_layout)"""
+    """(row <= col) pairs of columns that some dataset couples (packed_layout.cpp: compute_layout)"""
     jac, dim = jacobian_indices(nd, active, is_global)
     keys = set()
     for d in range(nd):
@@ -200,7 +200,7 @@ def pattern_nnz(nd, active, is_global):
 
 
 def pattern_only(nd, active, is_global, sparse_ok=True):
-    """does the image travel as its pattern (active.cpp: compute_layout, transfer_sparse)?"""
+    """does the image travel as its pattern (packed_layout.cpp: compute_layout, transfer_sparse)?"""
     dim = jacobian_indices(nd, active, is_global)[1]
     if dim * dim * nd <= SMALL_MAX or not sparse_ok or nd < 2:
         return False

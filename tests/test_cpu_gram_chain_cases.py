@@ -55,7 +55,7 @@ def test_the_oracle_is_a_sound_reference_on_every_new_input():
 
 
 def test_gram_launches_by_hand():
-    """kernels.hip: launch_gram, spelled out at the counts of parts E and F"""
+    """gram.hip: launch_gram, spelled out at the counts of parts E and F"""
     assert [CH.gram_launches(na) for na in range(1, 9)] == [['small<%d>' % na] for na in range(1, 9)]
     assert [CH.gram_launches(na) for na in (9, 16, 17, 32, 33, 48, 49, 64)] == [['gram<%d>' % t] for t in (1, 1, 2, 2, 3, 3, 4, 4)]
     assert CH.gram_launches(65) == CH.gram_launches(80) == ['block<5,5,true>@(0,0)']
@@ -179,7 +179,7 @@ def _block_origins(every):
 
 
 def test_the_librarys_own_layout_agrees_with_the_case_module():
-    """gfh_debug_packed_layout derives the gram workgroups, the pattern and the length of the packed image from data.cpp and active.cpp
+    """gfh_debug_packed_layout derives the gram workgroups, the pattern and the length of the packed image from data.cpp and packed_layout.cpp
     themselves: the restated rules agree on every case, with and without the pattern"""
     for c in CH.part_e() + CH.f_t7() + CH.f_small() + CH.part_g() + CH.part_h():
         jac, dim = GL.jacobian_indices(c.nd, c.active, c.is_global)

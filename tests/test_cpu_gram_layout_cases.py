@@ -246,7 +246,7 @@ def test_every_unit_compiles_for_gfx950():
 
 def test_the_librarys_own_layout_agrees_with_the_case_module():
     """gfh_debug_packed_layout derives, without a GPU, the gram workgroups, the datasets held and whether the image is pattern-only from
-    data.cpp and active.cpp themselves: the case module's restatement of those rules agrees on every case and every pseudo-rank"""
+    data.cpp and packed_layout.cpp themselves: the case module's restatement of those rules agrees on every case and every pseudo-rank"""
     todo = [(c, 1, 0) for c in GL.all_cases()] + [(c, n, r) for c, n in GL.part_c() for r in range(n)]
     for c, nranks, r in todo:
         jac, dim = GL.jacobian_indices(c.nd, c.active, c.is_global)

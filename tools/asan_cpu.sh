@@ -15,7 +15,9 @@ RT=$(dirname $(find /opt/rocm/lib/llvm -name "libclang_rt.asan-x86_64.so" | head
 for src in gadfit_amd/csrc/*.cpp; do f=$(basename $src .cpp)
   /opt/rocm/bin/hipcc -O1 -g -std=c++17 -fPIC --offload-arch=gfx950 -fvisibility=hidden -fsanitize=address -shared-libasan -fno-omit-frame-pointer -w -c gadfit_amd/csrc/$f.cpp -o $T/$f.o
 done
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -fvisibility=hidden --offload-arch=gfx950 -w -c gadfit_amd/csrc/kernels.hip -o $T/kernels.o
+for src in gadfit_amd/csrc/*.hip; do f=$(basename $src .hip)
+  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -fvisibility=hidden --offload-arch=gfx950 -w -c gadfit_amd/csrc/$f.hip -o $T/$f.o
+done
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -fsanitize=address -shared-libasan -o $T/lib.so $T/*.o -L/opt/rocm/lib -lhiprtc -lrccl -pthread -Wl,-rpath,/opt/rocm/lib -Wl,--version-script=gadfit_amd/csrc/exports.map
 cp gadfit_amd/lib/libgadfit_hip.so $T/lib.bak; cp $T/lib.so gadfit_amd/lib/libgadfit_hip.so
 ASAN_OPTIONS=detect_leaks=0:verify_asan_link_order=0 LD_PRELOAD=$RT/libclang_rt.asan-x86_64.so LD_LIBRARY_PATH=$RT \

@@ -1,6 +1,6 @@
 // Why does k_assemble take ~29 us for dim = 259, 64 datasets?  Times the library's launcher on synthetic tables
 // and three ablations of the same access pattern.  build: hipcc -O3 --offload-arch=gfx950 -I../../gadfit_amd/csrc
-//   assemble_probe.hip ../../gadfit_amd/csrc/kernels.hip -o assemble_probe
+//   assemble_probe.hip ../../gadfit_amd/csrc/assemble.hip -o assemble_probe
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>

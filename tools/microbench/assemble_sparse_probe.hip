@@ -1,7 +1,7 @@
 // Where do k_assemble_sparse's ~24 us at config 3 (dim 259, 64 datasets, 1.4 k pattern entries) go?  Times the library's launcher on a
 // synthetic block-arrow pattern, the same with the dataset loop cut to one dataset (the entries that walk all datasets then cost one
 // term), and an empty kernel of the same grid.  build: hipcc -O3 --offload-arch=gfx950 -I../../gadfit_amd/csrc
-//   assemble_sparse_probe.hip ../../gadfit_amd/csrc/kernels.hip -o assemble_sparse_probe
+//   assemble_sparse_probe.hip ../../gadfit_amd/csrc/assemble.hip -o assemble_sparse_probe
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
