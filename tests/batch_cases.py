@@ -1,5 +1,6 @@
-"""The inputs of tests/test_gpu_batch_shapes.py and the rule that selects which of them a device fit may be held against
-(tests/test_cpu_batch_cases.py runs the rule and the compilations without a GPU).  Everything here is deterministic and needs no GPU.
+"""The inputs of tests/batch_form_suite.py and tests/test_gpu_batch_shapes.py that the three forms share, and the rule that selects which inputs a device fit may be
+held against (tests/test_cpu_batch_cases.py runs the rule and the compilations without a GPU).  What differs per form -- the lengths
+of Part 1 among it -- is the table of tests/batch_form_cases.py.  Everything here is deterministic and needs no GPU.
 
 THE SELECTION RULE.  Past convergence, accept / reject in Levenberg-Marquardt is decided by rounding.  A fit is
 compared with the device only if the oracle agrees with itself on it:
@@ -15,7 +16,7 @@ compared with the device only if the oracle agrees with itself on it:
 The rule is evaluated by the oracle alone; the device's results never enter it.  Cases that fail it leave the fit comparisons only
 (their first pass is still compared), and each part has a cap on how many may.
 
-Part 1: model_exp2, lengths at the edges of a wave (n = na, n < 64, 64 k - 1, 64 k, 64 k + 1, and rows enough that the row loop dominates).
+Part 1: model_exp2, spectrum_n(n, s) with the lengths n at the edges of each form's row of lanes (tests/batch_form_cases.py).
 Part 2: model_exp4, every active count 1 ... 8, lists in the caller's order.
 Part 3: the whole operator set: p[0] e_0(p, x) + ... + p[4] e_4(p, x) with the random expressions of tests/test_gpu_random_models.py,
 and one written model for the three operators those expressions never draw (erf, a bare abs, unary minus)."""
@@ -27,7 +28,7 @@ from gadfit_amd import ad
 from gadfit_amd.ad import trace_model
 from oracle import binding as orc
 from tests import models as M
-from tests.test_gpu_batch import COUNTS, SCENARIOS, TOL_PASS, spectrum4, start_of
+from tests.batch_common import COUNTS, TOL_PASS, spectrum4
 from tests.test_gpu_random_models import NP_, _rand_expr
 
 SELF_TOL = 1e-12
@@ -69,16 +70,7 @@ class Batch:
         return self.off[:k + 1], self.x[:e], self.y[:e], self.w[:e]
 
 
-# ---- Part 1: spectrum lengths at the wave's edges (model_exp2) -------------------------------------------------------------------
-LENGTHS = (4, 5, 6, 8, 17, 31, 63, 64, 65, 127, 128, 129, 191, 192, 193, 1000, 4097, 20001)
-PART1_ACTIVE = [0, 1, 2, 3]
-PART1_SCENARIOS = ('a', 'b', 'c')
-PART1_ONE_ACTIVE = [1]
-PART1_ONE_SCENARIOS = ('a', 'b')
-PART1_LARGE_MAX_N = 193            # Part 4 tiles the spectra up to this length
-PART1_LARGE_FITS = 2 ** 17 + 3
-
-
+# ---- Part 1: the spectra of model_exp2 (their lengths per form: tests/batch_form_cases.py) ------------------------------------------
 def spectrum_n(n, s):
     u = (M.splitmix64(4, M.SEED + 3000 * (s + 1) + n) >> np.uint64(11)).astype(np.float64) / 9007199254740992.0
     truth = M.EXP2_TRUTH * (0.8 + 0.4 * u)
@@ -86,42 +78,7 @@ def spectrum_n(n, s):
     return truth, x, y, 1.0 / sigma, sigma
 
 
-def part1_order():
-    """(n, s) of the 108 spectra in batch order: per s the lengths from both ends inwards (4, 20001, 5, 4097, 6, 1000, ...), so that
-    short spectra lie between long ones and long ones between short ones"""
-    per_s = []
-    for i in range(len(LENGTHS) // 2):
-        per_s += [LENGTHS[i], LENGTHS[-1 - i]]
-    return [(n, s) for s in range(6) for n in per_s]
-
-
-@functools.lru_cache(maxsize=None)
-def part1():
-    """(tape, order [(n, s)], truths [108][4], Batch)"""
-    order = part1_order()
-    sp = [spectrum_n(n, s) for n, s in order]
-    return trace_model(M.model_exp2, 4), order, np.array([it[0] for it in sp]), Batch([it[1:4] for it in sp])
-
-
-def part1_starts(off, active=PART1_ACTIVE):
-    """only the active parameters are moved off truth"""
-    truths = part1()[2]
-    starts = truths.copy()
-    starts[:, active] = np.array([start_of(t, off) for t in truths])[:, active]
-    return starts
-
-
-@functools.lru_cache(maxsize=None)
-def part1_selection(name, one_active=False):
-    """the rule over the 108 spectra under a scenario of test_gpu_batch.py: [(kept, oracle result, self-difference)]"""
-    tape, _, _, batch = part1()
-    active = PART1_ONE_ACTIVE if one_active else PART1_ACTIVE
-    off, kw = SCENARIOS[name]
-    starts = part1_starts(off, active)
-    return [select(tape, *batch.items[b], starts[b], active, kw) for b in range(len(batch.items))]
-
-
-# ---- Part 2: every active count, in the caller's order (model_exp4, the 48 spectra of test_gpu_batch.spectrum4) ------------------
+# ---- Part 2: every active count, in the caller's order (model_exp4, the 48 spectra of batch_common.spectrum4) -------------------
 EXP4_SETS = ([3], [0, 1], [6, 1, 4], [0, 2, 4, 6], [7, 0, 3, 2, 5], [0, 1, 2, 3, 4, 5], [1, 2, 3, 4, 5, 6, 7], [0, 1, 2, 3, 4, 5, 6, 7])
 # under 'short' the amplitudes alone ([0, 2, 4, 6]) are a linear fit: it converges in one step and then hangs on rounding (19 of its 48
 # fits fail the rule), so the four-parameter set of 'short' is another one (tests/test_cpu_batch_cases.py holds the rule over it)
@@ -245,15 +202,15 @@ def part3_selection(seed, name):
 RANDOM_POW_SEED = 5
 
 
-def batch_units():
-    """[(tape, active list)] under the default switches; RANDOM_POW_SEED's unit is asked for once more under GADFIT_HIP_FAST_DIV=0"""
-    units = [(part1()[0], PART1_ACTIVE), (part1()[0], PART1_ONE_ACTIVE)]
-    seen = set()
-    for a in list(EXP4_SETS) + [EXP4_SHORT_FOUR] + [o[0] for pair in EXP4_ORDER.values() for o in pair]:
-        if tuple(a) not in seen:
-            seen.add(tuple(a))
-            units.append((part2()[0], list(a)))
-    for seed in OPERATOR_SEEDS:
-        tape, active = part3(seed)[:2]
-        units.append((tape, active))
-    return units
+def part2_units():
+    """[(tape, active list)] of Part 2: the ten active lists, whichever form runs them"""
+    seen = []
+    for a in [a for name in sorted(EXP4_ARGS) for a in exp4_sets(name)] + [o[0] for pair in EXP4_ORDER.values() for o in pair]:
+        if list(a) not in seen:
+            seen.append(list(a))
+    return [(part2()[0], a) for a in seen]
+
+
+def operator_units():
+    """[(tape, active list)] of Part 3 under the default switches; RANDOM_POW_SEED's unit is asked for once more under GADFIT_HIP_FAST_DIV=0"""
+    return [part3(seed)[:2] for seed in OPERATOR_SEEDS]

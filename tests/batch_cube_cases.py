@@ -1,6 +1,6 @@
 """The inputs of tests/test_gpu_batch_cube.py and tests/test_cpu_batch_cube.py: batches as data cubes (gfh_set_batch_cube) -- every
 spectrum on one abscissa grid, samples in float64, float32 or uint16, the weights formed from y on the device.  Everything here is
-deterministic and needs no GPU; the scenarios, the bounds and the selection rule (select) are those of tests/test_gpu_batch.py and
+deterministic and needs no GPU; the scenarios, the bounds and the selection rule (select) are those of tests/batch_common.py and
 tests/batch_cases.py, imported, not restated.
 
 COUNTS.  For a length n one grid x_i = 0.5 + 99.5 (i + 0.5) / n and six spectra s = 0 ... 5 of model_exp2:
@@ -27,7 +27,7 @@ import numpy as np
 from gadfit_amd.ad import trace_model
 from tests import batch_cases as BC
 from tests import models as M
-from tests.test_gpu_batch import SCENARIOS, start_of
+from tests.batch_common import SCENARIOS, start_of
 
 CUBE_TRUTH = np.array([3000.0, 2.5, 1500.0, 15.0])
 CUBE_SEED = 3000000
@@ -155,7 +155,7 @@ def oracle_selection(y_index, error_type, name):
 
 def cube_units():
     """[(lanes, y_type number, error_type)]: every cube translation unit of model_exp2 with ACTIVE that the GPU tests ask for -- all 15
-    loads at each of the three lane forms (the ragged units of the same set are tests/batch_cases.py's and its lane modules')"""
+    loads at each of the three lane forms (the ragged units of the same set are tests/batch_form_cases.py's)"""
     return [(lanes, yt, et) for lanes in (64, 16, 256) for yt in range(3) for et in ERROR_TYPES]
 
 

@@ -1,53 +1,58 @@
-"""What tests/test_gpu_batch_shapes.py rests on, shown without a GPU: the selection rule of tests/batch_cases.py run by the oracle
-alone over every case list (each part's cap on dropped cases holds), each part covering what it claims (the exits, rejections and
-STEP 3 it is there for), and every batch translation unit the GPU tests ask for compiling for gfx950 on a compile-only context."""
+"""What the three forms' GPU modules (tests/batch_form_suite.py) rest on, shown without a GPU: the selection rule of
+tests/batch_cases.py run by the oracle alone over every case list (Part 1 of every form of tests/batch_form_cases.py, Parts 2 and 3; each part's cap on dropped cases holds),
+each part covering what it claims (the exits, rejections and STEP 3 it is there for), and every batch translation unit the GPU tests
+ask for at 64 lanes compiling for gfx950 on a compile-only context (tests/test_cpu_batch_rows.py and tests/test_cpu_batch_wg.py
+compile the other forms')."""
 import numpy as np
 import pytest
 
 from gadfit_amd import _lib
 from tests import batch_cases as BC
+from tests import batch_form_cases as FC
 
 
 def _counts(sel):
     return [s[1][0] for s in sel]          # (iterations, n_sweeps, n_chi2, n_omega, exit_reason) per fit
 
 
-def test_part1_lengths_none_dropped_and_all_exits_met():
-    """6 spectra x 18 lengths x scenarios a, b, c: the oracle agrees with itself on all 324 fits; exits 0, 2 and 7, rejections and
-    STEP 3 occur; the lengths cover n = na, n < 64, and one below / at / one above 64, 128 and 192"""
-    order = BC.part1_order()
-    assert len(order) == 108 and sorted(set(n for n, _ in order)) == sorted(BC.LENGTHS)
-    assert min(BC.LENGTHS) == len(BC.PART1_ACTIVE) and {63, 64, 65, 127, 128, 129, 191, 192, 193} <= set(BC.LENGTHS)
-    n = [o[0] for o in order]          # the order puts a long spectrum between two short ones and a short one between two long ones
-    assert any(n[k - 1] < 64 and n[k] > 4096 and n[k + 1] < 64 for k in range(1, 107))
-    assert any(n[k - 1] > 4096 and n[k] < 64 and n[k + 1] > 4096 for k in range(1, 107))
+@pytest.mark.parametrize('form', FC.FORMS, ids=lambda f: str(f.lanes))
+def test_part1_rule_counts(form):
+    """6 spectra x the form's lengths.  With four active parameters under (a), (b), (c) the oracle agrees with itself on every fit
+    (none dropped); exits 0, 2 and 7, rejections and STEP 3 occur; the lengths start at n = na and hold the form's edges, and the
+    order puts short spectra beside long ones.
+    With active = [1] a fit is at convergence within a step or two and some then make a chi2 comparison closer than MARGIN (the third
+    condition of the rule drops them, and nothing else does): at 64 lanes every seventh under (b) (4e-16 ... 1e-13) -- no scenario
+    loses more than a quarter of its 108; at 16 lanes 2 (a: both n = 4) and 6 (b: n = 17, 63, 80, 80, 257, 257), at most 5 % of the
+    228; at 256 lanes 2 under (a) (n = 4, s = 1 and 4), at most 3 of the 138 ((b) fails the rule on 23 and is left out).  Every
+    length keeps form.one_kept_per_length of its six fits in each scenario, and a dropped fit's first pass is still compared (the
+    pass test of the GPU module takes every spectrum)."""
+    order = FC.order(form)
+    total = form.spectra          # (108, 114, 138)
+    assert len(order) == total == FC.SAMPLES * len(form.lengths) == len(FC.batch(form)[3].items) and sorted(set(n for n, _ in order)) == sorted(form.lengths)
+    assert min(form.lengths) == len(FC.ACTIVE) and form.edges <= set(form.lengths)
+    assert form.short_beside_long([o[0] for o in order])
     exits, rejected, omega, worst = set(), 0, 0, 0.0
-    for name in BC.PART1_SCENARIOS:
-        sel = BC.part1_selection(name)
-        assert [b for b, s in enumerate(sel) if not s[0]] == [], name          # the cap of this part: none dropped
+    for name in FC.FIT_SCENARIOS:
+        sel = FC.selection(form, name)
+        assert [b for b, s in enumerate(sel) if not s[0]] == [], name          # none dropped
         worst = max([worst] + [s[2] for s in sel])
         for it, _, n_chi2, n_omega, ex in _counts(sel):
             exits.add(ex); rejected += n_chi2 != it + 1; omega += n_omega > 0
-    print('part 1: worst self-difference of the parameters %.2e, fits with a rejection %d, with STEP 3 %d' % (worst, rejected, omega))
+    print('%d lanes: worst self-difference of the parameters %.2e, fits with a rejection %d, with STEP 3 %d' % (form.lanes, worst, rejected, omega))
     assert exits == {0, 2, 7} and rejected > 0 and omega > 0
-
-
-def test_part1_one_active_parameter_keeps_every_length():
-    """active = [1] under (a) and (b): a one-parameter fit is at convergence within a step or two, and under (b) every seventh fit then
-    makes a chi2 comparison closer than MARGIN (4e-16 ... 1e-13: the third condition of the rule drops it).  No cap is
-    given for this list; what it is there for is every length of Part 1 through the 1 x 1 instance of the kernels, so: every length
-    keeps at least one fit in each scenario, and no scenario loses more than a quarter of its 108 fits."""
-    order = BC.part1_order()
-    exits = set()
-    for name in BC.PART1_ONE_SCENARIOS:
-        sel = BC.part1_selection(name, True)
-        kept = [b for b, s in enumerate(sel) if s[0]]
-        print('part 1, one active (%s): %d of 108 dropped' % (name, 108 - len(kept)))
-        assert set(order[b][0] for b in kept) == set(BC.LENGTHS), name
-        assert 108 - len(kept) <= 27, name
+    dropped, exits = [], set()
+    for name in form.one_scenarios:
+        sel = FC.selection(form, name, True)
+        lost = [order[b] for b, s in enumerate(sel) if not s[0]]
+        print('%d lanes, one active (%s): %d of %d dropped: (n, s) = %s' % (form.lanes, name, len(lost), total, lost))
+        dropped.append(len(lost))
+        for length in form.lengths:
+            assert sum(s[0] for b, s in enumerate(sel) if order[b][0] == length) >= form.one_kept_per_length, (name, length)
         assert all(s[2] <= BC.SELF_TOL and s[3] <= BC.MARGIN for s in sel if not s[0]), name          # all of them by the margin alone
-        exits |= set(sel[b][1][0][4] for b in kept)
-    assert {0, 2, 7} <= exits
+        exits |= set(s[1][0][4] for s in sel if s[0])
+    assert form.one_cap_each is None or max(dropped) <= form.one_cap_each
+    assert form.one_cap_total is None or sum(dropped) <= form.one_cap_total
+    assert exits >= ({0, 2, 7} if 'b' in form.one_scenarios else {2})          # (a) converges; the other exits are (b)'s
 
 
 def test_part2_every_active_count_none_dropped():
@@ -140,7 +145,7 @@ def test_part3_fits_that_accept_a_step_inside_rounding_are_dropped():
 
 
 def test_every_batch_unit_compiles_for_gfx950(monkeypatch):
-    units = BC.batch_units()
+    units = FC.units(FC.WAVE) + BC.operator_units()
     assert len(units) + 1 < 60
     c = _lib.Context(-1)
     try:

@@ -1,7 +1,7 @@
-"""What tests/test_gpu_batch_wg.py rests on, shown without a GPU: the selection rule of tests/batch_cases.py run by the oracle alone
-over Part W1 of tests/batch_wg_cases.py, gfh_set_batch_lanes taking 256 and the refusals holding under it, the auto rule never
-returning 256, the 256-lane form of every batch translation unit the GPU tests ask for compiling for gfx950 on a compile-only context,
-and profiles/batch_workgroup.json holding the cells it was asked for with the two must-win cells won."""
+"""What tests/test_gpu_batch_wg.py rests on, shown without a GPU (the selection rule over its spectra is run
+by tests/test_cpu_batch_cases.py): gfh_set_batch_lanes taking 256 and the refusals holding under it, the auto rule never returning
+256, the 256-lane form of every batch translation unit the GPU tests ask for compiling for gfx950 on a compile-only context, and
+profiles/batch_workgroup.json holding the cells it was asked for with the two must-win cells won."""
 import json
 import os
 
@@ -9,46 +9,24 @@ import numpy as np
 import pytest
 
 from gadfit_amd import _lib
-from tests import batch_row_cases as RC
-from tests import batch_wg_cases as WC
+from tests import batch_form_cases as FC
+from tests import batch_records
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def test_w1_rule_counts():
-    """6 spectra x 23 lengths: with four active parameters the oracle agrees with itself on all 3 x 138 fits; with one active
-    parameter under (a) 2 fail the rule (n = 4, s = 1 and 4) by its margin -- at most 3 of the 138 may, every length keeps at least
-    four of its six fits, and a dropped fit's first pass is still compared (the pass test of the GPU module takes all 138)."""
-    order = WC.w1_order()
-    assert len(order) == 138 and sorted(set(n for n, _ in order)) == sorted(WC.LENGTHS) and len(WC.LENGTHS) == 23
-    assert min(WC.LENGTHS) == len(WC.ACTIVE)
-    assert {64 * k + e for k in (1, 2, 3, 4, 8, 12) for e in (-1, 0, 1)} <= set(WC.LENGTHS)
-    n = [o[0] for o in order]          # short spectra lie beside long ones
-    assert any(n[k] <= 64 and n[k + 1] > 1024 for k in range(137))
-    for name in WC.FIT_SCENARIOS:
-        sel = WC.w1_selection(name)
-        assert [b for b, s in enumerate(sel) if not s[0]] == [], name          # none of the 414 dropped
-    for name in WC.ONE_SCENARIOS:
-        sel = WC.w1_selection(name, True)
-        lost = [order[b] for b, s in enumerate(sel) if not s[0]]
-        print('W1, one active (%s): %d of 138 dropped: (n, s) = %s' % (name, len(lost), lost))
-        assert len(lost) <= WC.ONE_ACTIVE_MAX_DROPPED
-        for length in WC.LENGTHS:
-            assert sum(s[0] for b, s in enumerate(sel) if order[b][0] == length) >= 4, (name, length)
 
 
 def test_set_batch_lanes_takes_256_and_the_refusals_hold_under_it():
     c = _lib.Context(-1)
     try:
-        tape = WC.w1()[0]
+        tape = FC.batch(FC.WORKGROUP)[0]
         c.set_model(tape)
         c.set_batch_lanes(256)
         assert c.batch_lanes_used() == 0          # a setting, not a launch
-        src = c.batch_source(WC.ACTIVE)
+        src = c.batch_source(FC.ACTIVE)
         assert '#define GFH_BLANES 256\n' in src and '__syncthreads' in src
         with pytest.raises(_lib.GadfitHipError, match=r'gfh_set_batch_lanes: 8 lanes per fit are not built'):
             c.set_batch_lanes(8)
-        assert '#define GFH_BLANES 256\n' in c.batch_source(WC.ACTIVE)          # a refused value leaves the setting
+        assert '#define GFH_BLANES 256\n' in c.batch_source(FC.ACTIVE)          # a refused value leaves the setting
         with pytest.raises(_lib.GadfitHipError, match=r'256'):                 # ... and the refusal names the value that is built
             c.set_batch_lanes(32)
         # every refusal of a batch holds in the workgroup form as in the others
@@ -58,7 +36,7 @@ def test_set_batch_lanes_takes_256_and_the_refusals_hold_under_it():
         with pytest.raises(_lib.GadfitHipError, match='no GPU'):
             c.set_batch_data([0, 3, 20], x, x, x)
         with pytest.raises(_lib.GadfitHipError, match='More independent fitting parameters than data points'):
-            c.fit_batch(np.ones((2, 4)), WC.ACTIVE, max_iter=1)
+            c.fit_batch(np.ones((2, 4)), FC.ACTIVE, max_iter=1)
         with pytest.raises(_lib.GadfitHipError, match='max_iter is required'):
             c.fit_batch(np.ones((2, 4)), [0, 1], lanes_per_fit=256)
         with pytest.raises(_lib.GadfitHipError, match='8 lanes per fit are not built'):
@@ -80,18 +58,18 @@ def test_auto_never_returns_256():
     # ... and under auto a context that holds a long batch acts for 64
     c = _lib.Context(-1)
     try:
-        c.set_model(WC.w1()[0])
+        c.set_model(FC.batch(FC.WORKGROUP)[0])
         c.set_batch_lanes(0)
         x = np.linspace(0.5, 9.5, 8 + 65536)
         with pytest.raises(_lib.GadfitHipError, match='no GPU'):
             c.set_batch_data([0, 8, 8 + 65536], x, x, x)
-        assert '#define GFH_BLANES 64\n' in c.batch_source(WC.ACTIVE)
+        assert '#define GFH_BLANES 64\n' in c.batch_source(FC.ACTIVE)
     finally:
         c.close()
 
 
 def test_the_workgroup_form_of_every_unit_compiles_for_gfx950():
-    units = WC.wg_units()
+    units = FC.units(FC.WORKGROUP)
     assert len(units) == 2 + 10
     c = _lib.Context(-1)
     try:
@@ -107,13 +85,13 @@ def test_the_workgroup_form_of_every_unit_compiles_for_gfx950():
 def test_the_record_holds_the_cells_and_the_two_must_win_cells_are_won():
     """profiles/batch_workgroup.json (tools/bench_batch.py --workgroup): both forms of one run per (model, fits per launch, points per
     spectrum), every cell of the grid up to 2^30 points in total, and the 256-lane form faster than the 64-lane form of the same run
-    by more than the two forms' min-max spread (batch_row_cases.row_wins) at 256 fits of 16384 and of 65536 points, both models.
+    by more than the two forms' min-max spread (batch_records.row_wins) at 256 fits of 16384 and of 65536 points, both models.
     The compiler's figures of the 256-lane kernels: no scratch."""
     rec = json.load(open(os.path.join(ROOT, 'profiles', 'batch_workgroup.json')))
     for model, na in (('gauss4', 4), ('exp4', 8)):
         for fits in (64, 256, 1024, 16384):
             for points in (1000, 4096, 16384, 65536):
-                m = WC.cell(rec, model, fits, points)
+                m = batch_records.cell(rec, model, fits, points)
                 if fits * points > 2 ** 30:
                     assert m is None, (model, fits, points)
                     continue
@@ -122,10 +100,10 @@ def test_the_record_holds_the_cells_and_the_two_must_win_cells_are_won():
                 for lanes in ('64', '256'):
                     e = m['lanes'][lanes]
                     assert 0.0 < e['device_ms_min'] <= e['device_ms'] <= e['device_ms_max'] and e['finite']
-                assert m['workgroup_wins'] == bool(RC.row_wins(m['lanes']['256'], m['lanes']['64']))
-    for model, fits, points in WC.MUST_WIN:
-        m = WC.cell(rec, model, fits, points)
-        assert RC.row_wins(m['lanes']['256'], m['lanes']['64']), (model, fits, points, m['lanes'])
+                assert m['workgroup_wins'] == bool(batch_records.row_wins(m['lanes']['256'], m['lanes']['64']))
+    for model, fits, points in batch_records.MUST_WIN:
+        m = batch_records.cell(rec, model, fits, points)
+        assert batch_records.row_wins(m['lanes']['256'], m['lanes']['64']), (model, fits, points, m['lanes'])
     regs = rec['registers']
     for unit in ('gauss4', 'exp4', 'exp2'):
         for kernel in ('gfh_k_fit_batch', 'gfh_k_batch_pass'):

@@ -8,10 +8,7 @@ additions): they cover early exits at different iterations, rejections, retrials
 fits sits on a decision that rounding alone takes.  (max_iter = 8 or a rel_error exit would let the fits run past convergence, where
 accept / reject is decided by rounding: SURVEY section 4.)
 
-GADFIT_BATCH_OBSERVE=<file>: the observed maxima are written there as JSON (tools/bench_batch.py puts them into profiles/batch_fits.json)."""
-import json
-import os
-
+The scenarios, the bounds and the record of observed maxima (GADFIT_BATCH_OBSERVE) are in tests/batch_common.py."""
 import numpy as np
 import pytest
 
@@ -19,36 +16,12 @@ from gadfit_amd import _lib
 from gadfit_amd.ad import exp, trace_model
 from oracle import binding as orc
 from tests import models as M
+from tests.batch_common import COUNTS, SCENARIOS, TOL_CHI2, TOL_LAMBDA, TOL_PARS, TOL_PASS, observe, same_bits, spectrum4, start_of
 
 pytestmark = pytest.mark.gpu
 
 B = 512
 ACTIVE = [0, 1, 2, 3]
-TOL_PASS = 2e-13          # the project's per-pass bound (tests/test_gpu_parity.py)
-TOL_LAMBDA = 1e-14        # the same decisions give the same products of lam_up / lam_down
-# fitted parameters and chi2: north_star's bound is 1e-10; observed 2.0e-13 and 1.7e-13 (profiles/batch_fits.json, observed_maxima_against_the_oracle), and the oracle
-# against itself with its point sums in another order differs by 1.7e-13 on these inputs, so 10 x observed would sit at what a
-# reordered sum does: the assertion stays at 3e-12
-TOL_PARS = 3e-12
-TOL_CHI2 = 3e-12
-SCENARIOS = {
-    'a': (0.05, dict(lambda_=1.0, max_iter=50, chi2_rel=1e-6)),
-    'b': (0.4, dict(lambda_=1e-6, max_iter=4)),
-    'c': (0.4, dict(lambda_=1e-6, accth=0.9, max_iter=4)),
-    'd': (0.4, dict(lambda_=1e-6, max_iter=40, chi2_rel=1e-4)),
-}
-COUNTS = ('iterations', 'n_sweeps', 'n_chi2', 'n_omega', 'exit_reason')
-_OBSERVED = {}
-
-
-def _observe(**kw):
-    for k, v in kw.items():
-        _OBSERVED[k] = max(_OBSERVED.get(k, 0.0), float(v))
-        print('observed %s = %.3e' % (k, float(v)))
-    path = os.environ.get('GADFIT_BATCH_OBSERVE')
-    if path:
-        with open(path, 'w') as fh:
-            json.dump(_OBSERVED, fh, indent=1, sort_keys=True)
 
 
 def spectrum(b):
@@ -56,10 +29,6 @@ def spectrum(b):
     truth = M.EXP2_TRUTH * (0.8 + 0.4 * u)
     x, y, s = M.make_single(M.exp2_numpy, truth, 64 + (37 * b) % 449, 0.5, 100.0, seed=M.SEED + b)
     return truth, x, y, 1.0 / s, s
-
-
-def start_of(truth, off):
-    return truth * np.where(np.arange(4) % 2 == 0, 1.0 + off, 1.0 - off)
 
 
 class Spectra:
@@ -96,14 +65,6 @@ def S():
     s.ctx.close()
 
 
-def _same_bits(p, r, p0, r0):
-    assert np.array_equal(p, p0)
-    for f in COUNTS + ('dof',):
-        assert np.array_equal(r[f], r0[f]), f
-    assert np.array_equal(r['lambda_'].view(np.uint64), r0['lambda_'].view(np.uint64))
-    assert np.array_equal(r['chi2'].view(np.uint64), r0['chi2'].view(np.uint64))
-
-
 def test_one_pass_against_the_oracle(S):
     """gfh_batch_pass at the 5 %-off start values: every fit's J^T J, J^T r and chi2 against OracleProblem.sweep."""
     starts = S.starts(0.05)
@@ -118,7 +79,7 @@ def test_one_pass_against_the_oracle(S):
         worst['JTres'] = max(worst['JTres'], np.max(np.abs(JTr[b] - JTr0) / (np.sqrt(np.diag(JTJ0) * chi0) + 1e-300)))
         worst['chi2'] = max(worst['chi2'], abs(chi2[b] - chi0) / chi0)
         assert np.array_equal(JTJ[b], JTJ[b].T)
-    _observe(pass_JTJ=worst['JTJ'], pass_JTres=worst['JTres'], pass_chi2=worst['chi2'])
+    observe(pass_JTJ=worst['JTJ'], pass_JTres=worst['JTres'], pass_chi2=worst['chi2'])
     assert worst['JTJ'] < TOL_PASS and worst['JTres'] < TOL_PASS and worst['chi2'] <= TOL_PASS
 
 
@@ -145,7 +106,7 @@ def test_fits_against_the_oracle(S, name):
     print('scenario (%s): iterations %s, exits %s, fits with a rejection %d' % (
         name, sorted(set(res['iterations'].tolist())), sorted(set(res['exit_reason'].tolist())),
         int(np.sum(res['n_chi2'] != res['iterations'] + 1))))
-    _observe(**{'fit_%s_lambda' % name: worst['lam'], 'fit_%s_pars' % name: worst['pars'], 'fit_%s_chi2' % name: worst['chi2']})
+    observe(**{'fit_%s_lambda' % name: worst['lam'], 'fit_%s_pars' % name: worst['pars'], 'fit_%s_chi2' % name: worst['chi2']})
     assert not mismatches, '%d of %d fits differ in (iterations, n_sweeps, n_chi2, n_omega, exit_reason): %s' % (len(mismatches), B, mismatches[:8])
     assert worst['lam'] <= TOL_LAMBDA and worst['pars'] < TOL_PARS and worst['chi2'] < TOL_CHI2
 
@@ -169,7 +130,7 @@ def test_against_gfh_fit_one_spectrum_at_a_time(S):
             worst = max(worst, np.max(np.abs(pars[b] - out.ravel()) / np.abs(out.ravel())))
     finally:
         c.close()
-    _observe(vs_gfh_fit_pars=worst)
+    observe(vs_gfh_fit_pars=worst)
     assert worst < TOL_PARS
 
 
@@ -187,13 +148,13 @@ def test_a_fit_does_not_depend_on_its_batch(S):
                 _, x, y, w, _ = S.items[k]
                 c.set_batch_data([0, x.size], x, y, w)
                 p1, r1, _ = c.fit_batch(starts[k:k + 1], ACTIVE, **kw)
-                _same_bits(p1, r1, pars[k:k + 1], res[k:k + 1])
+                same_bits(p1, r1, pars[k:k + 1], res[k:k + 1])
             rev = S.items[::-1]
             off_r = np.concatenate([[0], np.cumsum([it[1].size for it in rev])])
             c.set_batch_data(off_r, np.concatenate([it[1] for it in rev]), np.concatenate([it[2] for it in rev]),
                              np.concatenate([it[3] for it in rev]))
             pr, rr, _ = c.fit_batch(starts[::-1], ACTIVE, **kw)
-            _same_bits(pr[::-1], rr[::-1], pars, res)
+            same_bits(pr[::-1], rr[::-1], pars, res)
         finally:
             c.close()
 
@@ -219,7 +180,7 @@ def test_a_failing_fit_stays_alone(S):
     assert r1['exit_reason'][k] == 8 and r1['iterations'][k] == 0 and np.array_equal(p1[k], starts[k])
     assert r1['n_sweeps'][k] == 1 and r1['n_chi2'][k] == 1 and r1['chi2'][k] == 0.0
     keep = np.arange(B) != k
-    _same_bits(p1[keep], r1[keep], pars[keep], res[keep])
+    same_bits(p1[keep], r1[keep], pars[keep], res[keep])
 
 
 def test_python_api_returns_what_fit_batch_returns(S):
@@ -251,7 +212,7 @@ def test_python_api_returns_what_fit_batch_returns(S):
                                    lambda_=1.0, max_iter=50, chi2_rel=1e-6)
     finally:
         gf.gadf_close()
-    _same_bits(p1, r1, p0, r0)
+    same_bits(p1, r1, p0, r0)
     assert set(r0['exit_reason'].tolist()) == {2}
 
 
@@ -284,13 +245,6 @@ EXP4_CASES = {
     'subset_chi2_abs': ([1, 4, 6], 0.3, dict(lambda_=1.0, DTD_min=[1e-3] * 3, chi2_abs=1.5, rel_error=1e-2, max_iter=20)),      # exit 1
     'subset_rel_error': ([1, 4, 6], 0.3, dict(lambda_=10.0, DTD_min=[1e3] * 3, rel_error=5e-2, max_iter=20)),                   # exit 5
 }
-
-
-def spectrum4(b):
-    u = (M.splitmix64(8, M.SEED + 2000 * (b + 1)) >> np.uint64(11)).astype(np.float64) / 9007199254740992.0
-    truth = M.EXP4_TRUTH * (0.9 + 0.2 * u)
-    x, y, s = M.make_single(M.exp4_numpy, truth, 128 + (53 * b) % 385, 0.05, 100.0, seed=M.SEED + 7 * b + 3)
-    return truth, x, y, 1.0 / s
 
 
 @pytest.fixture(scope='module')
@@ -326,7 +280,7 @@ def test_eight_parameters_subsets_and_the_other_options_against_the_oracle(S4, n
         worst['pars'] = max(worst['pars'], np.max(np.abs(pars[b] - p.pars.ravel()) / np.abs(p.pars.ravel())))
         worst['chi2'] = max(worst['chi2'], abs(res['chi2'][b] - r0.chi2) / r0.chi2)
     print('exp4 %s: iterations %s, exits %s' % (name, sorted(set(res['iterations'].tolist())), sorted(set(res['exit_reason'].tolist()))))
-    _observe(**{'exp4_%s_lambda' % name: worst['lam'], 'exp4_%s_pars' % name: worst['pars'], 'exp4_%s_chi2' % name: worst['chi2']})
+    observe(**{'exp4_%s_lambda' % name: worst['lam'], 'exp4_%s_pars' % name: worst['pars'], 'exp4_%s_chi2' % name: worst['chi2']})
     assert worst['lam'] <= TOL_LAMBDA and worst['pars'] < 1e-10 and worst['chi2'] < 1e-10
 
 
@@ -343,6 +297,6 @@ def test_one_pass_with_eight_parameters_against_the_oracle(S4):
         sc = np.sqrt(np.outer(np.diag(JTJ0), np.diag(JTJ0))) + 1e-300
         worst = max(worst, np.max(np.abs(JTJ[b] - JTJ0) / sc), np.max(np.abs(JTr[b] - JTr0) / (np.sqrt(np.diag(JTJ0) * chi0) + 1e-300)),
                     abs(chi2[b] - chi0) / chi0)
-    _observe(exp4_pass=worst)
+    observe(exp4_pass=worst)
     assert worst < TOL_PASS
 

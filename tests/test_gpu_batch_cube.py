@@ -19,16 +19,13 @@ import pytest
 from gadfit_amd import _lib
 from oracle import binding as orc
 from tests import batch_cube_cases as CC
-from tests.test_gpu_batch import COUNTS, SCENARIOS, TOL_LAMBDA, TOL_PASS
+from tests.batch_common import COUNTS, SCENARIOS, TOL_FIT, TOL_LAMBDA, TOL_PASS, context, same_pass
 
 pytestmark = pytest.mark.gpu
 
-TOL_FIT = 1e-10                     # parameters and chi2 against the oracle (tests/batch_cases.py's bounds)
-
 
 def _context(lanes=64):
-    c = _lib.Context(0)
-    c.set_model(CC.tape())
+    c = context(CC.tape())
     c.set_batch_lanes(lanes)
     return c
 
@@ -37,12 +34,8 @@ def _bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
-def _same_pass(a, b):
-    for u, v, name in zip(a, b, ('JTJ', 'JTres', 'chi2')):
-        assert np.array_equal(_bits(u), _bits(v)), name
-
-
 def _same_fit(p, r, p0, r0):
+    """as batch_common.same_bits, and the parameters bit for bit too (same_bits compares their values: +0.0 equals -0.0 there)"""
     assert np.array_equal(_bits(p), _bits(p0))
     for f in COUNTS + ('dof',):
         assert np.array_equal(r[f], r0[f]), f
@@ -77,7 +70,8 @@ def _run(c, n, idx, form):
 
 
 def _same_run(a, b):
-    _same_pass(a[0], b[0])
+    """two results of _run: the passes by same_pass, each scenario's fit by _same_fit"""
+    same_pass(a[0], b[0])
     for (p, r), (p0, r0) in zip(a[1:], b[1:]):
         _same_fit(p, r, p0, r0)
 
@@ -218,7 +212,7 @@ def test_a_fit_reads_no_point_of_its_neighbours(lanes, n, yt):
                 Y[~clean] = np.nan
             _set_cube(c, n, yt, et, idx, Y, w)
             got = _run(c, n, idx, form)
-            _same_pass([v[clean] for v in got[0]], [v[clean] for v in full[0]])
+            same_pass([v[clean] for v in got[0]], [v[clean] for v in full[0]])
             for (p1, r1), (p0, r0), name in zip(got[1:], full[1:], CC.FIT_SCENARIOS):
                 _same_fit(p1[clean], r1[clean], p0[clean], r0[clean])
                 bad = ~clean
@@ -248,7 +242,7 @@ def test_a_large_batch_of_short_rows():
         p66, r66, _ = c.fit_batch(st[:66], CC.ACTIVE, **kw)
     finally:
         c.close()
-    _same_pass(one, [v[idx] for v in one])
+    same_pass(one, [v[idx] for v in one])
     _same_fit(pars, res, pars[idx], res[idx])
     _same_fit(pars[:66], res[:66], p66, r66)
     assert len(set(res['exit_reason'][:66].tolist()) - {8}) > 0
@@ -275,7 +269,7 @@ def test_one_pass_over_more_than_2_31_samples():
     finally:
         c.close()
     print('more than 2**31 samples: %.1f s' % (time.time() - t0))
-    _same_pass(one, [v[idx] for v in three])
+    same_pass(one, [v[idx] for v in three])
     assert len({three[2][k] for k in range(3)}) == 3          # three different spectra: a row that lands on another one shows
 
 
@@ -347,7 +341,7 @@ def test_life_cycle_on_one_context(established):
             if key.startswith('mem'):
                 assert v == one[key], key
             elif key == 'pass2':
-                _same_pass(v, one[key])
+                same_pass(v, one[key])
             elif key == 'plain':
                 assert np.array_equal(v[0], one[key][0]) and v[1:] == one[key][1:]
             else:

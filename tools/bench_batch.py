@@ -25,14 +25,14 @@ process, so a module run alone writes its own keys only).  --observed-only: the 
 --rows: the two forms of the batch kernels against each other, the table the auto rule of gfh_set_batch_lanes(0) is written from.
 Per model (this file's 4-parameter Gaussian; exp4, four exponentials with all 8 parameters active), spectrum length and form:
 --sizes[0] fits per launch, the median and the min-max of the timed launches, device and wall time per fit.  The yardstick of the row
-form is the wave form on the same card in the same run, never the row form's own time: `row_wins` is tests/batch_row_cases.row_wins
+form is the wave form on the same card in the same run, never the row form's own time: `row_wins` is tests/batch_records.row_wins
 (the medians differ by more than the sum of the two forms' min-max spreads), and `auto_rule` is the largest measured length with
 row_wins per active-count class.  --registers: the compiler's register, scratch and occupancy figures of the four kernels
 (hipcc -Rpass-analysis=kernel-resource-usage on the generated source; needs hipcc, no GPU).
 --workgroup: the 256-lane form (a workgroup of four waves per fit) against the 64-lane form by the recipe of --rows, over points per
 spectrum AND fits per launch, since what the workgroup form buys is occupancy when the fits are fewer than the card's SIMDs: per
 (model, fits, points) both forms alternating launch by launch on one context; cells above 2^30 points in total are dropped.  The
-yardstick of the 256-lane form is the 64-lane form of the same run; `workgroup_wins` is tests/batch_row_cases.row_wins.  With
+yardstick of the 256-lane form is the 64-lane form of the same run; `workgroup_wins` is tests/batch_records.row_wins.  With
 --registers: the compiler's figures (LDS included) of the 256-lane kernels of the three units of the --rows table.
 --cube: a batch as a data cube (gfh_set_batch_cube: one shared grid, narrow samples, the weight formed in the load) against the
 ragged form of the same spectra with precomputed SQRT_Y weights -- the yardstick, measured in the same run, never the cube's own time.
@@ -40,7 +40,7 @@ The spectra are counts (the models above scaled by 1000 and rounded, so that uin
 points) the five forms -- ragged, float64 / USER (the shared grid alone), float64 / SQRT_Y (against it: the price of the in-load
 weight), float32 / SQRT_Y, uint16 / SQRT_Y -- alternate launch by launch on one context of one card, each launch behind the upload
 of its own data, by the recipe of --rows; all five hold the same values, so they run the same passes (checked: the totals must be
-equal).  `upload_ms` is the wall time of the set call, median of 3.  `wins` is tests/batch_row_cases.row_wins against the ragged
+equal).  `upload_ms` is the wall time of the set call, median of 3.  `wins` is tests/batch_records.row_wins against the ragged
 form.  With --registers: the compiler's figures of the uint16 / SQRT_Y and float64 / USER units of model_exp2 and model_exp4 at the
 three lane forms (no GPU); model_exp2's must have no scratch."""
 import argparse
@@ -215,12 +215,12 @@ def cube_registers_record():
 
 
 def cube_main(a):
-    from tests import batch_row_cases as RC
+    from tests import batch_records as RC
     rec = dict(method='per cell (model, lanes per fit, fits, points per spectrum) five data forms of the same spectra -- counts, round(%g x the model) -- '
                       'alternating launch by launch on one context of one card in one run, each launch behind the upload of its own data: the median and '
                       'the min-max of %d launches after %d warm-up launches; device = HIP events around the kernel; lambda0 = %g, max_iter = %d and no '
                       'other exit; all forms hold the same values and run the same passes (checked); upload_ms = wall time of the set call, median of 3; '
-                      'the yardstick is the ragged form of the same run with precomputed SQRT_Y weights; wins = tests/batch_row_cases.row_wins against '
+                      'the yardstick is the ragged form of the same run with precomputed SQRT_Y weights; wins = tests/batch_records.row_wins against '
                       'it; no counter pass was made' % (CUBE_SCALE, a.launches, a.warmup, LAMBDA0, MAX_ITER), measurements=[])
     if os.path.exists(a.out):
         old = json.load(open(a.out))
@@ -303,7 +303,7 @@ def cube_main(a):
 
 def rows_main(a, points, lanes_list):
     """the two forms against each other over spectrum lengths (see the module's text)"""
-    from tests import batch_row_cases as RC
+    from tests import batch_records as RC
     nf = int(a.sizes.split(',')[0])
     rec = dict(method='%d fits per launch; per (model, length, form) the median and the min-max of %d launches after %d warm-up launches; device = HIP '
                       'events around the kernel, wall = around the call; lambda0 = %g, max_iter = %d and no other exit, so both forms run the same passes up to the accept / reject decisions that rounding takes past convergence (the totals are in each record); '
@@ -377,7 +377,7 @@ def rows_main(a, points, lanes_list):
 
 def workgroup_main(a, points, sizes, models):
     """the 256-lane form against the 64-lane form over points per spectrum and fits per launch (see the module's text)"""
-    from tests import batch_row_cases as RC
+    from tests import batch_records as RC
     lanes_list = [64, 256]
     rec = dict(method='per (model, fits per launch, points per spectrum, form) the median and the min-max of %d launches after %d warm-up launches; device = HIP '
                       'events around the kernel, wall = around the call; lambda0 = %g, max_iter = %d and no other exit, so both forms run the same passes up to the '
