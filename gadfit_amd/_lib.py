@@ -111,6 +111,12 @@ SYMBOLS = {
     'gfh_debug_batch_lanes': (_i, [_vp]),
     'gfh_set_batch_cube': (_i, [_vp, _i64, _i64, _dp, _vp, _i, _i, _dp]),
     'gfh_debug_batch_form': (_i, [_vp]),
+    'gfh_batch_frames_begin': (_i, [_vp, _i64, _i64, _dp, _i, _i]),
+    'gfh_batch_frames_put': (_i, [_vp, _i64, _i64, _vp, _dp]),
+    'gfh_set_batch_frames': (_i, [_vp, _i64, _i64, _dp, _vp, _i, _i, _dp, _i64]),
+    'gfh_debug_batch_frames_missing': (_i64, [_vp]),
+    'gfh_debug_batch_frames_seconds': (C.c_double, [_vp]),
+    'gfh_debug_batch_read': (_i, [_vp, _i, _i64, _i64, _vp]),
     'gfh_set_lookahead': (_i, [_vp, _i]),
     'gfh_set_keep_jacobian': (_i, [_vp, _i]),
     'gfh_set_use_ad': (_i, [_vp, _i]),
@@ -510,6 +516,7 @@ class Context:
             raise GadfitHipError('set_batch_data: x, y and w must hold offsets[-1] = %d values each, got %d, %d, %d'
                                  % (off[-1], x.size, y.size, w.size))
         self.n_fits = 0
+        self._cube_dtype = None
         try:
             self._chk(lib().gfh_set_batch_data(self._h, off.size - 1, off.ctypes.data_as(C.POINTER(_i64)), dp(x), dp(y), dp(w)))
         except GadfitHipError as e:
@@ -536,6 +543,7 @@ class Context:
             if w.shape != Y.shape:
                 raise GadfitHipError('set_batch_cube: w must have the shape of Y %s, got %s' % (Y.shape, w.shape))
         self.n_fits = 0
+        self._cube_dtype = Y.dtype
         try:
             self._chk(lib().gfh_set_batch_cube(self._h, Y.shape[0], Y.shape[1], dp(x), Y.ctypes.data_as(_vp), _CUBE_TYPES[Y.dtype],
                                                int(error_type), None if w is None else dp(w)))
@@ -544,6 +552,100 @@ class Context:
                 self.n_fits = Y.shape[0]
             raise
         self.n_fits = Y.shape[0]
+
+    # --- a cube from a stack of frames (gfh_batch_frames_begin, gfh_batch_frames_put, gfh_set_batch_frames)
+    def _frames_piece(self, who, what, F, dtype, n_fits):
+        if not isinstance(F, np.ndarray) or F.dtype != dtype:
+            raise GadfitHipError('%s: %s must be a numpy array of %s (it is uploaded as it is), got %s'
+                                 % (who, what, np.dtype(dtype).name, F.dtype if isinstance(F, np.ndarray) else type(F).__name__))
+        if F.ndim != 2 or not F.flags['C_CONTIGUOUS']:
+            raise GadfitHipError('%s: %s must be 2-D [n_frames][n_fits] and C-contiguous' % (who, what))
+        if n_fits is not None and F.shape[1] != n_fits:
+            raise GadfitHipError('%s: %s must hold one sample per fit of the batch in every frame (%d), got %d' % (who, what, n_fits, F.shape[1]))
+
+    def batch_frames_begin(self, x, n_fits, dtype, error_type=0):
+        """begins a cube that is filled frame by frame: the grid x [n_points], n_fits spectra, the sample type dtype (float64, float32
+        or uint16) and the weight rule as set_batch_cube; every frame is missing until batch_frames_put has put it --
+        gfh_batch_frames_begin"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        try:
+            dtype = np.dtype(dtype)
+        except TypeError:
+            dtype = None
+        if dtype not in _CUBE_TYPES:
+            raise GadfitHipError('batch_frames_begin: dtype must be float64, float32 or uint16, got %s' % (dtype,))
+        if x.ndim != 1:
+            raise GadfitHipError('batch_frames_begin: x must be 1-D [n_points]')
+        self.n_fits = 0
+        self._cube_dtype = None
+        try:
+            self._chk(lib().gfh_batch_frames_begin(self._h, int(n_fits), x.size, dp(x), _CUBE_TYPES[dtype], int(error_type)))
+        except GadfitHipError as e:
+            if 'no GPU bound' in str(e):       # (a compile-only context keeps the geometry and the form, as under set_batch_cube)
+                self.n_fits = int(n_fits); self._cube_dtype = dtype
+            raise
+        self.n_fits = int(n_fits); self._cube_dtype = dtype
+
+    def batch_frames_put(self, first_frame, F_piece, w_piece=None):
+        """frames [first_frame, first_frame + len(F_piece)) of the begun batch: F_piece [n_frames][n_fits] C-contiguous in the begun
+        dtype, uploaded as it is; under USER w_piece alike, the weights as used in (y - f) * w.  In any order and any piece sizes; a
+        frame put again holds the later data -- gfh_batch_frames_put"""
+        if self.batch_frames_missing() < 0:
+            raise GadfitHipError('batch_frames_put: no batch has been begun (batch_frames_begin; set_batch_data and set_batch_cube replace a begun batch)')
+        self._frames_piece('batch_frames_put', 'F_piece', F_piece, self._cube_dtype, self.n_fits)
+        if w_piece is not None:
+            w_piece = np.ascontiguousarray(w_piece, dtype=np.float64)
+            if w_piece.shape != F_piece.shape:
+                raise GadfitHipError('batch_frames_put: w_piece must have the shape of F_piece %s, got %s' % (F_piece.shape, w_piece.shape))
+        self._chk(lib().gfh_batch_frames_put(self._h, int(first_frame), F_piece.shape[0], F_piece.ctypes.data_as(_vp),
+                                             None if w_piece is None else dp(w_piece)))
+
+    def set_batch_frames(self, x, F, error_type=0, w=None, frames_per_put=0):
+        """a batch as a stack of frames: every spectrum on the one grid x [n_points], F [n_points][n_fits] C-contiguous in float64,
+        float32 or uint16 -- one image per abscissa, the fit index fastest, uploaded as it is and transposed into the cube on the
+        device; error_type and w (frame-major as F) as set_batch_cube.  frames_per_put: frames per upload, 0 the library's rule (at
+        most 256 MiB of staging).  From here on the batch is the cube set_batch_cube(x, F.T) holds -- gfh_set_batch_frames"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if not isinstance(F, np.ndarray) or F.dtype not in _CUBE_TYPES:
+            raise GadfitHipError('set_batch_frames: F must be a numpy array of float64, float32 or uint16 (it is uploaded as it is), got %s'
+                                 % (F.dtype if isinstance(F, np.ndarray) else type(F).__name__))
+        if F.ndim != 2 or not F.flags['C_CONTIGUOUS']:
+            raise GadfitHipError('set_batch_frames: F must be 2-D [n_points][n_fits] and C-contiguous')
+        if x.ndim != 1 or x.size != F.shape[0]:
+            raise GadfitHipError('set_batch_frames: x must hold one abscissa per frame of F (%d), got %d' % (F.shape[0], x.size))
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float64)
+            if w.shape != F.shape:
+                raise GadfitHipError('set_batch_frames: w must have the shape of F %s, got %s' % (F.shape, w.shape))
+        self.n_fits = 0
+        self._cube_dtype = None
+        try:
+            self._chk(lib().gfh_set_batch_frames(self._h, F.shape[1], F.shape[0], dp(x), F.ctypes.data_as(_vp), _CUBE_TYPES[F.dtype],
+                                                 int(error_type), None if w is None else dp(w), int(frames_per_put)))
+        except GadfitHipError as e:
+            if 'no GPU bound' in str(e):
+                self.n_fits = F.shape[1]; self._cube_dtype = F.dtype
+            raise
+        self.n_fits = F.shape[1]; self._cube_dtype = F.dtype
+
+    def batch_frames_missing(self):
+        """frames of the begun batch not yet put; -1: the batch held was not begun by batch_frames_begin / set_batch_frames --
+        gfh_debug_batch_frames_missing"""
+        return int(lib().gfh_debug_batch_frames_missing(self._h))
+
+    def batch_frames_seconds(self):
+        """device time of the transposing kernels of every put since the batch was begun -- gfh_debug_batch_frames_seconds"""
+        return float(lib().gfh_debug_batch_frames_seconds(self._h))
+
+    def debug_batch_read(self, which, first, count):
+        """elements [first, first + count) of the cube held, row-major [n_fits][n_points], as stored: which 0 the samples in the
+        dtype this object set or began the cube with, 1 the USER weights as float64 -- gfh_debug_batch_read"""
+        dtype = getattr(self, '_cube_dtype', None)
+        if dtype is None or getattr(self, 'n_fits', 0) < 1:
+            raise GadfitHipError('debug_batch_read: this object holds no cube (set_batch_cube, set_batch_frames, batch_frames_begin)')
+        out = np.empty(int(count), dtype=np.float64 if which == 1 else dtype)
+        self._chk(lib().gfh_debug_batch_read(self._h, int(which), int(first), int(count), out.ctypes.data_as(_vp)))
+        return out
 
     def batch_form_used(self):
         """the data form of the last batch launch: None (none yet), 'ragged', or ('cube', y_type, error_type) -- gfh_debug_batch_form"""

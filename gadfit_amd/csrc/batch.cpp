@@ -1,6 +1,7 @@
 // batch.cpp -- batched independent fits: many Levenberg-Marquardt fits of ONE model in ONE kernel launch, each with its own data,
 // start parameters, lambda history and exit (gfh_set_batch_data, gfh_fit_batch, gfh_batch_pass, gfh_batch_source, gfh_batch_prepare,
-// gfh_set_batch_lanes; gfh_set_batch_cube: the same batch as a cube on one grid with narrow samples).  This file validates, uploads, compiles / loads and launches; the loop itself (gadfit.F90:670-915) is the
+// gfh_set_batch_lanes; gfh_set_batch_cube: the same batch as a cube on one grid with narrow samples; gfh_batch_frames_begin,
+// gfh_batch_frames_put, gfh_set_batch_frames: that cube from a frame-major stack, transposed on the device by frames.hip).  This file validates, uploads, compiles / loads and launches; the loop itself (gadfit.F90:670-915) is the
 // generated kernel gfh_k_fit_batch (batch_fit.hip; codegen.cpp, emit_batch_kernels), a wave per fit or -- gfh_set_batch_lanes(16) -- a
 // DPP row of 16 lanes per fit and four fits per wave, or -- gfh_set_batch_lanes(256) -- a workgroup of four waves per fit.  One stream, one launch and one device-to-host copy per call.
 // Everything the kernels do not carry is refused here with its own message, before anything touches the device.
@@ -59,6 +60,41 @@ int check_geometry(gfh_ctx* c, const char* who, int na) {
   if (c->batch.n_fits < 1) return fail(c, w + ": no batch data (gfh_set_batch_data, gfh_set_batch_cube)");
   if (c->batch.min_points < na) return fail(c, "More independent fitting parameters than data points (a fit of the batch has " +
                                               std::to_string((long long)c->batch.min_points) + " points).");      // gadfit.F90:648-657, per fit
+  return 0;
+}
+// a cube begun by gfh_batch_frames_begin is fitted once every frame has been put
+int check_frames(gfh_ctx* c, const char* who) {
+  if (!c->batch.frames || c->batch.frames_missing == 0) return 0;
+  return fail(c, std::string(who) + ": " + std::to_string((long long)c->batch.frames_missing) + " of " + std::to_string((long long)c->batch.max_points) +
+                 " frames of the batch begun by gfh_batch_frames_begin have not been put (gfh_batch_frames_put)");
+}
+// the batch held is no longer one that gfh_batch_frames_begin began
+void frames_end(gfh_ctx* c) {
+  c->batch.frames = false; c->batch.frame_put.clear(); c->batch.frames_missing = 0; c->batch.frames_kernel_ms = 0.0;
+}
+constexpr size_t elem_bytes(int y_type) { return y_type == 0 ? 8 : y_type == 1 ? 4 : 2; }
+// The largest staging of gfh_set_batch_frames' default pieces (frames_per_put 0), samples and USER weights together.  Kept at the
+// 256 MiB it was proposed with: every stack of the measured table (profiles/batch_frames.json; at most 262 MB)
+// is ONE put under it, so the default there is the single put it was to be compared with, and the same stacks cut into eight puts
+// took 0.15 ... 0.3 ms longer (about 30 us per further put) -- a stack above the bound pays that per 256 MiB, against 5 ms of upload.
+// The measurement gave no reason for another value; it does not hold a smaller one to be worse by more than that.
+constexpr int64_t kFramesStageBytes = (int64_t)256 << 20;
+
+// what a cube can be, for the three calls that make one (gfh_set_batch_cube, gfh_batch_frames_begin, gfh_set_batch_frames): one
+// order, one wording, each under its own name.  null_arg: a required pointer is NULL, `required` names them; has_w: -1 the call takes no w
+int check_cube(gfh_ctx* c, const char* who, bool null_arg, const char* required, int64_t n_fits, int64_t n_points, int y_type, int error_type,
+               int has_w) {
+  const std::string w(who);
+  if (null_arg) return fail(c, w + ": null argument (" + required + " required)");
+  if (n_fits < 1) return fail(c, w + ": a batch holds at least one fit");
+  if (n_points < 1) return fail(c, w + ": a spectrum holds at least one point");
+  if (n_fits > ((int64_t)1 << 31) - 4) return fail(c, w + ": more fits than one launch takes (2^31 - 4)");
+  if (y_type < 0 || y_type > 2) return fail(c, w + ": unknown y_type " + std::to_string(y_type) + " (0 double, 1 float, 2 uint16_t)");
+  if (error_type < 0 || error_type > 4)
+    return fail(c, w + ": unknown error_type " + std::to_string(error_type) + " (0 NONE, 1 SQRT_Y, 2 PROPTO_Y, 3 INVERSE_Y, 4 USER)");
+  if (has_w >= 0 && error_type == 4 && !has_w) return fail(c, w + ": error_type USER needs the weights w");
+  if (has_w >= 0 && error_type != 4 && has_w) return fail(c, w + ": w is taken under error_type USER alone (the other types form the weights from y on the device)");
+  if (n_points > INT64_MAX / 8 / n_fits) return fail(c, w + ": n_fits x n_points overflows");
   return 0;
 }
 
@@ -125,7 +161,7 @@ int gfh_set_batch_data(gfh_ctx* c, int64_t n_fits, const int64_t* offsets, const
   }
   if (join_pending(c)) return 1;
   if (c->device >= 0 && c->batch.on_device) { hipSetDevice(c->device); if (c->stream) hipStreamSynchronize(c->stream); }
-  batch_free(c);
+  batch_free(c); frames_end(c);
   c->batch.cube = false; c->batch.y_type = c->batch.error_type = 0;
   c->batch.n_fits = n_fits; c->batch.off.assign(offsets, offsets + n_fits + 1); c->batch.min_points = shortest; c->batch.max_points = longest;
   NEED_GPU(c);
@@ -151,19 +187,10 @@ int gfh_set_batch_data(gfh_ctx* c, int64_t n_fits, const int64_t* offsets, const
 int gfh_set_batch_cube(gfh_ctx* c, int64_t n_fits, int64_t n_points, const double* x, const void* y, int y_type, int error_type,
                        const double* w) try {
   if (check_context(c, "gfh_set_batch_cube")) return 1;
-  if (!x || !y) return fail(c, "gfh_set_batch_cube: null argument (x and y are required)");
-  if (n_fits < 1) return fail(c, "gfh_set_batch_cube: a batch holds at least one fit");
-  if (n_points < 1) return fail(c, "gfh_set_batch_cube: a spectrum holds at least one point");
-  if (n_fits > ((int64_t)1 << 31) - 4) return fail(c, "gfh_set_batch_cube: more fits than one launch takes (2^31 - 4)");
-  if (y_type < 0 || y_type > 2) return fail(c, "gfh_set_batch_cube: unknown y_type " + std::to_string(y_type) + " (0 double, 1 float, 2 uint16_t)");
-  if (error_type < 0 || error_type > 4)
-    return fail(c, "gfh_set_batch_cube: unknown error_type " + std::to_string(error_type) + " (0 NONE, 1 SQRT_Y, 2 PROPTO_Y, 3 INVERSE_Y, 4 USER)");
-  if (error_type == 4 && !w) return fail(c, "gfh_set_batch_cube: error_type USER needs the weights w");
-  if (error_type != 4 && w) return fail(c, "gfh_set_batch_cube: w is taken under error_type USER alone (the other types form the weights from y on the device)");
-  if (n_points > INT64_MAX / 8 / n_fits) return fail(c, "gfh_set_batch_cube: n_fits x n_points overflows");
+  if (check_cube(c, "gfh_set_batch_cube", !x || !y, "x and y are", n_fits, n_points, y_type, error_type, w != nullptr)) return 1;
   if (join_pending(c)) return 1;
   if (c->device >= 0 && c->batch.on_device) { hipSetDevice(c->device); if (c->stream) hipStreamSynchronize(c->stream); }
-  batch_free(c);
+  batch_free(c); frames_end(c);
   c->batch.cube = true; c->batch.y_type = y_type; c->batch.error_type = error_type;
   c->batch.n_fits = n_fits; c->batch.off.clear(); c->batch.min_points = c->batch.max_points = n_points;
   NEED_GPU(c);
@@ -178,6 +205,110 @@ int gfh_set_batch_cube(gfh_ctx* c, int64_t n_fits, int64_t n_points, const doubl
   c->batch.on_device = true;
   return 0;
 } catch (const std::exception& e) { return fail(c, std::string("gfh_set_batch_cube: ") + e.what()); }
+
+// A cube that arrives frame by frame (include/gadfit_hip.h): instruments deliver F [n_points][n_fits], one image per abscissa with
+// the pixel index fastest.  begin is gfh_set_batch_cube without the samples -- the same checks, the same state, the same blocks --
+// and marks every frame as missing; gfh_batch_frames_put uploads a piece as it is stored and k_frames_to_cube (frames.hip)
+// transposes it into the cube's columns.  Once no frame is missing nothing downstream knows where the cube came from.
+int gfh_batch_frames_begin(gfh_ctx* c, int64_t n_fits, int64_t n_points, const double* x, int y_type, int error_type) try {
+  if (check_context(c, "gfh_batch_frames_begin")) return 1;
+  if (check_cube(c, "gfh_batch_frames_begin", !x, "x is", n_fits, n_points, y_type, error_type, -1)) return 1;
+  std::vector<unsigned char> flags((size_t)n_points, 0);          // (before anything is replaced: this can fail)
+  if (join_pending(c)) return 1;
+  if (c->device >= 0 && c->batch.on_device) { hipSetDevice(c->device); if (c->stream) hipStreamSynchronize(c->stream); }
+  batch_free(c); frames_end(c);
+  c->batch.cube = true; c->batch.y_type = y_type; c->batch.error_type = error_type;
+  c->batch.n_fits = n_fits; c->batch.off.clear(); c->batch.min_points = c->batch.max_points = n_points;
+  c->batch.frames = true; c->batch.frame_put.swap(flags); c->batch.frames_missing = n_points;
+  NEED_GPU(c);
+  const size_t n = (size_t)n_fits * (size_t)n_points;
+  if (dev_alloc(c, c->batch.x, sizeof(double) * (size_t)n_points) || dev_alloc(c, c->batch.y, n * elem_bytes(y_type))) return 1;
+  if (error_type == 4 && dev_alloc(c, c->batch.w, sizeof(double) * n)) return 1;
+  copy_path_ready();
+  HIPCHK(c, hipMemcpyAsync(c->batch.x.p, x, sizeof(double) * (size_t)n_points, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->batch.on_device = true;
+  return 0;
+} catch (const std::exception& e) { return fail(c, std::string("gfh_batch_frames_begin: ") + e.what()); }
+
+// Frames [first_frame, first_frame + n_frames) of the begun batch: y [n_frames][n_fits] in the begun sample type, w alike as doubles
+// under USER.  In any order and any piece sizes; a frame put again holds the later data.  The piece is staged in blocks of its own
+// size, which go when no frame is missing; the call returns after the stream has drained, so the caller's buffers are free again.
+int gfh_batch_frames_put(gfh_ctx* c, int64_t first_frame, int64_t n_frames, const void* y, const double* w) try {
+  if (check_context(c, "gfh_batch_frames_put")) return 1;
+  if (!c->batch.frames)
+    return fail(c, "gfh_batch_frames_put: no batch has been begun (gfh_batch_frames_begin; gfh_set_batch_data and gfh_set_batch_cube replace a begun batch)");
+  const int64_t n_fits = c->batch.n_fits, n_points = c->batch.max_points;
+  if (first_frame < 0) return fail(c, "gfh_batch_frames_put: first_frame is negative (" + std::to_string((long long)first_frame) + ")");
+  if (n_frames < 1) return fail(c, "gfh_batch_frames_put: a piece holds at least one frame");
+  if (first_frame > n_points - n_frames)
+    return fail(c, "gfh_batch_frames_put: frames [" + std::to_string((long long)first_frame) + ", " + std::to_string((long long)first_frame) + " + " +
+                   std::to_string((long long)n_frames) + ") reach past the " + std::to_string((long long)n_points) + " frames of the batch");
+  if (!y) return fail(c, "gfh_batch_frames_put: null argument (y is required)");
+  if (c->batch.error_type == 4 && !w) return fail(c, "gfh_batch_frames_put: error_type USER needs the weights w");
+  if (c->batch.error_type != 4 && w) return fail(c, "gfh_batch_frames_put: w is taken under error_type USER alone (the other types form the weights from y on the device)");
+  NEED_GPU(c);
+  if (!c->batch.on_device) return fail(c, "gfh_batch_frames_put: the begun batch is not on the device (gfh_batch_frames_begin failed)");
+  const size_t eb = elem_bytes(c->batch.y_type), ne = (size_t)n_frames * (size_t)n_fits;
+  if (dev_alloc(c, c->batch.stage_y, ne * eb)) return 1;
+  if (w && dev_alloc(c, c->batch.stage_w, ne * sizeof(double))) return 1;
+  copy_path_ready();
+  harvest_events(c);
+  HIPCHK(c, hipMemcpyAsync(c->batch.stage_y.p, y, ne * eb, hipMemcpyHostToDevice, c->stream));
+  if (w) HIPCHK(c, hipMemcpyAsync(c->batch.stage_w.p, w, ne * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+  HIPCHK(c, launch_frames_to_cube(c->stream, (int)eb, c->batch.stage_y.p, n_frames, n_fits, c->batch.y.p, n_points, first_frame));
+  if (w) HIPCHK(c, launch_frames_to_cube(c->stream, 8, c->batch.stage_w.p, n_frames, n_fits, c->batch.w.p, n_points, first_frame));
+  HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->batch.frames_kernel_ms += ev_ms(c->ev[0], c->ev[1]);
+  for (int64_t p = first_frame; p < first_frame + n_frames; p++)
+    if (!c->batch.frame_put[(size_t)p]) { c->batch.frame_put[(size_t)p] = 1; c->batch.frames_missing--; }
+  if (c->batch.frames_missing == 0) { dev_free(c->batch.stage_y); dev_free(c->batch.stage_w); }
+  return 0;
+} catch (const std::exception& e) { return fail(c, std::string("gfh_batch_frames_put: ") + e.what()); }
+
+// begin + puts of a whole stack y [n_points][n_fits] (w alike under USER), frames_per_put frames each; 0: the largest count whose
+// staging -- samples and weights -- stays within kFramesStageBytes, but at least one frame
+int gfh_set_batch_frames(gfh_ctx* c, int64_t n_fits, int64_t n_points, const double* x, const void* y, int y_type, int error_type,
+                         const double* w, int64_t frames_per_put) try {
+  if (check_context(c, "gfh_set_batch_frames")) return 1;
+  if (check_cube(c, "gfh_set_batch_frames", !x || !y, "x and y are", n_fits, n_points, y_type, error_type, w != nullptr)) return 1;
+  if (frames_per_put < 0) return fail(c, "gfh_set_batch_frames: frames_per_put is negative (0: pieces of at most " +
+                                         std::to_string((long long)(kFramesStageBytes >> 20)) + " MiB of staging)");
+  if (gfh_batch_frames_begin(c, n_fits, n_points, x, y_type, error_type)) return 1;
+  const int64_t per_frame = n_fits * (int64_t)(elem_bytes(y_type) + (w ? sizeof(double) : 0));
+  const int64_t step = frames_per_put ? frames_per_put : std::max<int64_t>(1, kFramesStageBytes / per_frame);
+  for (int64_t p = 0, k; p < n_points; p += k) {
+    k = std::min(step, n_points - p);
+    if (gfh_batch_frames_put(c, p, k, static_cast<const char*>(y) + (size_t)p * (size_t)n_fits * elem_bytes(y_type),
+                             w ? w + (size_t)p * (size_t)n_fits : nullptr)) return 1;
+  }
+  return 0;
+} catch (const std::exception& e) { return fail(c, std::string("gfh_set_batch_frames: ") + e.what()); }
+
+// frames of the begun batch not yet put; -1: the batch held was not begun by gfh_batch_frames_begin
+int64_t gfh_debug_batch_frames_missing(gfh_ctx* c) { return c && c->batch.frames ? c->batch.frames_missing : -1; }
+// device time of the transposing kernels of every put since the last gfh_batch_frames_begin, in seconds (HIP events)
+double gfh_debug_batch_frames_seconds(gfh_ctx* c) { return c && c->batch.frames ? 1e-3 * c->batch.frames_kernel_ms : 0.0; }
+
+// Elements [first, first + count) of the cube held, as stored (row-major [n_fits][n_points]): which 0 the samples in their type, 1
+// the USER weights as doubles.  For tests that hold the cube's bytes; frames not yet put read as whatever the block held.
+int gfh_debug_batch_read(gfh_ctx* c, int which, int64_t first, int64_t count, void* dst) try {
+  if (check_context(c, "gfh_debug_batch_read")) return 1;
+  if (c->batch.n_fits < 1 || !c->batch.cube) return fail(c, "gfh_debug_batch_read: the context holds no cube (gfh_set_batch_cube, gfh_batch_frames_begin)");
+  if (which != 0 && which != 1) return fail(c, "gfh_debug_batch_read: which is 0 (the samples) or 1 (the USER weights)");
+  if (which == 1 && c->batch.error_type != 4) return fail(c, "gfh_debug_batch_read: the cube holds weights under error_type USER alone");
+  if (first < 0 || count < 0 || first > c->batch.n_fits * c->batch.max_points - count)
+    return fail(c, "gfh_debug_batch_read: elements [first, first + count) reach past the cube");
+  if (!dst) return fail(c, "gfh_debug_batch_read: null argument");
+  NEED_GPU(c);
+  if (!c->batch.on_device) return fail(c, "gfh_debug_batch_read: no batch data on the device");
+  const size_t eb = which ? sizeof(double) : elem_bytes(c->batch.y_type);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (count) HIPCHK(c, hipMemcpy(dst, (which ? c->batch.w : c->batch.y).as<char>() + (size_t)first * eb, (size_t)count * eb, hipMemcpyDeviceToHost));
+  return 0;
+} catch (const std::exception& e) { return fail(c, std::string("gfh_debug_batch_read: ") + e.what()); }
 
 // gadf_fit (gadfit.F90:502-1035) for every spectrum of the batch at once: STEP 1+2, the damped solve (potr_f08,
 // gadfit_linalg.F90:36-57), STEP 3 under accth, STEP 4 with its retrials and STEP 5 run on the device, a wave or -- gfh_set_batch_lanes --
@@ -198,7 +329,7 @@ int gfh_fit_batch(gfh_ctx* c, double* pars, int na, const int32_t* active, const
   LmOptions lo;
   if (const char* refusal = resolve_lm_options(*o, &lo)) return fail(c, refusal);                        // gadfit.F90:575-578
   if (!o->has_max_iter || o->max_iter < 0) return fail(c, "gfh_fit_batch: max_iter is required (a loop that runs on the device must be bounded)");
-  if (check_geometry(c, "gfh_fit_batch", na)) return 1;
+  if (check_geometry(c, "gfh_fit_batch", na) || check_frames(c, "gfh_fit_batch")) return 1;
   BatchOpts bo; memset(&bo, 0, sizeof bo);
   bo.lambda = lo.lambda; bo.lam_up = lo.lam_up; bo.lam_down = lo.lam_down; bo.lam_incs = lo.lam_incs;      // gadfit.F90:568-584 (lm_options.h)
   bo.use_accth = lo.use_accth; bo.accth = o->accth;
@@ -241,7 +372,7 @@ int gfh_fit_batch(gfh_ctx* c, double* pars, int na, const int32_t* active, const
 int gfh_batch_pass(gfh_ctx* c, const double* pars, int na, const int32_t* active, double* JTJ, double* JTres, double* chi2) try {
   if (check_context(c, "gfh_batch_pass") || check_model(c, "gfh_batch_pass", na, active)) return 1;
   if (!pars || !JTJ || !JTres || !chi2) return fail(c, "gfh_batch_pass: null argument");
-  if (check_geometry(c, "gfh_batch_pass", na)) return 1;
+  if (check_geometry(c, "gfh_batch_pass", na) || check_frames(c, "gfh_batch_pass")) return 1;
   NEED_GPU(c);
   if (!c->batch.on_device) return fail(c, "gfh_batch_pass: no batch data on the device (gfh_set_batch_data, gfh_set_batch_cube)");
   ModelKernels* mk = nullptr;

@@ -199,6 +199,14 @@ struct gfh_ctx {
     int last_form = -1;             // the data form of the last batch launch (gfh_debug_batch_form); -1: none yet
     bool on_device = false;
     gfh::DevBuf x, y, w, off_d, io, img;
+    // gfh_batch_frames_begin: the cube above, filled frame by frame.  One flag per frame (1: put), the count of those still 0, the
+    // staging blocks of the piece in flight (stage_y, and stage_w under USER: freed when no frame is missing) and the device time of
+    // the transposing kernels since begin.  frames goes back to false with the next gfh_set_batch_data / gfh_set_batch_cube.
+    bool frames = false;
+    std::vector<unsigned char> frame_put;
+    int64_t frames_missing = 0;
+    double frames_kernel_ms = 0.0;
+    gfh::DevBuf stage_y, stage_w;
     std::vector<char> host;         // where the one device-to-host copy of a call lands
   } batch;
 };

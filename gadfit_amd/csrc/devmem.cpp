@@ -84,14 +84,15 @@ void gfh::dev_release(int device, DevBuf& b) {
 
 // the blocks of a batch of independent fits (context.h, Batch; batch.cpp fills them): dropped together by the next
 // gfh_set_batch_data or gfh_set_batch_cube, and what gfh_device_memory reports of them (a cube holds its grid in x, its narrow
-// samples in y, w under USER alone and no offsets)
+// samples in y, w under USER alone and no offsets; while gfh_batch_frames_put fills it, the staging blocks of a piece as well)
 void gfh::batch_free(gfh_ctx* c) {
-  DevBuf* bufs[] = {&c->batch.x, &c->batch.y, &c->batch.w, &c->batch.off_d, &c->batch.io, &c->batch.img};
+  DevBuf* bufs[] = {&c->batch.x, &c->batch.y, &c->batch.w, &c->batch.off_d, &c->batch.io, &c->batch.img, &c->batch.stage_y, &c->batch.stage_w};
   for (DevBuf* b : bufs) dev_free(*b);
   c->batch.on_device = false;
 }
 size_t gfh::batch_bytes(const gfh_ctx* c) {
-  return c->batch.x.bytes + c->batch.y.bytes + c->batch.w.bytes + c->batch.off_d.bytes + c->batch.io.bytes + c->batch.img.bytes;
+  return c->batch.x.bytes + c->batch.y.bytes + c->batch.w.bytes + c->batch.off_d.bytes + c->batch.io.bytes + c->batch.img.bytes +
+         c->batch.stage_y.bytes + c->batch.stage_w.bytes;
 }
 
 int gfh::pinned_reserve(gfh_ctx* c, size_t bytes) {

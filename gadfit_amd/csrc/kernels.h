@@ -1,4 +1,4 @@
-// kernels.h -- launchers of the static (model-independent) kernels: gram.hip, assemble.hip, jtv.hip, kernels.hip
+// kernels.h -- launchers of the static (model-independent) kernels: gram.hip, assemble.hip, jtv.hip, frames.hip, kernels.hip
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -32,5 +32,9 @@ hipError_t launch_publish(hipStream_t st, const double* src, int n, const int* s
                           unsigned long long* host_flag, unsigned long long seq);
 hipError_t launch_status_slot(hipStream_t st, const int* status, double* dst);
 hipError_t launch_fill_pads(hipStream_t st, int nd, const i64* seg, double* x, double* y, double* w, unsigned char* is_pad);
+// frames.hip: stage [n_frames][n_fits] transposed into columns [first_frame, first_frame + n_frames) of cube [n_fits][n_points];
+// elem_bytes 2, 4 or 8
+hipError_t launch_frames_to_cube(hipStream_t st, int elem_bytes, const void* stage, i64 n_frames, i64 n_fits, void* cube,
+                                 i64 n_points, i64 first_frame);
 hipError_t launch_init_weights(hipStream_t st, int type, i64 n, const double* y, double* w, const unsigned char* is_pad);
 }  // namespace gfh

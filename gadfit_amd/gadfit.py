@@ -284,7 +284,7 @@ def gadf_fit(lambda_=None, lam_up=None, lam_down=None, accth=None, grad_chi2=Non
 
 
 def _batch_context(who):
-    """the session's context with its model current, for a batch call (gadf_fit_batch, gadf_fit_cube)"""
+    """the session's context with its model current, for a batch call (gadf_fit_batch, gadf_fit_cube, gadf_fit_frames)"""
     if _S.ctx is None:
         _S.ctx = _lib.Context(_S.device)
         if 'GADFIT_HIP_KEEP_J' not in os.environ:
@@ -341,6 +341,53 @@ def gadf_fit_batch(xs, ys, ws, pars, lambda_=None, lam_up=None, lam_down=None, a
     return out, res
 
 
+def _fit_cube(who, frames, x, Y, pars, sigma, DTD_min, lanes_per_fit, frames_per_put, kw):
+    """gadf_fit_cube and gadf_fit_frames: one body, the data spectrum-major (Y [n_fits][n_points]) or frame-major (F [n_points][n_fits])"""
+    _need_init()
+    if _S.n_datasets != 1:
+        raise GadfitError('%s needs a session with one dataset slot: gadf_init(f)' % who)
+    active = [i for i, a in enumerate(_S.active) if a]
+    if not active:
+        raise GadfitError('There are no active parameters.')
+    x = np.asarray(x, dtype=np.float64).ravel()
+    name, fits_axis = ('F', 1) if frames else ('Y', 0)
+    if not isinstance(Y, np.ndarray) or Y.ndim != 2 or Y.shape[1 - fits_axis] != x.size or Y.shape[fits_axis] < 1:
+        raise GadfitError('%s: F must be a numpy array [n_points][n_fits] with one row (a frame) per abscissa of x (%d)' % (who, x.size) if frames else
+                          '%s: Y must be a numpy array [n_fits][n_points] with one column per abscissa of x (%d)' % (who, x.size))
+    n_fits = Y.shape[fits_axis]
+    if _S.error_type == USER:
+        if sigma is None:
+            raise GadfitError('%s: USER errors requested but no sigma was given' % who)
+        sigma = np.asarray(sigma, dtype=np.float64)
+        if sigma.shape != Y.shape:
+            raise GadfitError('%s: sigma must have the shape of %s' % (who, name))
+    elif sigma is not None:
+        raise GadfitError('%s: sigma is taken under USER errors alone (gadf_set_errors)' % who)
+    pars = np.asarray(pars, dtype=np.float64)
+    if pars.shape != (n_fits, len(_S.fitfuncs[0].pars)):
+        raise GadfitError('%s: pars must be [n_fits][n_pars] = [%d][%d]' % (who, n_fits, len(_S.fitfuncs[0].pars)))
+    if _S.comm is not None:
+        raise GadfitError('%s: the fits are independent; split the cube over the ranks instead of sharing a communicator' % who)
+    _batch_context(who)
+    try:
+        if frames:
+            _S.ctx.set_batch_frames(x, Y, _S.error_type, None if sigma is None else 1.0 / sigma, frames_per_put)
+        else:
+            _S.ctx.set_batch_cube(x, Y, _S.error_type, None if sigma is None else 1.0 / sigma)
+        out, res, _ = _S.ctx.fit_batch(pars, active, DTD_min=DTD_min, lanes_per_fit=lanes_per_fit, **kw)
+    except _lib.GadfitHipError as e:
+        raise GadfitError(str(e))
+    return out, res
+
+
+def _cube_fit_args(lambda_, lam_up, lam_down, accth, rel_error, chi2_rel, chi2_abs, lam_incs, max_iter, damp_max, kw):
+    if 'lambda' in kw:
+        lambda_ = kw.pop('lambda')
+    return dict(lambda_=_f32(lambda_), lam_up=_f32(lam_up), lam_down=_f32(lam_down), accth=_f32(accth), rel_error=_f32(rel_error),
+                chi2_rel=_f32(chi2_rel), chi2_abs=_f32(chi2_abs), lam_incs=lam_incs, max_iter=max_iter,
+                damp_max=None if damp_max is None else int(damp_max), **{k: v for k, v in kw.items() if v is not None})
+
+
 def gadf_fit_cube(x, Y, pars, sigma=None, lambda_=None, lam_up=None, lam_down=None, accth=None, rel_error=None, chi2_rel=None,
                   chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, lanes_per_fit=None, **kw):
     """gadf_fit_batch over a data cube (gfh_set_batch_cube): every spectrum on the one grid ``x`` [n_points], ``Y`` [n_fits][n_points] a
@@ -348,40 +395,19 @@ def gadf_fit_cube(x, Y, pars, sigma=None, lambda_=None, lam_up=None, lam_down=No
     the session's ``gadf_set_errors`` type (NONE, SQRT_Y, PROPTO_Y, INVERSE_Y: no weight array exists anywhere; gadf_fit_batch ignores
     that type, this call takes it); under USER ``sigma`` [n_fits][n_points] is required and 1 / sigma is passed.  ``pars``, the fit
     arguments, ``lanes_per_fit`` and what is returned are gadf_fit_batch's."""
-    _need_init()
-    if 'lambda' in kw:
-        lambda_ = kw.pop('lambda')
-    if _S.n_datasets != 1:
-        raise GadfitError('gadf_fit_cube needs a session with one dataset slot: gadf_init(f)')
-    active = [i for i, a in enumerate(_S.active) if a]
-    if not active:
-        raise GadfitError('There are no active parameters.')
-    x = np.asarray(x, dtype=np.float64).ravel()
-    if not isinstance(Y, np.ndarray) or Y.ndim != 2 or Y.shape[1] != x.size or Y.shape[0] < 1:
-        raise GadfitError('gadf_fit_cube: Y must be a numpy array [n_fits][n_points] with one column per abscissa of x (%d)' % x.size)
-    if _S.error_type == USER:
-        if sigma is None:
-            raise GadfitError('gadf_fit_cube: USER errors requested but no sigma was given')
-        sigma = np.asarray(sigma, dtype=np.float64)
-        if sigma.shape != Y.shape:
-            raise GadfitError('gadf_fit_cube: sigma must have the shape of Y')
-    elif sigma is not None:
-        raise GadfitError('gadf_fit_cube: sigma is taken under USER errors alone (gadf_set_errors)')
-    pars = np.asarray(pars, dtype=np.float64)
-    if pars.shape != (Y.shape[0], len(_S.fitfuncs[0].pars)):
-        raise GadfitError('gadf_fit_cube: pars must be [n_fits][n_pars] = [%d][%d]' % (Y.shape[0], len(_S.fitfuncs[0].pars)))
-    if _S.comm is not None:
-        raise GadfitError('gadf_fit_cube: the fits are independent; split the cube over the ranks instead of sharing a communicator')
-    _batch_context('gadf_fit_cube')
-    try:
-        _S.ctx.set_batch_cube(x, Y, _S.error_type, None if sigma is None else 1.0 / sigma)
-        out, res, _ = _S.ctx.fit_batch(pars, active, DTD_min=DTD_min, lanes_per_fit=lanes_per_fit, lambda_=_f32(lambda_), lam_up=_f32(lam_up), lam_down=_f32(lam_down),
-                                       accth=_f32(accth), rel_error=_f32(rel_error), chi2_rel=_f32(chi2_rel), chi2_abs=_f32(chi2_abs),
-                                       lam_incs=lam_incs, max_iter=max_iter, damp_max=None if damp_max is None else int(damp_max),
-                                       **{k: v for k, v in kw.items() if v is not None})
-    except _lib.GadfitHipError as e:
-        raise GadfitError(str(e))
-    return out, res
+    return _fit_cube('gadf_fit_cube', False, x, Y, pars, sigma, DTD_min, lanes_per_fit, 0,
+                     _cube_fit_args(lambda_, lam_up, lam_down, accth, rel_error, chi2_rel, chi2_abs, lam_incs, max_iter, damp_max, kw))
+
+
+def gadf_fit_frames(x, F, pars, sigma=None, lambda_=None, lam_up=None, lam_down=None, accth=None, rel_error=None, chi2_rel=None,
+                    chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, lanes_per_fit=None, frames_per_put=0, **kw):
+    """gadf_fit_cube for a stack of frames (gfh_set_batch_frames): ``F`` [n_points][n_fits], one image per abscissa of ``x`` with the
+    fit (pixel) index fastest, as instruments deliver it -- C-contiguous in float64, float32 or uint16, uploaded as it is and
+    transposed into the cube on the device, so no ``np.ascontiguousarray(F.T)`` runs on the host.  ``sigma`` (under USER) is
+    frame-major as ``F``; ``frames_per_put``: frames per upload, 0 the library's rule.  Everything else, and what is returned (the
+    bits included), is gadf_fit_cube's on the transposed arrays."""
+    return _fit_cube('gadf_fit_frames', True, x, F, pars, sigma, DTD_min, lanes_per_fit, frames_per_put,
+                     _cube_fit_args(lambda_, lam_up, lam_down, accth, rel_error, chi2_rel, chi2_abs, lam_incs, max_iter, damp_max, kw))
 
 
 def gadf_print(begin=None, end=None, points=None, output=None, grouped=None, logplot=None):

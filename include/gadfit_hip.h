@@ -220,7 +220,8 @@ int  gfh_debug_mesh_stats(gfh_ctx* ctx, int64_t* out4);
  * lane; it is cut at the first pass that needs it, an error code if the card cannot provide it, and freed by gfh_destroy.  A group
  * handle reports member 0's card and the sum of the members' pools.  The blocks of a batch of independent fits (gfh_set_batch_data:
  * the spectra, their offsets, the parameter / result block and the images of gfh_batch_pass; after gfh_set_batch_cube the grid, the
- * samples in their narrow type and, under USER, the weights -- and nothing of the batch they replaced) are counted in out3[2] as well. */
+ * samples in their narrow type and, under USER, the weights -- and nothing of the batch they replaced; while gfh_batch_frames_put
+ * fills a cube, the staging blocks of a piece too) are counted in out3[2] as well. */
 int  gfh_device_memory(gfh_ctx* ctx, int64_t* out3);
 /* Generated HIP source for the current model and an active set (debug / AOT builds).
  * Returns bytes needed (including NUL); copies at most cap bytes. */
@@ -459,6 +460,42 @@ int  gfh_set_batch_cube(gfh_ctx* ctx, int64_t n_fits, int64_t n_points, const do
 /* The data form of the last batch launch of this context: -1 none yet, 0 ragged (gfh_set_batch_data), else a cube:
  * 1 + y_type + 3 * error_type (1 ... 15).  For tests that assert the dispatch. */
 int  gfh_debug_batch_form(gfh_ctx* ctx);
+/* A cube from a stack of frames.  Instruments deliver a detector image followed over time, echoes per voxel or a hyperspectral cube
+ * frame by frame, F [n_points][n_fits]: one image per abscissa with the pixel (fit) index fastest -- the transpose of what
+ * gfh_set_batch_cube takes.  Here the frames are uploaded as they are stored and a small model-independent kernel (k_frames_to_cube,
+ * gadfit_amd/csrc/frames.hip) transposes them through LDS into the cube's layout on the device; from there on the batch IS a cube:
+ * its bytes, and from them the bits of gfh_fit_batch / gfh_batch_pass, are those of gfh_set_batch_cube on the transposed array, no
+ * generated kernel differs, and gfh_debug_batch_form reports the same form.
+ *
+ * gfh_batch_frames_begin: geometry, grid, sample type and weight rule as gfh_set_batch_cube, with its checks in its order and
+ * wording under this name (there is no y and no w to check yet).  Replaces the batch held; allocates x, the cube y and, under USER,
+ * the cube w (counted by gfh_device_memory); marks all n_points frames as missing.  A compile-only context keeps geometry and form,
+ * then ends in "no GPU".
+ * gfh_batch_frames_put: frames [first_frame, first_frame + n_frames), y [n_frames][n_fits] in the begun sample type, w alike as
+ * doubles under USER (else NULL).  Frames may come in any order and any piece sizes; a frame put again holds the later data.  The
+ * piece is uploaded to staging blocks of its own size (counted by gfh_device_memory while they exist), transposed on the context's
+ * stream, and the call returns after the stream has drained: the caller may reuse its buffers.  When a put leaves no frame missing
+ * the staging blocks are freed and gfh_device_memory reports what gfh_set_batch_cube of the shape reports; a put into a complete
+ * batch takes and frees its own staging.  Refused, each with its own message, before the device is asked for: no batch begun (or the
+ * begun one replaced since by gfh_set_batch_data / gfh_set_batch_cube), first_frame < 0, n_frames < 1, a range past n_points, NULL
+ * y, USER without w, w under another rule.
+ * While frames are missing gfh_fit_batch and gfh_batch_pass are refused with a message that says how many of how many frames have not
+ * been put; gfh_batch_source, gfh_batch_prepare and gfh_set_batch_lanes need no data and are unaffected.
+ * gfh_set_batch_frames: begin + puts of a whole stack y [n_points][n_fits] (w alike under USER), frames_per_put frames each.
+ * frames_per_put 0: the largest count whose staging, samples and weights together, stays within 256 MiB, but at least one frame;
+ * negative values are refused, and so is everything gfh_set_batch_cube refuses.
+ * Not built: a Fortran entry, pinned or overlapped uploads, frames with a row pitch, other sample types, cubes over several cards. */
+int  gfh_batch_frames_begin(gfh_ctx* ctx, int64_t n_fits, int64_t n_points, const double* x, int y_type, int error_type);
+int  gfh_batch_frames_put(gfh_ctx* ctx, int64_t first_frame, int64_t n_frames, const void* y, const double* w);
+int  gfh_set_batch_frames(gfh_ctx* ctx, int64_t n_fits, int64_t n_points, const double* x, const void* y, int y_type, int error_type,
+                          const double* w, int64_t frames_per_put);
+/* Frames of the begun batch not yet put; -1: the batch held was not begun by gfh_batch_frames_begin. */
+int64_t gfh_debug_batch_frames_missing(gfh_ctx* ctx);
+/* Device time (HIP events) of the transposing kernels of every put since the last gfh_batch_frames_begin, in seconds. */
+double gfh_debug_batch_frames_seconds(gfh_ctx* ctx);
+/* Elements [first, first + count) of the cube held (row-major [n_fits][n_points]), as stored: which 0 the samples in their type,
+ * 1 the USER weights as doubles.  For tests that hold the cube's bytes. */
+int  gfh_debug_batch_read(gfh_ctx* ctx, int which, int64_t first, int64_t count, void* dst);
 
 /* ---- Jacobian_indices / dim (gadfit.F90:615-631) as a helper for callers */
 int  gfh_jacobian_indices(int n_datasets, int n_act, const int32_t* active_pars,

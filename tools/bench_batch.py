@@ -8,6 +8,7 @@ profiles/r05_small_fits.txt: 1000 points, a Gaussian on a background, 4 paramete
     python tools/bench_batch.py --workgroup [--points 1000,4096,16384,65536] [--sizes 64,256,1024,16384] [--models gauss4,exp4]
                                 [--registers] [--observed FILE [--observed-only]] [--out profiles/batch_workgroup.json]
     python tools/bench_batch.py --cube [--cells gauss4:64:16384:1000,...] [--registers] [--out profiles/batch_cube.json]
+    python tools/bench_batch.py --frames [--cells uint16:1:64:131072:1000,...] [--out profiles/batch_frames.json]
 
 Per batch size: warm-up launches, then the median of the timed launches -- device time from the HIP events around the kernel
 (gfh_fit_batch's `seconds`) and wall time around the whole call (parameters down, launch, results back).  Two yardsticks, neither of
@@ -42,7 +43,14 @@ weight), float32 / SQRT_Y, uint16 / SQRT_Y -- alternate launch by launch on one 
 of its own data, by the recipe of --rows; all five hold the same values, so they run the same passes (checked: the totals must be
 equal).  `upload_ms` is the wall time of the set call, median of 3.  `wins` is tests/batch_records.row_wins against the ragged
 form.  With --registers: the compiler's figures of the uint16 / SQRT_Y and float64 / USER units of model_exp2 and model_exp4 at the
-three lane forms (no GPU); model_exp2's must have no scratch."""
+three lane forms (no GPU); model_exp2's must have no scratch.
+--frames: a stack of frames F [points][fits] (gfh_set_batch_frames: uploaded as stored, transposed into the cube on the device) against
+the two routes a caller had before, over the shapes of the --cube table; cells are sample type:error type:lanes:fits:points.  Per cell
+the wall time of the set call through five routes that alternate call by call on one context: set_batch_cube of the already transposed
+array (the floor: the upload alone), np.ascontiguousarray(F.T) + set_batch_cube (the yardstick: the route before), set_batch_frames with
+the default pieces, with one put and with eight puts; the transposing kernel's device time (HIP events) and the bytes it moves per second.  fit_batch must
+return the same parameters and counts from all three routes, and at 131072 x 1000 uint16 the frames route must beat the host
+transpose by tests/batch_records.row_wins, or the tool fails."""
 import argparse
 import json
 import os
@@ -301,6 +309,127 @@ def cube_main(a):
     print('wrote', a.out)
 
 
+FRAMES_CELLS = 'uint16:1:64:131072:1000,uint16:1:16:131072:64,uint16:1:256:256:65536,float32:1:64:16384:1000,float64:4:64:16384:1000'
+FRAMES_ROUTES = ('cube', 'host_transpose', 'frames', 'frames_one_put', 'frames_8_puts')
+FRAMES_MUST_WIN = ('uint16', 131072, 1000)
+
+
+def _as_row(e):
+    """a wall-time record in the keys tests/batch_records.row_wins reads"""
+    return dict(device_ms=e['wall_ms'], device_ms_min=e['wall_ms_min'], device_ms_max=e['wall_ms_max'])
+
+
+def frames_main(a):
+    """a stack of frames (gfh_set_batch_frames) against the two routes a caller had before (see the module's text)"""
+    from tests import batch_records as RC
+    rec = dict(method='per cell (sample type, weight rule, lanes per fit, fits, points per spectrum) one stack of counts F [points][fits] -- round(%g x the '
+                      'gauss4 model), the data of --cube transposed -- set through five routes that alternate call by call on one context of one card in one '
+                      'run: cube = set_batch_cube of the already transposed array (the floor: the upload alone), host_transpose = '
+                      'np.ascontiguousarray(F.T) + set_batch_cube (the route before this call existed; under USER the weights are transposed too), '
+                      'frames = set_batch_frames with the default pieces (default_frames_per_put: where it equals points, the default IS one put and '
+                      'the two routes are one call), frames_one_put = set_batch_frames with one put of the whole stack, frames_8_puts = eight pieces; '
+                      'each round of the five begins one route later than the round before; wall time around the call(s), the median and the min-max of %d calls after %d warm-up calls; kernel_ms = device time of the transposing '
+                      'kernels of one set (HIP events, summed over the puts, and under USER over both kernels), kernel_GB_per_s = bytes read plus '
+                      'bytes written over it; fit_batch (lambda0 = %g, max_iter = %d) returns the same parameters and counts from cube, '
+                      'host_transpose and frames (checked); wins = tests/batch_records.row_wins on the wall times; no counter pass was made, no '
+                      'share of a peak is claimed' % (CUBE_SCALE, a.launches, a.warmup, LAMBDA0, MAX_ITER), measurements=[])
+    kw = dict(lambda_=LAMBDA0, max_iter=MAX_ITER)
+    m = ROW_MODELS['gauss4']
+    for cell in a.cells.split(','):
+        tname, et, lanes, nf, n = cell.split(':')
+        et, lanes, nf, n = int(et), int(lanes), int(nf), int(n)
+        dtype = np.dtype(tname)
+        t0 = time.perf_counter()
+        xs, y, _ = spectra_flat('gauss4', nf, n)
+        x = xs[:n].copy()
+        del xs
+        counts = np.round(CUBE_SCALE * y).reshape(nf, n)
+        del y
+        if counts.min() < 1 or counts.max() > 65535:
+            sys.exit('the counts leave uint16')
+        Y = counts.astype(dtype)
+        W = 1.0 / np.sqrt(counts) if et == 4 else None
+        del counts
+        F = np.ascontiguousarray(Y.T)                   # the stack as the instrument delivers it
+        WF = None if W is None else np.ascontiguousarray(W.T)
+        start = np.tile(m['start'] * np.array([CUBE_SCALE, 1.0, 1.0, CUBE_SCALE]), (nf, 1))
+        print('%-8s rule %d %3d lanes %6d fits x %5d points: data in %.1f s' % (tname, et, lanes, nf, n, time.perf_counter() - t0), flush=True)
+        ctx = _lib.Context(0)
+        ctx.set_model(trace_model(m['model'], m['n_pars']))
+        ctx.set_batch_lanes(lanes)
+
+        def route(name):
+            t = time.perf_counter()
+            if name == 'cube':
+                ctx.set_batch_cube(x, Y, et, W)
+            elif name == 'host_transpose':
+                ctx.set_batch_cube(x, np.ascontiguousarray(F.T), et, None if WF is None else np.ascontiguousarray(WF.T))
+            else:
+                ctx.set_batch_frames(x, F, et, WF, frames_per_put=n if name == 'frames_one_put' else (n + 7) // 8 if name == 'frames_8_puts' else 0)
+            return time.perf_counter() - t
+        wall = {r: [] for r in FRAMES_ROUTES}; kern = {r: [] for r in FRAMES_ROUTES[2:]}
+        for it in range(a.warmup + a.launches):
+            # the routes alternate call by call, and the round begins one route later each time: a drift of the host or the card meets
+            # all alike, and no route is always the one behind the host transpose's half second of CPU work
+            for r in FRAMES_ROUTES[it % len(FRAMES_ROUTES):] + FRAMES_ROUTES[:it % len(FRAMES_ROUTES)]:
+                t = route(r)
+                if it >= a.warmup:
+                    wall[r].append(t)
+                    if r in kern:
+                        kern[r].append(ctx.batch_frames_seconds())
+        out = {}
+        for r in FRAMES_ROUTES[:3]:
+            route(r)
+            p, res, _ = ctx.fit_batch(start, m['active'], **kw)
+            if ctx.batch_lanes_used() != lanes or ctx.batch_form_used() != ('cube', (np.float64, np.float32, np.uint16).index(dtype.type), et):
+                sys.exit('the launch did not take the form asked for')
+            out[r] = (p, res)
+        p0, r0 = out['cube']
+        for r in FRAMES_ROUTES[1:3]:
+            p, res = out[r]
+            if not (np.array_equal(p.view(np.uint64), p0.view(np.uint64)) and
+                    all(np.array_equal(res[f], r0[f]) for f in ('n_sweeps', 'n_chi2', 'n_omega', 'exit_reason', 'iterations'))):
+                sys.exit('%s does not return what set_batch_cube returns' % r)
+        mem = ctx.device_memory()['workspace_pool']
+        ctx.close()
+        per_frame = nf * (dtype.itemsize + (8 if et == 4 else 0))
+        moved = 2 * n * per_frame
+        entry = dict(sample_type=tname, error_type=et, lanes=lanes, fits=nf, points=n, stack_MB=n * per_frame / 1e6,
+                     default_frames_per_put=int(min(n, max(1, (256 << 20) // per_frame))), routes={}, fits_equal=True,
+                     finite=bool(np.all(np.isfinite(p0))), device_bytes_held=int(mem))
+        for r in FRAMES_ROUTES:
+            e = dict(wall_ms=1e3 * statistics.median(wall[r]), wall_ms_min=1e3 * min(wall[r]), wall_ms_max=1e3 * max(wall[r]))
+            if r in kern:
+                k = statistics.median(kern[r])
+                e.update(kernel_ms=1e3 * k, kernel_ms_min=1e3 * min(kern[r]), kernel_ms_max=1e3 * max(kern[r]), kernel_GB_per_s=moved / k / 1e9)
+            entry['routes'][r] = e
+        for r in FRAMES_ROUTES[1:]:
+            e = entry['routes'][r]
+            e['over_cube_wall_time'] = e['wall_ms'] / entry['routes']['cube']['wall_ms']
+        for r in FRAMES_ROUTES[2:]:
+            e = entry['routes'][r]
+            e['over_host_transpose_wall_time'] = e['wall_ms'] / entry['routes']['host_transpose']['wall_ms']
+            e['wins'] = bool(RC.row_wins(_as_row(e), _as_row(entry['routes']['host_transpose'])))
+            e['loses'] = bool(RC.row_wins(_as_row(entry['routes']['host_transpose']), _as_row(e)))
+        one, dflt = entry['routes']['frames_one_put'], entry['routes']['frames']
+        entry['default_pieces_against_one_put'] = ('faster' if RC.row_wins(_as_row(dflt), _as_row(one)) else
+                                                   'slower' if RC.row_wins(_as_row(one), _as_row(dflt)) else 'within the spreads')
+        rec['measurements'].append(entry)
+        print('\n'.join('   %-15s wall %9.2f ms [%.2f, %.2f]%s%s' % (
+            r, e['wall_ms'], e['wall_ms_min'], e['wall_ms_max'],
+            '' if r == 'cube' else ', %.2f x the upload alone' % e['over_cube_wall_time'],
+            '' if 'kernel_ms' not in e else ', kernel %.3f ms = %.0f GB/s, %.3f of host_transpose%s' % (
+                e['kernel_ms'], e['kernel_GB_per_s'], e['over_host_transpose_wall_time'], ' -> wins' if e['wins'] else ' -> loses' if e['loses'] else ''))
+            for r, e in entry['routes'].items()), flush=True)
+        with open(a.out, 'w') as fh:          # (after every cell: a run that is cut short leaves what it measured)
+            json.dump(rec, fh, indent=1, sort_keys=True)
+            fh.write('\n')
+        if (tname, nf, n) == FRAMES_MUST_WIN and not entry['routes']['frames']['wins']:
+            sys.exit('at %d x %d %s the frames route does not beat the host transpose by more than the two spreads' % (nf, n, tname))
+        del Y, W, F, WF
+    print('wrote', a.out)
+
+
 def rows_main(a, points, lanes_list):
     """the two forms against each other over spectrum lengths (see the module's text)"""
     from tests import batch_records as RC
@@ -457,7 +586,8 @@ def main():
     ap.add_argument('--rows', action='store_true', help='the two forms of the batch kernels against each other, into profiles/batch_rows.json')
     ap.add_argument('--workgroup', action='store_true', help='the 256-lane form of the batch kernels against the 64-lane form, into profiles/batch_workgroup.json')
     ap.add_argument('--cube', action='store_true', help='a batch as a data cube against the ragged form of the same spectra, into profiles/batch_cube.json')
-    ap.add_argument('--cells', default=CUBE_CELLS, help='with --cube: model:lanes:fits:points, ...')
+    ap.add_argument('--frames', action='store_true', help='a stack of frames against the host transpose and the upload alone, into profiles/batch_frames.json')
+    ap.add_argument('--cells', default=None, help='with --cube: model:lanes:fits:points, ...; with --frames: sample type:error type:lanes:fits:points, ...')
     ap.add_argument('--models', default='gauss4,exp4', help='with --workgroup: the models measured by this call (the record keeps the others)')
     ap.add_argument('--registers', action='store_true', help='with --rows or --workgroup: only the register figures of the four kernels into the record; no GPU is needed')
     ap.add_argument('--sizes', default='1024,16384,131072')
@@ -471,7 +601,9 @@ def main():
                                                                  'nothing is timed, no GPU is needed')
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'batch_cube.json' if a.cube else 'batch_workgroup.json' if a.workgroup else 'batch_rows.json' if a.rows else 'batch_fits.json')
+        a.out = os.path.join(ROOT, 'profiles', 'batch_frames.json' if a.frames else 'batch_cube.json' if a.cube else 'batch_workgroup.json' if a.workgroup else 'batch_rows.json' if a.rows else 'batch_fits.json')
+    if a.cells is None:
+        a.cells = FRAMES_CELLS if a.frames else CUBE_CELLS
     if (a.rows or a.workgroup or a.cube) and a.registers:
         rec = json.load(open(a.out)) if os.path.exists(a.out) else {}
         rec['registers'] = cube_registers_record() if a.cube else registers_record((256,) if a.workgroup else (64, 16))
@@ -496,6 +628,8 @@ def main():
         return
     if a.launches < 5:
         sys.exit('at least 5 timed launches')
+    if a.frames:
+        return frames_main(a)
     if a.cube:
         return cube_main(a)
     if a.workgroup:
