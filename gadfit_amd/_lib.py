@@ -104,6 +104,8 @@ SYMBOLS = {
     'gfh_set_batch_data': (_i, [_vp, _i64, C.POINTER(_i64), _dp, _dp, _dp]),
     'gfh_fit_batch': (_i, [_vp, _dp, _i, _ip, C.POINTER(FitOptions), C.POINTER(BatchResult), _dp]),
     'gfh_batch_pass': (_i, [_vp, _dp, _i, _ip, _dp, _dp, _dp]),
+    'gfh_batch_covariance': (_i, [_vp, _dp, _i, _ip, _i, _dp, _dp, _ip]),
+    'gfh_fit_batch_errors': (_i, [_vp, _dp, _i, _ip, C.POINTER(FitOptions), C.POINTER(BatchResult), _i, _dp, _dp, _ip, _dp]),
     'gfh_batch_source': (_i64, [_vp, _i, _ip, C.c_char_p, _i64]),
     'gfh_batch_prepare': (_i, [_vp, _i, _ip]),
     'gfh_set_batch_lanes': (_i, [_vp, _i]),
@@ -681,26 +683,59 @@ class Context:
         p, a, n = self._batch_args('fit_batch', pars, active)
         if lanes_per_fit is not None:
             self.set_batch_lanes(lanes_per_fit)
+        o, _keep = self._batch_options('fit_batch', a, DTD_min, kw)
+        res = np.zeros(n, dtype=BATCH_RESULT_DTYPE)
+        sec = C.c_double()
+        self._chk(lib().gfh_fit_batch(self._h, dp(p), a.size, ip(a), C.byref(o), res.ctypes.data_as(C.POINTER(BatchResult)),
+                                      C.cast(C.byref(sec), _dp)))
+        return p, res.view(np.recarray), sec.value
+
+    def _batch_options(self, who, a, DTD_min, kw):
+        """the FitOptions of a batch fit from fit()'s keyword arguments, and what must outlive the call with them"""
         o = FitOptions()
         for k, v in kw.items():
             if v is None:
                 continue
             name = 'lambda' if k in ('lambda_', 'lam', 'lambda') else k
             if 'has_' + name not in _FIT_OPTION_FIELDS:
-                raise GadfitHipError('fit_batch: unknown fit argument %r' % k)
+                raise GadfitHipError('%s: unknown fit argument %r' % (who, k))
             setattr(o, 'lambda_' if name == 'lambda' else name, v)
             setattr(o, 'has_' + name, 1)
         o.umnigh_a = 0.5
+        dm = None
         if DTD_min is not None:
             dm = np.ascontiguousarray(DTD_min, dtype=np.float64)
             if dm.size != a.size:
-                raise GadfitHipError('fit_batch: DTD_min must hold one value per active parameter (%d), got %d' % (a.size, dm.size))
+                raise GadfitHipError('%s: DTD_min must hold one value per active parameter (%d), got %d' % (who, a.size, dm.size))
             o.DTD_min = dp(dm)
+        return o, dm
+
+    def fit_batch_errors(self, pars, active, scale=False, DTD_min=None, lanes_per_fit=None, **kw):
+        """fit_batch and, behind it on the device, each fit's parameter covariance at the fitted parameters: returns the fitted
+        parameters, the records, (cov [n_fits][na][na], sigma [n_fits][na], info [n_fits]) as batch_covariance returns them and the
+        device time of the two launches in seconds.  The parameters and records are fit_batch's bits -- gfh_fit_batch_errors"""
+        p, a, n = self._batch_args('fit_batch_errors', pars, active)
+        if lanes_per_fit is not None:
+            self.set_batch_lanes(lanes_per_fit)
+        o, _keep = self._batch_options('fit_batch_errors', a, DTD_min, kw)
         res = np.zeros(n, dtype=BATCH_RESULT_DTYPE)
+        cov = np.zeros((n, a.size, a.size)); sigma = np.zeros((n, a.size)); info = np.zeros(n, dtype=np.int32)
         sec = C.c_double()
-        self._chk(lib().gfh_fit_batch(self._h, dp(p), a.size, ip(a), C.byref(o), res.ctypes.data_as(C.POINTER(BatchResult)),
-                                      C.cast(C.byref(sec), _dp)))
-        return p, res.view(np.recarray), sec.value
+        self._chk(lib().gfh_fit_batch_errors(self._h, dp(p), a.size, ip(a), C.byref(o), res.ctypes.data_as(C.POINTER(BatchResult)),
+                                             int(scale), dp(cov), dp(sigma), ip(info), C.cast(C.byref(sec), _dp)))
+        return p, res.view(np.recarray), (cov, sigma, info), sec.value
+
+    def batch_covariance(self, pars, active, scale=False, lanes_per_fit=None):
+        """(cov [n_fits][na][na], sigma [n_fits][na], info [n_fits]) of every spectrum at pars [n_fits][n_pars]: cov = (J^T J)^-1
+        (the reference's LMsolver::getInvJTJ), under scale=True times the fit's chi2 / dof; sigma = sqrt of its diagonal; info 0, or
+        j + 1 where pivot j of the Cholesky factor failed (that fit's cov and sigma are NaN).  Rows and columns in the order of
+        `active`; lanes_per_fit as fit_batch -- gfh_batch_covariance"""
+        p, a, n = self._batch_args('batch_covariance', pars, active)
+        if lanes_per_fit is not None:
+            self.set_batch_lanes(lanes_per_fit)
+        cov = np.zeros((n, a.size, a.size)); sigma = np.zeros((n, a.size)); info = np.zeros(n, dtype=np.int32)
+        self._chk(lib().gfh_batch_covariance(self._h, dp(p), a.size, ip(a), int(scale), dp(cov), dp(sigma), ip(info)))
+        return cov, sigma, info
 
     def batch_pass(self, pars, active, lanes_per_fit=None):
         """(JTJ [n_fits][na][na], JTres [n_fits][na], chi2 [n_fits]) of every spectrum at pars [n_fits][n_pars] -- gfh_batch_pass;

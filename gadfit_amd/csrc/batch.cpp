@@ -1,5 +1,5 @@
 // batch.cpp -- batched independent fits: many Levenberg-Marquardt fits of ONE model in ONE kernel launch, each with its own data,
-// start parameters, lambda history and exit (gfh_set_batch_data, gfh_fit_batch, gfh_batch_pass, gfh_batch_source, gfh_batch_prepare,
+// start parameters, lambda history and exit (gfh_set_batch_data, gfh_fit_batch, gfh_batch_pass, gfh_batch_covariance, gfh_fit_batch_errors, gfh_batch_source, gfh_batch_prepare,
 // gfh_set_batch_lanes; gfh_set_batch_cube: the same batch as a cube on one grid with narrow samples; gfh_batch_frames_begin,
 // gfh_batch_frames_put, gfh_set_batch_frames: that cube from a frame-major stack, transposed on the device by frames.hip).  This file validates, uploads, compiles / loads and launches; the loop itself (gadfit.F90:670-915) is the
 // generated kernel gfh_k_fit_batch (batch_fit.hip; codegen.cpp, emit_batch_kernels), a wave per fit or -- gfh_set_batch_lanes(16) -- a
@@ -98,7 +98,7 @@ int check_cube(gfh_ctx* c, const char* who, bool null_arg, const char* required,
   return 0;
 }
 
-// the translation unit of an active set with the two batch kernels: generated, compiled and (load) loaded once per context, kept
+// the translation unit of an active set with the three batch kernels: generated, compiled and (load) loaded once per context, kept
 // in the context's kernel cache under a key no plain active set has, so that a new model or gfh_destroy releases it with the rest
 GenConfig batch_config(const gfh_ctx* c, int lanes) {
   GenConfig cfg;                    // the defaults, not the context's current switches: one form per (model, active set, lanes per fit)
@@ -134,10 +134,97 @@ int batch_kernels(gfh_ctx* c, const std::vector<int32_t>& active, int lanes, boo
     if (!load_kernels(code, &mk, &err)) return fail(c, err);
     publish_loaded(c->device, skey, mk);
   }
-  if (!mk.fit_batch || !mk.batch_pass) { release_loaded(c->device, &mk); return fail(c, "the batch kernels are missing from their code object"); }
+  if (!mk.fit_batch || !mk.batch_pass || !mk.batch_cov) { release_loaded(c->device, &mk); return fail(c, "the batch kernels are missing from their code object"); }
   mk.n_active = (int)active.size();
   ModelKernels* p = &c->kernel_cache.emplace(key, mk).first->second;
   if (out) *out = p;
+  return 0;
+}
+
+// The error outputs of a call (gfh_batch_covariance, gfh_fit_batch_errors) and their block on the device, written by gfh_k_batch_cov
+// (batch_cov.hip): [cov n_fits x na x na | sigma n_fits x na | info n_fits], the ints last so that the doubles stay aligned
+struct BatchErrors { int scale; double* cov; double* sigma; int32_t* info; };
+int check_errors(gfh_ctx* c, const char* who, const BatchErrors& e) {
+  const std::string w(who);
+  if (!e.cov || !e.sigma || !e.info) return fail(c, w + ": null argument");
+  if (e.scale != 0 && e.scale != 1)
+    return fail(c, w + ": scale is 0 (the inverse of J^T J) or 1 (that times chi2 / dof), got " + std::to_string(e.scale));
+  return 0;
+}
+size_t errors_bytes(int64_t nf, int na) { return sizeof(double) * (size_t)nf * ((size_t)na * na + na) + sizeof(int32_t) * (size_t)nf; }
+void errors_out(const char* h, int64_t nf, int na, const BatchErrors& e) {
+  const size_t cb = sizeof(double) * (size_t)nf * na * na, sb = sizeof(double) * (size_t)nf * na;
+  memcpy(e.cov, h, cb); memcpy(e.sigma, h + cb, sb); memcpy(e.info, h + cb + sb, sizeof(int32_t) * (size_t)nf);
+}
+// gfh_k_batch_cov over the batch held at the parameter block `pars` of the device, into the block `out` (errors_bytes)
+int launch_cov(gfh_ctx* c, ModelKernels* mk, int lanes, int na, int scale, void* pars, char* out) {
+  const int64_t nf = c->batch.n_fits; const int per_wg = 256 / lanes;
+  void* x = c->batch.x.p; void* y = c->batch.y.p; void* w = c->batch.w.p; void* off = c->batch.off_d.p;
+  long long npts = c->batch.max_points;      // a cube's kernels take n_points where the ragged ones take the offsets (GFH_BARGS)
+  void* cov = out; void* sigma = out + sizeof(double) * (size_t)nf * na * na; void* info = out + sizeof(double) * (size_t)nf * ((size_t)na * na + na);
+  long long n = nf; void* stp = c->status.p;
+  void* args[] = {&x, &y, &w, c->batch.cube ? (void*)&npts : (void*)&off, &pars, &scale, &cov, &sigma, &info, &n, &stp};
+  HIPCHK(c, hipModuleLaunchKernel(mk->batch_cov, (unsigned)((nf + per_wg - 1) / per_wg), 1, 1, 256, 1, 1, 0, c->stream, args, nullptr));
+  c->batch.last_lanes = lanes; c->batch.last_form = data_form(c);
+  return 0;
+}
+// The body of gfh_fit_batch and gfh_fit_batch_errors (errors: NULL, or where the second launch's outputs go), under the caller's name
+int fit_batch(gfh_ctx* c, const char* who_, double* pars, int na, const int32_t* active, const gfh_fit_options* o, gfh_batch_result* results,
+              double* seconds, const BatchErrors* errors) {
+  const std::string who(who_);
+  if (check_context(c, who_) || check_model(c, who_, na, active)) return 1;
+  if (!pars || !results) return fail(c, who + ": null argument");
+  if (errors && check_errors(c, who_, *errors)) return 1;
+  gfh_fit_options defaults; memset(&defaults, 0, sizeof defaults);
+  if (!o) o = &defaults;
+  // the options of gadf_fit a device-resident loop does not carry
+  if (o->has_uphill && o->uphill != 0) return fail(c, who + ": uphill != 0 is not carried by the batch kernel");
+  if (o->has_nielsen && o->nielsen) return fail(c, who + ": the nielsen lambda strategy is not carried by the batch kernel");
+  if (o->has_umnigh && o->umnigh) return fail(c, who + ": the umnigh lambda strategy is not carried by the batch kernel");
+  if (o->has_grad_chi2) return fail(c, who + ": the grad_chi2 test is not carried by the batch kernel");
+  if (o->has_cos_phi) return fail(c, who + ": the cos_phi test is not carried by the batch kernel");
+  if (o->has_rel_error_global) return fail(c, who + ": rel_error_global has no meaning for independent fits");
+  LmOptions lo;
+  if (const char* refusal = resolve_lm_options(*o, &lo)) return fail(c, refusal);                        // gadfit.F90:575-578
+  if (!o->has_max_iter || o->max_iter < 0) return fail(c, who + ": max_iter is required (a loop that runs on the device must be bounded)");
+  if (check_geometry(c, who_, na) || check_frames(c, who_)) return 1;
+  BatchOpts bo; memset(&bo, 0, sizeof bo);
+  bo.lambda = lo.lambda; bo.lam_up = lo.lam_up; bo.lam_down = lo.lam_down; bo.lam_incs = lo.lam_incs;      // gadfit.F90:568-584 (lm_options.h)
+  bo.use_accth = lo.use_accth; bo.accth = o->accth;
+  bo.has_chi2_abs = o->has_chi2_abs != 0; bo.chi2_abs = o->chi2_abs;
+  bo.has_chi2_rel = o->has_chi2_rel != 0; bo.chi2_rel = o->chi2_rel;
+  bo.has_rel_error = o->has_rel_error != 0; bo.rel_error = o->rel_error;
+  bo.has_max_iter = 1; bo.max_iter = o->max_iter;
+  bo.damp_plain = lo.damp_plain;
+  if (o->DTD_min) for (int j = 0; j < na; j++) bo.dtd_min[j] = o->DTD_min[j];                            // gadfit.F90:641-646 (the same for every fit)
+  NEED_GPU(c);
+  if (!c->batch.on_device) return fail(c, who + ": no batch data on the device (gfh_set_batch_data, gfh_set_batch_cube)");
+  gfh::Range range("gadfit gfh_fit_batch");
+  ModelKernels* mk = nullptr;
+  const int lanes = batch_lanes(c, na), per_wg = 256 / lanes;
+  if (batch_kernels(c, std::vector<int32_t>(active, active + na), lanes, true, &mk)) return 1;
+  const int64_t nf = c->batch.n_fits; const int np = c->model.n_pars;
+  const size_t pb = sizeof(double) * (size_t)nf * (size_t)np, rb = sizeof(gfh_batch_result) * (size_t)nf;
+  const size_t eb = errors ? errors_bytes(nf, na) : 0;          // [pars | records | covariances, standard errors, info]: one block, one copy back
+  if (dev_alloc(c, c->batch.io, pb + rb + eb)) return 1;
+  c->batch.host.resize(pb + rb + eb);
+  harvest_events(c);
+  HIPCHK(c, hipMemcpyAsync(c->batch.io.p, pars, pb, hipMemcpyHostToDevice, c->stream));
+  void* x = c->batch.x.p; void* y = c->batch.y.p; void* w = c->batch.w.p; void* off = c->batch.off_d.p;
+  long long npts = c->batch.max_points;      // a cube's kernels take n_points where the ragged ones take the offsets (GFH_BARGS)
+  void* dp = c->batch.io.p; void* recs = c->batch.io.as<char>() + pb; long long n = nf; void* stp = c->status.p;
+  void* args[] = {&x, &y, &w, c->batch.cube ? (void*)&npts : (void*)&off, &dp, &bo, &recs, &n, &stp};
+  HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+  HIPCHK(c, hipModuleLaunchKernel(mk->fit_batch, (unsigned)((nf + per_wg - 1) / per_wg), 1, 1, 256, 1, 1, 0, c->stream, args, nullptr));
+  c->batch.last_lanes = lanes; c->batch.last_form = data_form(c);
+  if (errors && launch_cov(c, mk, lanes, na, errors->scale, dp, c->batch.io.as<char>() + pb + rb)) return 1;
+  HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->batch.host.data(), c->batch.io.p, pb + rb + eb, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  memcpy(pars, c->batch.host.data(), pb);
+  memcpy(results, c->batch.host.data() + pb, rb);
+  if (errors) errors_out(c->batch.host.data() + pb + rb, nf, na, *errors);
+  if (seconds) *seconds = 1e-3 * ev_ms(c->ev[0], c->ev[1]);
   return 0;
 }
 
@@ -315,57 +402,45 @@ int gfh_debug_batch_read(gfh_ctx* c, int which, int64_t first, int64_t count, vo
 // a row of 16 lanes or a workgroup of 256 per fit.
 int gfh_fit_batch(gfh_ctx* c, double* pars, int na, const int32_t* active, const gfh_fit_options* o, gfh_batch_result* results,
                   double* seconds) try {
-  if (check_context(c, "gfh_fit_batch") || check_model(c, "gfh_fit_batch", na, active)) return 1;
-  if (!pars || !results) return fail(c, "gfh_fit_batch: null argument");
-  gfh_fit_options defaults; memset(&defaults, 0, sizeof defaults);
-  if (!o) o = &defaults;
-  // the options of gadf_fit a device-resident loop does not carry
-  if (o->has_uphill && o->uphill != 0) return fail(c, "gfh_fit_batch: uphill != 0 is not carried by the batch kernel");
-  if (o->has_nielsen && o->nielsen) return fail(c, "gfh_fit_batch: the nielsen lambda strategy is not carried by the batch kernel");
-  if (o->has_umnigh && o->umnigh) return fail(c, "gfh_fit_batch: the umnigh lambda strategy is not carried by the batch kernel");
-  if (o->has_grad_chi2) return fail(c, "gfh_fit_batch: the grad_chi2 test is not carried by the batch kernel");
-  if (o->has_cos_phi) return fail(c, "gfh_fit_batch: the cos_phi test is not carried by the batch kernel");
-  if (o->has_rel_error_global) return fail(c, "gfh_fit_batch: rel_error_global has no meaning for independent fits");
-  LmOptions lo;
-  if (const char* refusal = resolve_lm_options(*o, &lo)) return fail(c, refusal);                        // gadfit.F90:575-578
-  if (!o->has_max_iter || o->max_iter < 0) return fail(c, "gfh_fit_batch: max_iter is required (a loop that runs on the device must be bounded)");
-  if (check_geometry(c, "gfh_fit_batch", na) || check_frames(c, "gfh_fit_batch")) return 1;
-  BatchOpts bo; memset(&bo, 0, sizeof bo);
-  bo.lambda = lo.lambda; bo.lam_up = lo.lam_up; bo.lam_down = lo.lam_down; bo.lam_incs = lo.lam_incs;      // gadfit.F90:568-584 (lm_options.h)
-  bo.use_accth = lo.use_accth; bo.accth = o->accth;
-  bo.has_chi2_abs = o->has_chi2_abs != 0; bo.chi2_abs = o->chi2_abs;
-  bo.has_chi2_rel = o->has_chi2_rel != 0; bo.chi2_rel = o->chi2_rel;
-  bo.has_rel_error = o->has_rel_error != 0; bo.rel_error = o->rel_error;
-  bo.has_max_iter = 1; bo.max_iter = o->max_iter;
-  bo.damp_plain = lo.damp_plain;
-  if (o->DTD_min) for (int j = 0; j < na; j++) bo.dtd_min[j] = o->DTD_min[j];                            // gadfit.F90:641-646 (the same for every fit)
-  NEED_GPU(c);
-  if (!c->batch.on_device) return fail(c, "gfh_fit_batch: no batch data on the device (gfh_set_batch_data, gfh_set_batch_cube)");
-  gfh::Range range("gadfit gfh_fit_batch");
-  ModelKernels* mk = nullptr;
-  const int lanes = batch_lanes(c, na), per_wg = 256 / lanes;
-  if (batch_kernels(c, std::vector<int32_t>(active, active + na), lanes, true, &mk)) return 1;
-  const int64_t nf = c->batch.n_fits; const int np = c->model.n_pars;
-  const size_t pb = sizeof(double) * (size_t)nf * (size_t)np, rb = sizeof(gfh_batch_result) * (size_t)nf;
-  if (dev_alloc(c, c->batch.io, pb + rb)) return 1;
-  c->batch.host.resize(pb + rb);
-  harvest_events(c);
-  HIPCHK(c, hipMemcpyAsync(c->batch.io.p, pars, pb, hipMemcpyHostToDevice, c->stream));
-  void* x = c->batch.x.p; void* y = c->batch.y.p; void* w = c->batch.w.p; void* off = c->batch.off_d.p;
-  long long npts = c->batch.max_points;      // a cube's kernels take n_points where the ragged ones take the offsets (GFH_BARGS)
-  void* dp = c->batch.io.p; void* recs = c->batch.io.as<char>() + pb; long long n = nf; void* stp = c->status.p;
-  void* args[] = {&x, &y, &w, c->batch.cube ? (void*)&npts : (void*)&off, &dp, &bo, &recs, &n, &stp};
-  HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-  HIPCHK(c, hipModuleLaunchKernel(mk->fit_batch, (unsigned)((nf + per_wg - 1) / per_wg), 1, 1, 256, 1, 1, 0, c->stream, args, nullptr));
-  c->batch.last_lanes = lanes; c->batch.last_form = data_form(c);
-  HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->batch.host.data(), c->batch.io.p, pb + rb, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  memcpy(pars, c->batch.host.data(), pb);
-  memcpy(results, c->batch.host.data() + pb, rb);
-  if (seconds) *seconds = 1e-3 * ev_ms(c->ev[0], c->ev[1]);
-  return 0;
+  return fit_batch(c, "gfh_fit_batch", pars, na, active, o, results, seconds, nullptr);
 } catch (const std::exception& e) { return fail(c, std::string("gfh_fit_batch: ") + e.what()); }
+
+// gfh_fit_batch and, behind it on the same stream, gfh_k_batch_cov at the fitted parameters, which stay on the device between the two
+// launches: parameters, records, covariances, standard errors and info come back in the one copy.  The fit's launch and its
+// arguments are gfh_fit_batch's, so its outputs are that call's bits.  *seconds: the device time of both launches.
+int gfh_fit_batch_errors(gfh_ctx* c, double* pars, int na, const int32_t* active, const gfh_fit_options* o, gfh_batch_result* results,
+                         int scale, double* cov, double* sigma, int32_t* info, double* seconds) try {
+  const BatchErrors e{scale, cov, sigma, info};
+  return fit_batch(c, "gfh_fit_batch_errors", pars, na, active, o, results, seconds, &e);
+} catch (const std::exception& e) { return fail(c, std::string("gfh_fit_batch_errors: ") + e.what()); }
+
+// (J^T J)^-1 of every spectrum at given parameters (scale 0: the reference's LMsolver::getInvJTJ) or that times chi2 / dof (scale
+// 1), and the standard errors sqrt of its diagonal: cov [n_fits][na * na] (symmetric, both triangles), sigma [n_fits][na], info
+// [n_fits] (0, or j + 1: pivot j of the fit's Cholesky factor was not positive and finite -- its cov and sigma are NaN), in the
+// caller's order of the active parameters.  On whichever batch data is held, as gfh_batch_pass; one launch, one copy back.
+int gfh_batch_covariance(gfh_ctx* c, const double* pars, int na, const int32_t* active, int scale, double* cov, double* sigma,
+                         int32_t* info) try {
+  if (check_context(c, "gfh_batch_covariance") || check_model(c, "gfh_batch_covariance", na, active)) return 1;
+  const BatchErrors e{scale, cov, sigma, info};
+  if (!pars) return fail(c, "gfh_batch_covariance: null argument");
+  if (check_errors(c, "gfh_batch_covariance", e)) return 1;
+  if (check_geometry(c, "gfh_batch_covariance", na) || check_frames(c, "gfh_batch_covariance")) return 1;
+  NEED_GPU(c);
+  if (!c->batch.on_device) return fail(c, "gfh_batch_covariance: no batch data on the device (gfh_set_batch_data, gfh_set_batch_cube)");
+  ModelKernels* mk = nullptr;
+  const int lanes = batch_lanes(c, na);
+  if (batch_kernels(c, std::vector<int32_t>(active, active + na), lanes, true, &mk)) return 1;
+  const int64_t nf = c->batch.n_fits;
+  const size_t pb = sizeof(double) * (size_t)nf * (size_t)c->model.n_pars, eb = errors_bytes(nf, na);
+  if (dev_alloc(c, c->batch.io, pb) || dev_alloc(c, c->batch.img, eb)) return 1;
+  c->batch.host.resize(eb);
+  HIPCHK(c, hipMemcpyAsync(c->batch.io.p, pars, pb, hipMemcpyHostToDevice, c->stream));
+  if (launch_cov(c, mk, lanes, na, scale, c->batch.io.p, c->batch.img.as<char>())) return 1;
+  HIPCHK(c, hipMemcpyAsync(c->batch.host.data(), c->batch.img.p, eb, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  errors_out(c->batch.host.data(), nf, na, e);
+  return 0;
+} catch (const std::exception& e) { return fail(c, std::string("gfh_batch_covariance: ") + e.what()); }
 
 // STEP 1 + 2 (gadfit.F90:675-699) of every spectrum at given parameters: J^T J [n_fits][na * na] (symmetric, both triangles),
 // J^T r [n_fits][na], chi2 [n_fits] -- for callers with their own loop.

@@ -43,5 +43,8 @@ const char kBatchCube[] = {
 const char kBatchFit[] = {
 #embed "device/batch_fit.hip"
 , 0};
+const char kBatchCov[] = {
+#embed "device/batch_cov.hip"
+, 0};
 
 }  // namespace gfh

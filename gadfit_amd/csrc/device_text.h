@@ -17,5 +17,6 @@ extern const char kOmegaJt[];          // omega_jt.hip: gfh_k_omega_jt
 extern const char kBatchWgSum[];       // batch_wg_sum.hip: gfh_b_sum_n, the cross-wave reducer of the 256-lane form of the batch kernels
 extern const char kBatchCube[];        // batch_cube.hip: the data form and the load of the cube forms of the batch kernels (gfh_set_batch_cube)
 extern const char kBatchFit[];         // batch_fit.hip: gfh_k_fit_batch, gfh_k_batch_pass
+extern const char kBatchCov[];         // batch_cov.hip: gfh_k_batch_cov, each fit's parameter covariance and standard errors
 
 }  // namespace gfh

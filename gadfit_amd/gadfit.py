@@ -300,8 +300,27 @@ def _batch_context(who):
     _S.ctx.set_use_ad(True)
 
 
+_BATCH_ERRORS = {None: None, 'unscaled': False, 'scaled': True}
+
+
+def _batch_errors(who, errors):
+    """the ``errors`` argument of the batch calls: None (no error outputs), else batch_covariance's scale"""
+    if not (errors is None or isinstance(errors, str)) or errors not in _BATCH_ERRORS:
+        raise GadfitError("%s: errors must be None, 'unscaled' (the inverse of J^T J) or 'scaled' (that times chi2 / dof), got %r" % (who, errors))
+    return _BATCH_ERRORS[errors]
+
+
+def _batch_fit(pars, active, scale, **kw):
+    """fit_batch, or fit_batch_errors under errors=: what the batch calls return"""
+    if scale is None:
+        out, res, _ = _S.ctx.fit_batch(pars, active, **kw)
+        return out, res
+    out, res, (cov, sigma, info), _ = _S.ctx.fit_batch_errors(pars, active, scale=scale, **kw)
+    return out, res, dict(cov=cov, sigma=sigma, info=info)
+
+
 def gadf_fit_batch(xs, ys, ws, pars, lambda_=None, lam_up=None, lam_down=None, accth=None, rel_error=None, chi2_rel=None,
-                   chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, lanes_per_fit=None, **kw):
+                   chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, lanes_per_fit=None, errors=None, **kw):
     """Many independent fits of the session's model in one kernel launch (gfh_fit_batch): gadf_fit's loop (gadfit.F90:670-915) per
     spectrum, each with its own data, start parameters, lambda history and exit.  On a session initialised with one dataset slot
     (``gadf_init(f)``); the active set is the one ``gadf_set`` left.  ``xs, ys, ws``: one array per spectrum (``ws``: the weights as
@@ -309,8 +328,12 @@ def gadf_fit_batch(xs, ys, ws, pars, lambda_=None, lam_up=None, lam_down=None, a
     gadf_fit's; those a device-resident loop does not carry (uphill, nielsen, umnigh, grad_chi2, cos_phi, rel_error_global) are refused
     by the library, and max_iter is required.  ``lanes_per_fit``: 64 a wave per fit, 16 a row of 16 lanes per fit and four fits per wave
     (short spectra), 256 a workgroup of four waves per fit (few, long spectra), 0 auto (16 or 64); None leaves the session's setting (64 unless set before).  Returns (parameters [n_fits][n_pars], record array of per-fit results with the fields
-    iterations, exit_reason, n_sweeps, n_chi2, n_omega, dof, lambda_, chi2)."""
+    iterations, exit_reason, n_sweeps, n_chi2, n_omega, dof, lambda_, chi2).  ``errors``: None, or 'unscaled' / 'scaled' for a third
+    element, a dict of each fit's parameter covariance ``cov`` [n_fits][na][na] at the fitted parameters -- the inverse of J^T J, under
+    'scaled' times chi2 / dof --, the standard errors ``sigma`` [n_fits][na] and ``info`` [n_fits] (0, or j + 1: pivot j of that fit's
+    factor failed and its cov and sigma are NaN), computed on the device behind the fit (gfh_fit_batch_errors)."""
     _need_init()
+    scale = _batch_errors('gadf_fit_batch', errors)
     if 'lambda' in kw:
         lambda_ = kw.pop('lambda')
     if _S.n_datasets != 1:
@@ -332,18 +355,18 @@ def gadf_fit_batch(xs, ys, ws, pars, lambda_=None, lam_up=None, lam_down=None, a
     np.cumsum([v.size for v in xs], out=off[1:])
     try:
         _S.ctx.set_batch_data(off, np.concatenate(xs), np.concatenate(ys), np.concatenate(ws))
-        out, res, _ = _S.ctx.fit_batch(pars, active, DTD_min=DTD_min, lanes_per_fit=lanes_per_fit, lambda_=_f32(lambda_), lam_up=_f32(lam_up), lam_down=_f32(lam_down),
-                                       accth=_f32(accth), rel_error=_f32(rel_error), chi2_rel=_f32(chi2_rel), chi2_abs=_f32(chi2_abs),
-                                       lam_incs=lam_incs, max_iter=max_iter, damp_max=None if damp_max is None else int(damp_max),
-                                       **{k: v for k, v in kw.items() if v is not None})
+        return _batch_fit(pars, active, scale, DTD_min=DTD_min, lanes_per_fit=lanes_per_fit, lambda_=_f32(lambda_), lam_up=_f32(lam_up), lam_down=_f32(lam_down),
+                          accth=_f32(accth), rel_error=_f32(rel_error), chi2_rel=_f32(chi2_rel), chi2_abs=_f32(chi2_abs),
+                          lam_incs=lam_incs, max_iter=max_iter, damp_max=None if damp_max is None else int(damp_max),
+                          **{k: v for k, v in kw.items() if v is not None})
     except _lib.GadfitHipError as e:
         raise GadfitError(str(e))
-    return out, res
 
 
-def _fit_cube(who, frames, x, Y, pars, sigma, DTD_min, lanes_per_fit, frames_per_put, kw):
+def _fit_cube(who, frames, x, Y, pars, sigma, DTD_min, lanes_per_fit, frames_per_put, errors, kw):
     """gadf_fit_cube and gadf_fit_frames: one body, the data spectrum-major (Y [n_fits][n_points]) or frame-major (F [n_points][n_fits])"""
     _need_init()
+    scale = _batch_errors(who, errors)
     if _S.n_datasets != 1:
         raise GadfitError('%s needs a session with one dataset slot: gadf_init(f)' % who)
     active = [i for i, a in enumerate(_S.active) if a]
@@ -374,10 +397,9 @@ def _fit_cube(who, frames, x, Y, pars, sigma, DTD_min, lanes_per_fit, frames_per
             _S.ctx.set_batch_frames(x, Y, _S.error_type, None if sigma is None else 1.0 / sigma, frames_per_put)
         else:
             _S.ctx.set_batch_cube(x, Y, _S.error_type, None if sigma is None else 1.0 / sigma)
-        out, res, _ = _S.ctx.fit_batch(pars, active, DTD_min=DTD_min, lanes_per_fit=lanes_per_fit, **kw)
+        return _batch_fit(pars, active, scale, DTD_min=DTD_min, lanes_per_fit=lanes_per_fit, **kw)
     except _lib.GadfitHipError as e:
         raise GadfitError(str(e))
-    return out, res
 
 
 def _cube_fit_args(lambda_, lam_up, lam_down, accth, rel_error, chi2_rel, chi2_abs, lam_incs, max_iter, damp_max, kw):
@@ -389,24 +411,25 @@ def _cube_fit_args(lambda_, lam_up, lam_down, accth, rel_error, chi2_rel, chi2_a
 
 
 def gadf_fit_cube(x, Y, pars, sigma=None, lambda_=None, lam_up=None, lam_down=None, accth=None, rel_error=None, chi2_rel=None,
-                  chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, lanes_per_fit=None, **kw):
+                  chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, lanes_per_fit=None, errors=None, **kw):
     """gadf_fit_batch over a data cube (gfh_set_batch_cube): every spectrum on the one grid ``x`` [n_points], ``Y`` [n_fits][n_points] a
     C-contiguous numpy array of float64, float32 or uint16 that is uploaded as it is.  The weights follow from ``Y`` on the device by
     the session's ``gadf_set_errors`` type (NONE, SQRT_Y, PROPTO_Y, INVERSE_Y: no weight array exists anywhere; gadf_fit_batch ignores
     that type, this call takes it); under USER ``sigma`` [n_fits][n_points] is required and 1 / sigma is passed.  ``pars``, the fit
-    arguments, ``lanes_per_fit`` and what is returned are gadf_fit_batch's."""
-    return _fit_cube('gadf_fit_cube', False, x, Y, pars, sigma, DTD_min, lanes_per_fit, 0,
+    arguments, ``lanes_per_fit``, ``errors`` and what is returned are gadf_fit_batch's."""
+    return _fit_cube('gadf_fit_cube', False, x, Y, pars, sigma, DTD_min, lanes_per_fit, 0, errors,
                      _cube_fit_args(lambda_, lam_up, lam_down, accth, rel_error, chi2_rel, chi2_abs, lam_incs, max_iter, damp_max, kw))
 
 
 def gadf_fit_frames(x, F, pars, sigma=None, lambda_=None, lam_up=None, lam_down=None, accth=None, rel_error=None, chi2_rel=None,
-                    chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, lanes_per_fit=None, frames_per_put=0, **kw):
+                    chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, lanes_per_fit=None, frames_per_put=0, errors=None,
+                    **kw):
     """gadf_fit_cube for a stack of frames (gfh_set_batch_frames): ``F`` [n_points][n_fits], one image per abscissa of ``x`` with the
     fit (pixel) index fastest, as instruments deliver it -- C-contiguous in float64, float32 or uint16, uploaded as it is and
     transposed into the cube on the device, so no ``np.ascontiguousarray(F.T)`` runs on the host.  ``sigma`` (under USER) is
     frame-major as ``F``; ``frames_per_put``: frames per upload, 0 the library's rule.  Everything else, and what is returned (the
     bits included), is gadf_fit_cube's on the transposed arrays."""
-    return _fit_cube('gadf_fit_frames', True, x, F, pars, sigma, DTD_min, lanes_per_fit, frames_per_put,
+    return _fit_cube('gadf_fit_frames', True, x, F, pars, sigma, DTD_min, lanes_per_fit, frames_per_put, errors,
                      _cube_fit_args(lambda_, lam_up, lam_down, accth, rel_error, chi2_rel, chi2_abs, lam_incs, max_iter, damp_max, kw))
 
 

@@ -422,7 +422,25 @@ int  gfh_fit_batch(gfh_ctx* ctx, double* pars, int n_act, const int32_t* active_
 /* STEP 1 + 2 (gadfit.F90:675-699) of every spectrum at given parameters, for callers with their own loop: JTJ [n_fits][n_act*n_act]
  * (symmetric, both triangles), JTres [n_fits][n_act], chi2 [n_fits]. */
 int  gfh_batch_pass(gfh_ctx* ctx, const double* pars, int n_act, const int32_t* active_pars, double* JTJ, double* JTres, double* chi2);
-/* The generated source of the batch kernels (gfh_k_fit_batch, gfh_k_batch_pass: a translation unit of their own, behind the
+/* Errors of a batch: each fit's parameter covariance and standard errors, computed on the device by a third kernel of the batch
+ * translation units (gfh_k_batch_cov: STEP 1 + 2 at the parameters, the Cholesky factor of J^T J without damping, its inverse and
+ * the product of the inverse with its transpose, in registers).  scale 0: cov = (J^T J)^-1, the reference's LMsolver::getInvJTJ;
+ * scale 1: that times chi2 / dof with the chi2 and dof of the fit's record; any other value is refused.  cov [n_fits][n_act*n_act]
+ * (symmetric bit for bit, both triangles), sigma [n_fits][n_act] = sqrt of cov's diagonal, info [n_fits]: 0, or j + 1 where pivot
+ * j of the fit's factor was not positive and finite -- that fit's cov and sigma are NaN, its neighbours are unaffected.  Rows and
+ * columns in the caller's order of active_pars.  NULL outputs are refused.
+ * gfh_batch_covariance: at given parameters pars [n_fits][n_pars], on whichever batch data is held, with gfh_batch_pass's checks
+ * and refusals under its own name; one launch, one copy back.
+ * gfh_fit_batch_errors: gfh_fit_batch, then the covariance at the fitted parameters on the same stream -- the parameter block stays
+ * on the device between the two launches and everything returns in one copy.  pars, results are the bits of gfh_fit_batch; *seconds
+ * (may be NULL) = device time of both launches.
+ * Not built: the covariance of a plain gfh_fit, error bands of the fitted curve, a Fortran entry, a covariance under a robust loss
+ * (a batch carries the linear loss alone). */
+int  gfh_batch_covariance(gfh_ctx* ctx, const double* pars, int n_act, const int32_t* active_pars, int scale, double* cov,
+                          double* sigma, int32_t* info);
+int  gfh_fit_batch_errors(gfh_ctx* ctx, double* pars, int n_act, const int32_t* active_pars, const gfh_fit_options* opt,
+                          gfh_batch_result* results, int scale, double* cov, double* sigma, int32_t* info, double* seconds);
+/* The generated source of the batch kernels (gfh_k_fit_batch, gfh_k_batch_pass, gfh_k_batch_cov: a translation unit of their own, behind the
  * model's point functions) as gfh_model_source, and its compilation without a launch as gfh_model_prepare (needs no GPU). */
 int64_t gfh_batch_source(gfh_ctx* ctx, int n_act, const int32_t* active_pars, char* buf, int64_t cap);
 int  gfh_batch_prepare(gfh_ctx* ctx, int n_act, const int32_t* active_pars);

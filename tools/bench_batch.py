@@ -9,6 +9,7 @@ profiles/r05_small_fits.txt: 1000 points, a Gaussian on a background, 4 paramete
                                 [--registers] [--observed FILE [--observed-only]] [--out profiles/batch_workgroup.json]
     python tools/bench_batch.py --cube [--cells gauss4:64:16384:1000,...] [--registers] [--out profiles/batch_cube.json]
     python tools/bench_batch.py --frames [--cells uint16:1:64:131072:1000,...] [--out profiles/batch_frames.json]
+    python tools/bench_batch.py --cov [--sizes 16384,131072] [--points 1000] [--lanes 64] [--out profiles/batch_cov.json]
 
 Per batch size: warm-up launches, then the median of the timed launches -- device time from the HIP events around the kernel
 (gfh_fit_batch's `seconds`) and wall time around the whole call (parameters down, launch, results back).  Two yardsticks, neither of
@@ -50,7 +51,14 @@ the wall time of the set call through five routes that alternate call by call on
 array (the floor: the upload alone), np.ascontiguousarray(F.T) + set_batch_cube (the yardstick: the route before), set_batch_frames with
 the default pieces, with one put and with eight puts; the transposing kernel's device time (HIP events) and the bytes it moves per second.  fit_batch must
 return the same parameters and counts from all three routes, and at 131072 x 1000 uint16 the frames route must beat the host
-transpose by tests/batch_records.row_wins, or the tool fails."""
+transpose by tests/batch_records.row_wins, or the tool fails.
+--cov: the errors of a batch (gfh_fit_batch_errors: the fit, then gfh_k_batch_cov on the same stream) on this tool's problem with 4
+(gauss4) and 8 (exp4) active parameters, per batch size three routes that alternate call by call on one context: fit_batch alone (the
+first yardstick), fit_batch_errors, and the route a caller had before (the second yardstick): fit_batch, batch_pass at the fitted
+parameters, numpy.linalg.inv over the batch on the host.  Wall time around each route, and the device time the library reports for
+fit_batch and for fit_batch_errors (HIP events around the one launch and around the two): their difference is what gfh_k_batch_cov
+adds on the device.  The library takes no events around gfh_k_batch_pass, so that kernel's own device time is not in the record.  No
+ratio is asserted; the medians and the min-max are written down."""
 import argparse
 import json
 import os
@@ -155,7 +163,7 @@ ROW_MODELS = {
 
 
 def kernel_registers(src):
-    """{kernel: {vgprs, agprs, sgprs, scratch_bytes_per_lane, waves_per_simd, lds_bytes_per_block}} of the two batch kernels of a generated source"""
+    """{kernel: {vgprs, agprs, sgprs, scratch_bytes_per_lane, waves_per_simd, lds_bytes_per_block}} of the three batch kernels of a generated source"""
     import re
     import subprocess
     import tempfile
@@ -174,7 +182,7 @@ def kernel_registers(src):
         if not m:
             continue
         if m.group(1) == 'Function Name':
-            name = m.group(2) if m.group(2) in ('gfh_k_fit_batch', 'gfh_k_batch_pass') else None
+            name = m.group(2) if m.group(2) in ('gfh_k_fit_batch', 'gfh_k_batch_pass', 'gfh_k_batch_cov') else None
             if name:
                 out[name] = {}
         elif name and m.group(1) in keys:
@@ -306,6 +314,64 @@ def cube_main(a):
             json.dump(rec, fh, indent=1, sort_keys=True)
             fh.write('\n')
         del xs, counts, w, data
+    print('wrote', a.out)
+
+
+def cov_main(a):
+    """fit_batch_errors against fit_batch alone and against fit_batch + batch_pass + numpy.linalg.inv (see the module's text)"""
+    n_points, lanes = int(a.points or 1000), int(a.lanes or 64)
+    rec = dict(method='per (model, fits) three routes alternating call by call on one context of one card in one run: fit = fit_batch alone, errors = '
+                      'fit_batch_errors(scale=True), host = fit_batch + batch_pass at the fitted parameters + numpy.linalg.inv of the batch and its scaling '
+                      'by chi2 / dof on the host; the median and the min-max of %d calls after %d warm-up calls; wall = around the route, device = what the '
+                      'library reports (HIP events around the fit kernel, and around the fit kernel and gfh_k_batch_cov together); %d points per '
+                      'spectrum, %d lanes per fit, lambda0 = %g, max_iter = %d; no events surround gfh_k_batch_pass, so its device time is not recorded; '
+                      'no counter pass was made' % (a.launches, a.warmup, n_points, lanes, LAMBDA0, MAX_ITER), measurements=[])
+    kw = dict(lambda_=LAMBDA0, max_iter=MAX_ITER)
+    for name in ('gauss4', 'exp4'):
+        m = ROW_MODELS[name]
+        na = len(m['active'])
+        for nf in [int(s) for s in a.sizes.split(',')]:
+            xs, ys, ws = spectra_flat(name, nf, n_points)
+            ctx = _lib.Context(0)
+            ctx.set_model(trace_model(m['model'], m['n_pars']))
+            ctx.set_batch_lanes(lanes)
+            ctx.set_batch_data(np.arange(nf + 1, dtype=np.int64) * n_points, xs, ys, ws)
+            del xs, ys, ws
+            start = np.tile(m['start'], (nf, 1))
+            wall = dict(fit=[], errors=[], host=[]); dev = dict(fit=[], errors=[])
+            for it in range(a.warmup + a.launches):
+                t0 = time.perf_counter()
+                p, r, sec = ctx.fit_batch(start, m['active'], **kw)
+                t1 = time.perf_counter()
+                pe, re_, (cov, sigma, info), sec_e = ctx.fit_batch_errors(start, m['active'], scale=True, **kw)
+                t2 = time.perf_counter()
+                ph, rh, _ = ctx.fit_batch(start, m['active'], **kw)
+                JTJ, _, chi2 = ctx.batch_pass(ph, m['active'])
+                cov_h = np.linalg.inv(JTJ) * (chi2 / rh['dof'])[:, None, None]
+                sigma_h = np.sqrt(np.diagonal(cov_h, axis1=1, axis2=2))
+                t3 = time.perf_counter()
+                if it >= a.warmup:
+                    wall['fit'].append(t1 - t0); wall['errors'].append(t2 - t1); wall['host'].append(t3 - t2)
+                    dev['fit'].append(sec); dev['errors'].append(sec_e)
+            ctx.close()
+            if not (np.array_equal(p, pe) and np.array_equal(p, ph) and np.all(info == 0)):
+                sys.exit('the routes do not fit alike, or a covariance failed')
+            entry = dict(model=name, what=m['what'], n_active=na, fits=nf, points=n_points, lanes=lanes,
+                         worst_relative_sigma_difference_to_the_host_route=float(np.max(np.abs(sigma - sigma_h) / sigma_h)))
+            for k, v in wall.items():
+                entry['wall_ms_' + k] = dict(median=1e3 * statistics.median(v), min=1e3 * min(v), max=1e3 * max(v))
+            for k, v in dev.items():
+                entry['device_ms_' + k] = dict(median=1e3 * statistics.median(v), min=1e3 * min(v), max=1e3 * max(v))
+            entry['device_ms_cov_kernel_by_difference'] = entry['device_ms_errors']['median'] - entry['device_ms_fit']['median']
+            entry['wall_errors_over_fit'] = entry['wall_ms_errors']['median'] / entry['wall_ms_fit']['median']
+            entry['wall_host_route_over_errors'] = entry['wall_ms_host']['median'] / entry['wall_ms_errors']['median']
+            rec['measurements'].append(entry)
+            print('%-6s %7d fits: wall fit %.2f ms, errors %.2f ms, host route %.2f ms; device fit %.3f ms, fit + cov %.3f ms; sigma differs from the host route by %.1e'
+                  % (name, nf, entry['wall_ms_fit']['median'], entry['wall_ms_errors']['median'], entry['wall_ms_host']['median'],
+                     entry['device_ms_fit']['median'], entry['device_ms_errors']['median'], entry['worst_relative_sigma_difference_to_the_host_route']), flush=True)
+            with open(a.out, 'w') as fh:
+                json.dump(rec, fh, indent=1, sort_keys=True)
+                fh.write('\n')
     print('wrote', a.out)
 
 
@@ -587,6 +653,7 @@ def main():
     ap.add_argument('--workgroup', action='store_true', help='the 256-lane form of the batch kernels against the 64-lane form, into profiles/batch_workgroup.json')
     ap.add_argument('--cube', action='store_true', help='a batch as a data cube against the ragged form of the same spectra, into profiles/batch_cube.json')
     ap.add_argument('--frames', action='store_true', help='a stack of frames against the host transpose and the upload alone, into profiles/batch_frames.json')
+    ap.add_argument('--cov', action='store_true', help='fit_batch_errors against fit_batch alone and against the host route, into profiles/batch_cov.json')
     ap.add_argument('--cells', default=None, help='with --cube: model:lanes:fits:points, ...; with --frames: sample type:error type:lanes:fits:points, ...')
     ap.add_argument('--models', default='gauss4,exp4', help='with --workgroup: the models measured by this call (the record keeps the others)')
     ap.add_argument('--registers', action='store_true', help='with --rows or --workgroup: only the register figures of the four kernels into the record; no GPU is needed')
@@ -601,7 +668,7 @@ def main():
                                                                  'nothing is timed, no GPU is needed')
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'batch_frames.json' if a.frames else 'batch_cube.json' if a.cube else 'batch_workgroup.json' if a.workgroup else 'batch_rows.json' if a.rows else 'batch_fits.json')
+        a.out = os.path.join(ROOT, 'profiles', 'batch_cov.json' if a.cov else 'batch_frames.json' if a.frames else 'batch_cube.json' if a.cube else 'batch_workgroup.json' if a.workgroup else 'batch_rows.json' if a.rows else 'batch_fits.json')
     if a.cells is None:
         a.cells = FRAMES_CELLS if a.frames else CUBE_CELLS
     if (a.rows or a.workgroup or a.cube) and a.registers:
@@ -628,6 +695,10 @@ def main():
         return
     if a.launches < 5:
         sys.exit('at least 5 timed launches')
+    if a.cov:
+        if a.sizes == '1024,16384,131072':
+            a.sizes = '16384,131072'
+        return cov_main(a)
     if a.frames:
         return frames_main(a)
     if a.cube:
