@@ -106,6 +106,7 @@ SYMBOLS = {
     'gfh_batch_pass': (_i, [_vp, _dp, _i, _ip, _dp, _dp, _dp]),
     'gfh_batch_covariance': (_i, [_vp, _dp, _i, _ip, _i, _dp, _dp, _ip]),
     'gfh_fit_batch_errors': (_i, [_vp, _dp, _i, _ip, C.POINTER(FitOptions), C.POINTER(BatchResult), _i, _dp, _dp, _ip, _dp]),
+    'gfh_batch_eval': (_i, [_vp, _dp, _i, _ip, _dp, _dp, _i64, _i64, _i64, _dp, _dp, _dp, _dp]),
     'gfh_batch_source': (_i64, [_vp, _i, _ip, C.c_char_p, _i64]),
     'gfh_batch_prepare': (_i, [_vp, _i, _ip]),
     'gfh_set_batch_lanes': (_i, [_vp, _i]),
@@ -118,6 +119,7 @@ SYMBOLS = {
     'gfh_set_batch_frames': (_i, [_vp, _i64, _i64, _dp, _vp, _i, _i, _dp, _i64]),
     'gfh_debug_batch_frames_missing': (_i64, [_vp]),
     'gfh_debug_batch_frames_seconds': (C.c_double, [_vp]),
+    'gfh_debug_batch_pass_seconds': (C.c_double, [_vp]),
     'gfh_debug_batch_read': (_i, [_vp, _i, _i64, _i64, _vp]),
     'gfh_set_lookahead': (_i, [_vp, _i]),
     'gfh_set_keep_jacobian': (_i, [_vp, _i]),
@@ -519,6 +521,7 @@ class Context:
                                  % (off[-1], x.size, y.size, w.size))
         self.n_fits = 0
         self._cube_dtype = None
+        self._batch_off, self._batch_points = off.copy(), None
         try:
             self._chk(lib().gfh_set_batch_data(self._h, off.size - 1, off.ctypes.data_as(C.POINTER(_i64)), dp(x), dp(y), dp(w)))
         except GadfitHipError as e:
@@ -546,6 +549,7 @@ class Context:
                 raise GadfitHipError('set_batch_cube: w must have the shape of Y %s, got %s' % (Y.shape, w.shape))
         self.n_fits = 0
         self._cube_dtype = Y.dtype
+        self._batch_off, self._batch_points = None, Y.shape[1]
         try:
             self._chk(lib().gfh_set_batch_cube(self._h, Y.shape[0], Y.shape[1], dp(x), Y.ctypes.data_as(_vp), _CUBE_TYPES[Y.dtype],
                                                int(error_type), None if w is None else dp(w)))
@@ -580,6 +584,7 @@ class Context:
             raise GadfitHipError('batch_frames_begin: x must be 1-D [n_points]')
         self.n_fits = 0
         self._cube_dtype = None
+        self._batch_off, self._batch_points = None, x.size
         try:
             self._chk(lib().gfh_batch_frames_begin(self._h, int(n_fits), x.size, dp(x), _CUBE_TYPES[dtype], int(error_type)))
         except GadfitHipError as e:
@@ -621,6 +626,7 @@ class Context:
                 raise GadfitHipError('set_batch_frames: w must have the shape of F %s, got %s' % (F.shape, w.shape))
         self.n_fits = 0
         self._cube_dtype = None
+        self._batch_off, self._batch_points = None, F.shape[0]
         try:
             self._chk(lib().gfh_set_batch_frames(self._h, F.shape[1], F.shape[0], dp(x), F.ctypes.data_as(_vp), _CUBE_TYPES[F.dtype],
                                                  int(error_type), None if w is None else dp(w), int(frames_per_put)))
@@ -671,6 +677,10 @@ class Context:
         wave (short spectra), 256 a workgroup of four waves per fit (few, long spectra), 0 auto (batch_auto_lanes of the active count
         and the longest spectrum: 16 or 64, never 256) -- gfh_set_batch_lanes"""
         self._chk(lib().gfh_set_batch_lanes(self._h, int(lanes)))
+
+    def batch_pass_seconds(self):
+        """device time of the kernel of this context's last batch_pass (0.0: none yet) -- gfh_debug_batch_pass_seconds"""
+        return float(lib().gfh_debug_batch_pass_seconds(self._h))
 
     def batch_lanes_used(self):
         """64, 16 or 256: the form of the last batch launch (0: none yet) -- gfh_debug_batch_lanes"""
@@ -746,6 +756,56 @@ class Context:
         JTJ = np.zeros((n, a.size, a.size)); JTr = np.zeros((n, a.size)); chi2 = np.zeros(n)
         self._chk(lib().gfh_batch_pass(self._h, dp(p), a.size, ip(a), dp(JTJ), dp(JTr), dp(chi2)))
         return JTJ, JTr, chi2
+
+    def batch_eval(self, pars, active, cov=None, x_eval=None, residuals=False, first_fit=0, n_fits=None, lanes_per_fit=None, model=True):
+        """the fitted curves of fits [first_fit, first_fit + n_fits) of the batch held (n_fits None: to its end), computed on the
+        device: returns (model, residual or None, band or None, offsets, seconds).  pars [n_fits][n_pars] and cov [n_fits][na][na]
+        (batch_covariance's, or None: no band) hold the rows of the evaluated fits only.  x_eval None: on the fits' own points, in
+        the data's layout -- a cube gives [n_fits][n_points], the ragged form flat arrays that `offsets` [n_fits + 1] (relative to
+        the range) splits; model = f(x_i), residual = (y_i - f) w_i under residuals=True, band = sqrt(g^T C g) with g the gradient by
+        the active parameters in the order of `active`.  x_eval [n_eval]: model and band on that grid, [n_fits][n_eval]; residuals
+        are refused.  model=False leaves the model out (None).  A fit whose cov is NaN gets NaN bands alone.  seconds: the device
+        time of the kernel; lanes_per_fit as fit_batch -- gfh_batch_eval"""
+        nb = getattr(self, 'n_fits', 0)
+        if nb < 1:
+            raise GadfitHipError('batch_eval: no batch data (set_batch_data, set_batch_cube)')
+        first = int(first_fit)
+        n = nb - first if n_fits is None else int(n_fits)
+        a = np.ascontiguousarray(active, dtype=np.int32)
+        if a.size < 1 or a.min() < 0 or a.max() >= self.n_pars:
+            raise GadfitHipError('batch_eval: active parameter indices must lie in [0, %d)' % self.n_pars)
+        p = np.ascontiguousarray(pars, dtype=np.float64)
+        xe = None if x_eval is None else np.ascontiguousarray(x_eval, dtype=np.float64).ravel()
+        ok = first >= 0 and n >= 1 and first + n <= nb
+        if ok and p.size != n * self.n_pars:
+            raise GadfitHipError('batch_eval: pars must hold the rows of the evaluated fits, n_fits x n_pars = %d x %d values, got %d' % (n, self.n_pars, p.size))
+        if cov is not None:
+            cov = np.ascontiguousarray(cov, dtype=np.float64)
+            if ok and cov.size != n * a.size * a.size:
+                raise GadfitHipError('batch_eval: cov must hold the rows of the evaluated fits, n_fits x na x na = %d x %d x %d values, got %d'
+                                     % (n, a.size, a.size, cov.size))
+        if lanes_per_fit is not None:
+            self.set_batch_lanes(lanes_per_fit)
+        offsets = None
+        if not ok:
+            shape = (0,)          # (the library words the refusal)
+        elif xe is not None:
+            shape = (n, xe.size)
+        elif self._batch_off is None:
+            shape = (n, self._batch_points)
+        else:
+            offsets = self._batch_off[first:first + n + 1] - self._batch_off[first]
+            shape = (int(offsets[-1]),)
+        if offsets is None and ok:
+            offsets = np.arange(n + 1, dtype=np.int64) * shape[1]
+        out_m = np.empty(shape) if model else None
+        out_r = np.empty(shape) if residuals else None
+        out_b = np.empty(shape) if cov is not None else None
+        sec = C.c_double()
+        self._chk(lib().gfh_batch_eval(self._h, dp(p), a.size, ip(a), None if cov is None else dp(cov), None if xe is None else dp(xe),
+                                       0 if xe is None else xe.size, first, n, *[None if v is None else dp(v) for v in (out_m, out_r, out_b)],
+                                       C.cast(C.byref(sec), _dp)))
+        return out_m, out_r, out_b, offsets, sec.value
 
     def batch_source(self, active):
         a = np.ascontiguousarray(active, dtype=np.int32)

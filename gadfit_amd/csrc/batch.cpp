@@ -1,5 +1,5 @@
 // batch.cpp -- batched independent fits: many Levenberg-Marquardt fits of ONE model in ONE kernel launch, each with its own data,
-// start parameters, lambda history and exit (gfh_set_batch_data, gfh_fit_batch, gfh_batch_pass, gfh_batch_covariance, gfh_fit_batch_errors, gfh_batch_source, gfh_batch_prepare,
+// start parameters, lambda history and exit (gfh_set_batch_data, gfh_fit_batch, gfh_batch_pass, gfh_batch_covariance, gfh_fit_batch_errors, gfh_batch_eval, gfh_batch_source, gfh_batch_prepare,
 // gfh_set_batch_lanes; gfh_set_batch_cube: the same batch as a cube on one grid with narrow samples; gfh_batch_frames_begin,
 // gfh_batch_frames_put, gfh_set_batch_frames: that cube from a frame-major stack, transposed on the device by frames.hip).  This file validates, uploads, compiles / loads and launches; the loop itself (gadfit.F90:670-915) is the
 // generated kernel gfh_k_fit_batch (batch_fit.hip; codegen.cpp, emit_batch_kernels), a wave per fit or -- gfh_set_batch_lanes(16) -- a
@@ -98,7 +98,7 @@ int check_cube(gfh_ctx* c, const char* who, bool null_arg, const char* required,
   return 0;
 }
 
-// the translation unit of an active set with the three batch kernels: generated, compiled and (load) loaded once per context, kept
+// the translation unit of an active set with the four batch kernels: generated, compiled and (load) loaded once per context, kept
 // in the context's kernel cache under a key no plain active set has, so that a new model or gfh_destroy releases it with the rest
 GenConfig batch_config(const gfh_ctx* c, int lanes) {
   GenConfig cfg;                    // the defaults, not the context's current switches: one form per (model, active set, lanes per fit)
@@ -134,7 +134,7 @@ int batch_kernels(gfh_ctx* c, const std::vector<int32_t>& active, int lanes, boo
     if (!load_kernels(code, &mk, &err)) return fail(c, err);
     publish_loaded(c->device, skey, mk);
   }
-  if (!mk.fit_batch || !mk.batch_pass || !mk.batch_cov) { release_loaded(c->device, &mk); return fail(c, "the batch kernels are missing from their code object"); }
+  if (!mk.fit_batch || !mk.batch_pass || !mk.batch_cov || !mk.batch_eval) { release_loaded(c->device, &mk); return fail(c, "the batch kernels are missing from their code object"); }
   mk.n_active = (int)active.size();
   ModelKernels* p = &c->kernel_cache.emplace(key, mk).first->second;
   if (out) *out = p;
@@ -463,10 +463,14 @@ int gfh_batch_pass(gfh_ctx* c, const double* pars, int na, const int32_t* active
   long long npts = c->batch.max_points;
   void* dp = c->batch.io.p; void* img = c->batch.img.p; long long n = nf; void* stp = c->status.p;
   void* args[] = {&x, &y, &w, c->batch.cube ? (void*)&npts : (void*)&off, &dp, &img, &n, &stp};
+  harvest_events(c);
+  HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
   HIPCHK(c, hipModuleLaunchKernel(mk->batch_pass, (unsigned)((nf + per_wg - 1) / per_wg), 1, 1, 256, 1, 1, 0, c->stream, args, nullptr));
   c->batch.last_lanes = lanes; c->batch.last_form = data_form(c);
+  HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
   HIPCHK(c, hipMemcpyAsync(c->batch.host.data(), c->batch.img.p, ib, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->batch.pass_ms = ev_ms(c->ev[0], c->ev[1]);
   const double* h = reinterpret_cast<const double*>(c->batch.host.data());
   for (int64_t f = 0; f < nf; f++) {
     const double* r = h + (size_t)f * rec;
@@ -476,6 +480,72 @@ int gfh_batch_pass(gfh_ctx* c, const double* pars, int na, const int32_t* active
   }
   return 0;
 } catch (const std::exception& e) { return fail(c, std::string("gfh_batch_pass: ") + e.what()); }
+
+// Curves of a batch (include/gadfit_hip.h): the model, the weighted residuals and the 1-sigma band of fits [first_fit, first_fit +
+// n_fits_eval) of the batch held, on their own points or on the caller's grid, by gfh_k_batch_eval (batch_eval.hip).  Everything the
+// batch kernels do not carry is refused by the shared checks under this call's name, its own refusals follow, all before the device
+// is asked for.  io = [pars | cov | x_eval] goes down in one copy, img = [model | residual | band] (the requested ones, each `tot`
+// doubles) comes back in one.
+int gfh_batch_eval(gfh_ctx* c, const double* pars, int na, const int32_t* active, const double* cov, const double* x_eval, int64_t n_eval,
+                   int64_t first_fit, int64_t n_fits_eval, double* model, double* residual, double* band, double* seconds) try {
+  if (check_context(c, "gfh_batch_eval") || check_model(c, "gfh_batch_eval", na, active)) return 1;
+  if (!pars) return fail(c, "gfh_batch_eval: null argument (pars is required)");
+  if (!model && !residual && !band) return fail(c, "gfh_batch_eval: no output requested (model, residual and band are all NULL)");
+  if (band && !cov) return fail(c, "gfh_batch_eval: a band needs the fits' covariances (cov is NULL)");
+  if (residual && x_eval) return fail(c, "gfh_batch_eval: a residual on a caller's grid has no meaning (residual is given on the fits' own points alone)");
+  if (x_eval && n_eval < 1) return fail(c, "gfh_batch_eval: a grid holds at least one point (x_eval given with n_eval = " + std::to_string((long long)n_eval) + ")");
+  if (!x_eval && n_eval != 0) return fail(c, "gfh_batch_eval: n_eval = " + std::to_string((long long)n_eval) + " without x_eval (NULL, 0: the fits' own points)");
+  if (check_geometry(c, "gfh_batch_eval", na) || check_frames(c, "gfh_batch_eval")) return 1;
+  const int64_t nf = c->batch.n_fits;
+  if (first_fit < 0 || n_fits_eval < 1 || first_fit > nf - n_fits_eval)
+    return fail(c, "gfh_batch_eval: fits [" + std::to_string((long long)first_fit) + ", " + std::to_string((long long)first_fit) + " + " +
+                   std::to_string((long long)n_fits_eval) + ") are empty or reach past the " + std::to_string((long long)nf) + " fits of the batch");
+  // the points of one output: the data's own layout, or [n_fits_eval][n_eval]
+  const int64_t per_fit = x_eval ? n_eval : c->batch.max_points;
+  const int n_out = (model ? 1 : 0) + (residual ? 1 : 0) + (band ? 1 : 0);
+  if (per_fit > INT64_MAX / 8 / n_out / n_fits_eval) return fail(c, "gfh_batch_eval: the size of the outputs overflows");
+  const int64_t tot = x_eval || c->batch.cube ? n_fits_eval * per_fit : c->batch.off[(size_t)(first_fit + n_fits_eval)] - c->batch.off[(size_t)first_fit];
+  NEED_GPU(c);
+  if (!c->batch.on_device) return fail(c, "gfh_batch_eval: no batch data on the device (gfh_set_batch_data, gfh_set_batch_cube)");
+  gfh::Range range("gadfit gfh_batch_eval");
+  ModelKernels* mk = nullptr;
+  const int lanes = batch_lanes(c, na), per_wg = 256 / lanes;
+  if (batch_kernels(c, std::vector<int32_t>(active, active + na), lanes, true, &mk)) return 1;
+  const size_t pb = sizeof(double) * (size_t)n_fits_eval * (size_t)c->model.n_pars;
+  const size_t cb = band ? sizeof(double) * (size_t)n_fits_eval * (size_t)na * na : 0, xb = x_eval ? sizeof(double) * (size_t)n_eval : 0;
+  const size_t ob = sizeof(double) * (size_t)tot;
+  if (dev_alloc(c, c->batch.io, pb + cb + xb) || dev_alloc(c, c->batch.img, std::max<size_t>(ob * n_out, 8))) return 1;
+  c->batch.host.resize(std::max(pb + cb + xb, ob * n_out));
+  char* h = c->batch.host.data();          // down from here, and -- behind the kernel in the stream's order -- back into it
+  memcpy(h, pars, pb);
+  if (cb) memcpy(h + pb, cov, cb);
+  if (xb) memcpy(h + pb + cb, x_eval, xb);
+  harvest_events(c);
+  HIPCHK(c, hipMemcpyAsync(c->batch.io.p, h, pb + cb + xb, hipMemcpyHostToDevice, c->stream));
+  void* x = c->batch.x.p; void* y = c->batch.y.p; void* w = c->batch.w.p; void* off = c->batch.off_d.p;
+  long long npts = c->batch.max_points;      // a cube's kernels take n_points where the ragged ones take the offsets (GFH_BARGS)
+  char* in = c->batch.io.as<char>(); char* out = c->batch.img.as<char>();
+  void* dp = in; void* dc = cb ? in + pb : nullptr; void* dx = xb ? in + pb + cb : nullptr;
+  size_t at = 0;
+  void* dm = nullptr; void* dr = nullptr; void* db = nullptr;
+  if (model) { dm = out + at; at += ob; }
+  if (residual) { dr = out + at; at += ob; }
+  if (band) { db = out + at; at += ob; }
+  long long ne = n_eval, first = first_fit, n = n_fits_eval; void* stp = c->status.p;
+  void* args[] = {&x, &y, &w, c->batch.cube ? (void*)&npts : (void*)&off, &dp, &dc, &dx, &ne, &first, &n, &dm, &dr, &db, &stp};
+  HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+  HIPCHK(c, hipModuleLaunchKernel(mk->batch_eval, (unsigned)((n_fits_eval + per_wg - 1) / per_wg), 1, 1, 256, 1, 1, 0, c->stream, args, nullptr));
+  c->batch.last_lanes = lanes; c->batch.last_form = data_form(c);
+  HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+  HIPCHK(c, hipMemcpyAsync(h, out, at, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  at = 0;
+  if (model) { memcpy(model, h + at, ob); at += ob; }
+  if (residual) { memcpy(residual, h + at, ob); at += ob; }
+  if (band) { memcpy(band, h + at, ob); at += ob; }
+  if (seconds) *seconds = 1e-3 * ev_ms(c->ev[0], c->ev[1]);
+  return 0;
+} catch (const std::exception& e) { return fail(c, std::string("gfh_batch_eval: ") + e.what()); }
 
 // The generated source of the batch translation unit for the current model and an active set, as gfh_model_source: in the form of
 // the context's setting (under auto: what the rule gives for the geometry held, 64 without one); gfh_batch_prepare alike.
@@ -505,6 +575,8 @@ int gfh_set_batch_lanes(gfh_ctx* c, int lanes) try {
 
 // The form of the last batch launch of this context (64, 16 or 256; 0: none yet), so that a test asserts the dispatch.
 int gfh_debug_batch_lanes(gfh_ctx* c) { return c ? c->batch.last_lanes : 0; }
+// device time of the kernel of the last gfh_batch_pass of this context in seconds (HIP events; 0: none yet)
+double gfh_debug_batch_pass_seconds(gfh_ctx* c) { return c ? 1e-3 * c->batch.pass_ms : 0.0; }
 // ... and its data form: -1 none yet, 0 ragged, else a cube, 1 + y_type + 3 * error_type
 int gfh_debug_batch_form(gfh_ctx* c) { return c ? c->batch.last_form : -1; }
 

@@ -8,7 +8,7 @@
 // Only what depends on the tape is generated here: the point functions, the quadrature call sites, the selector and the
 // #defines in front of them (emit_ad.cpp unrolls a tape, emit_quadrature.cpp and emit_branching.cpp write what integrate() and a
 // branching eval() add).  The kernels themselves are hand-written HIP that no tape changes; they are plain files under
-// device/ (sweep.hip, fused_sweep_gram.hip, chi2.hip, omega.hip, omega_jt.hip, batch_fit.hip, batch_cov.hip, batch_wg_sum.hip, batch_cube.hip, ...), embedded by
+// device/ (sweep.hip, fused_sweep_gram.hip, chi2.hip, omega.hip, omega_jt.hip, batch_fit.hip, batch_cov.hip, batch_eval.hip, batch_wg_sum.hip, batch_cube.hip, ...), embedded by
 // device_text.cpp and streamed into the translation unit by generate_source as they are.  Loading and validating a tape is
 // model.cpp.
 #include "codegen_internal.h"
@@ -59,7 +59,7 @@ static std::string coop_defines(int NA) {
   return o.str();
 }
 
-// GenConfig::batch: the three kernels of batched independent fits, behind the point functions of the translation unit (batch.cpp is
+// GenConfig::batch: the four kernels of batched independent fits, behind the point functions of the translation unit (batch.cpp is
 // their host side and refuses what they do not carry before it comes here; the checks below keep the generator honest on its own).
 static bool emit_batch_kernels(const Model& m, const std::vector<int32_t>& active, const GenConfig& cfg, std::ostringstream& s, std::string* err) {
   const int NA = (int)active.size();
@@ -77,6 +77,7 @@ static bool emit_batch_kernels(const Model& m, const std::vector<int32_t>& activ
   if (cfg.batch_lanes == 256) s << kBatchWgSum;          // batch_wg_sum.hip: LDS and a barrier, in the text of the workgroup form alone
   s << kBatchFit;                   // batch_fit.hip: gfh_k_fit_batch, gfh_k_batch_pass, written once against GFH_BLANES
   s << kBatchCov;                   // batch_cov.hip: gfh_k_batch_cov, behind them in every form
+  s << kBatchEval;                  // batch_eval.hip: gfh_k_batch_eval, behind that
   return true;
 }
 

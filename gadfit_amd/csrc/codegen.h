@@ -26,7 +26,7 @@ struct GenConfig {
   int loss = 0;           // robust cost (gfh_set_loss): 0 linear, 1 cauchy, 2 huber
   bool fast_div = true;   // share one reciprocal per denominator (<= 1 ulp from the reference's r/v)
   int waves_per_eu = 0;   // > 0: the plain sweep / chi2 / omega kernels are compiled for at least this many waves per SIMD (register cap)
-  bool batch = false;     // three more kernels behind the point functions: gfh_k_fit_batch (a whole LM fit per wave), gfh_k_batch_pass, gfh_k_batch_cov
+  bool batch = false;     // four more kernels behind the point functions: gfh_k_fit_batch (a whole LM fit per wave), gfh_k_batch_pass, gfh_k_batch_cov, gfh_k_batch_eval
                           // (batch.cpp).  A translation unit of its own: the default one does not change by a byte
   int batch_lanes = 64;   // ... lanes per fit of those two (GFH_BLANES): 64, a wave per fit, 16, a DPP row per fit and four fits per wave,
                           // or 256, a workgroup per fit

@@ -197,6 +197,7 @@ struct gfh_ctx {
     bool cube = false;
     int y_type = 0, error_type = 0;
     int last_form = -1;             // the data form of the last batch launch (gfh_debug_batch_form); -1: none yet
+    double pass_ms = 0.0;           // device time of the last gfh_batch_pass's kernel (gfh_debug_batch_pass_seconds): a yardstick for its neighbours
     bool on_device = false;
     gfh::DevBuf x, y, w, off_d, io, img;
     // gfh_batch_frames_begin: the cube above, filled frame by frame.  One flag per frame (1: put), the count of those still 0, the

@@ -46,5 +46,8 @@ const char kBatchFit[] = {
 const char kBatchCov[] = {
 #embed "device/batch_cov.hip"
 , 0};
+const char kBatchEval[] = {
+#embed "device/batch_eval.hip"
+, 0};
 
 }  // namespace gfh

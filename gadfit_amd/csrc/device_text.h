@@ -18,5 +18,6 @@ extern const char kBatchWgSum[];       // batch_wg_sum.hip: gfh_b_sum_n, the cro
 extern const char kBatchCube[];        // batch_cube.hip: the data form and the load of the cube forms of the batch kernels (gfh_set_batch_cube)
 extern const char kBatchFit[];         // batch_fit.hip: gfh_k_fit_batch, gfh_k_batch_pass
 extern const char kBatchCov[];         // batch_cov.hip: gfh_k_batch_cov, each fit's parameter covariance and standard errors
+extern const char kBatchEval[];        // batch_eval.hip: gfh_k_batch_eval, the fitted curves, residuals and error bands of a range of fits
 
 }  // namespace gfh

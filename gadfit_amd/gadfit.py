@@ -433,6 +433,30 @@ def gadf_fit_frames(x, F, pars, sigma=None, lambda_=None, lam_up=None, lam_down=
                      _cube_fit_args(lambda_, lam_up, lam_down, accth, rel_error, chi2_rel, chi2_abs, lam_incs, max_iter, damp_max, kw))
 
 
+def gadf_batch_curves(pars, cov=None, x=None, residuals=False, first_fit=0, n_fits=None):
+    """The fitted curves of the batch that the session's last gadf_fit_batch / gadf_fit_cube / gadf_fit_frames left on its context,
+    computed on the device from the data held there and the session's model (gfh_batch_eval): for fits [first_fit, first_fit +
+    n_fits) (``n_fits`` None: to the end of the batch) at ``pars`` [n_fits][n_pars] -- the rows of those fits, as the fit returned
+    them -- with the active set ``gadf_set`` left.  Returns a dict: ``model`` f(x_i); ``residual`` (y_i - f) w_i under
+    ``residuals=True``, else None; ``band``, the 1-sigma band sqrt(g^T C g) of the curve with C = ``cov`` [n_fits][na][na], what
+    ``errors=`` returned (``out[2]['cov']``; its rows of those fits), else None; ``offsets`` [n_fits + 1].  ``x`` None: on the fits'
+    own points -- [n_fits][n_points] after gadf_fit_cube / gadf_fit_frames, flat arrays after gadf_fit_batch, which ``offsets``
+    splits.  ``x`` [n_eval]: ``model`` and ``band`` on that grid, [n_fits][n_eval]; residuals are refused there.  A fit whose
+    covariance failed (``info`` != 0) has a NaN band and nothing else."""
+    _need_init()
+    if _S.ctx is None or getattr(_S.ctx, 'n_fits', 0) < 1:
+        raise GadfitError('gadf_batch_curves: the session holds no batch (gadf_fit_batch, gadf_fit_cube or gadf_fit_frames comes first)')
+    active = [i for i, a in enumerate(_S.active) if a]
+    if not active:
+        raise GadfitError('There are no active parameters.')
+    _batch_context('gadf_batch_curves')
+    try:
+        model, residual, band, offsets, _ = _S.ctx.batch_eval(pars, active, cov=cov, x_eval=x, residuals=residuals, first_fit=first_fit, n_fits=n_fits)
+    except _lib.GadfitHipError as e:
+        raise GadfitError(str(e))
+    return dict(model=model, residual=residual, band=band, offsets=offsets)
+
+
 def gadf_print(begin=None, end=None, points=None, output=None, grouped=None, logplot=None):
     """gadfit.F90:1255-1395 writes curve / parameter files; here only the parameter table."""
     _need_init()

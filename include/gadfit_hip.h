@@ -434,13 +434,35 @@ int  gfh_batch_pass(gfh_ctx* ctx, const double* pars, int n_act, const int32_t* 
  * gfh_fit_batch_errors: gfh_fit_batch, then the covariance at the fitted parameters on the same stream -- the parameter block stays
  * on the device between the two launches and everything returns in one copy.  pars, results are the bits of gfh_fit_batch; *seconds
  * (may be NULL) = device time of both launches.
- * Not built: the covariance of a plain gfh_fit, error bands of the fitted curve, a Fortran entry, a covariance under a robust loss
+ * Not built: the covariance of a plain gfh_fit, a Fortran entry, a covariance under a robust loss
  * (a batch carries the linear loss alone). */
 int  gfh_batch_covariance(gfh_ctx* ctx, const double* pars, int n_act, const int32_t* active_pars, int scale, double* cov,
                           double* sigma, int32_t* info);
 int  gfh_fit_batch_errors(gfh_ctx* ctx, double* pars, int n_act, const int32_t* active_pars, const gfh_fit_options* opt,
                           gfh_batch_result* results, int scale, double* cov, double* sigma, int32_t* info, double* seconds);
-/* The generated source of the batch kernels (gfh_k_fit_batch, gfh_k_batch_pass, gfh_k_batch_cov: a translation unit of their own, behind the
+/* Curves of a batch: the fitted model, the weighted residuals and the 1-sigma band of the curve, computed on the device by a fourth
+ * kernel of the batch translation units (gfh_k_batch_eval) from the data held and the model's own point functions, for fits
+ * [first_fit, first_fit + n_fits_eval) of the batch held.  pars [n_fits_eval][n_pars] and cov [n_fits_eval][n_act*n_act] (as
+ * gfh_batch_covariance returns it; NULL without a band) hold the rows of the evaluated fits only: the caller slices.
+ *   x_eval NULL, n_eval 0: on the fits' own points, in the data's own layout -- ragged (gfh_set_batch_data): flat arrays with fit f
+ *     at offsets[f] - offsets[first_fit]; a cube: [n_fits_eval][n_points].
+ *       model    = f(x_i; pars)
+ *       residual = (y_i - f) w_i, with the weight as used (a cube's is formed from y by its error_type)
+ *       band     = sqrt(g^T C g), g[a] = df / dp_active_pars[a] (unweighted), C the fit's cov: t_a = sum_b C[a][b] g[b] with b
+ *                  ascending, s2 = sum_a g[a] t_a with a ascending, without contraction; a negative s2 gives 0, NaN propagates -- a
+ *                  fit whose cov is NaN (info != 0 of gfh_batch_covariance) gets NaN bands, its model and residuals stay finite.
+ *   x_eval [n_eval]: on a grid shared by all fits (finer than the data, or beyond its ends): model and band as
+ *     [n_fits_eval][n_eval]; residual must be NULL.
+ * model, residual, band: each may be NULL, at least one is not.  Without a band the value is computed without the gradient: the
+ * last bits of model may differ between a call with a band and one without.  The three lane forms return the same bits.  With
+ * gfh_batch_pass's checks and refusals under its own name; one upload, one launch (gfh_set_batch_lanes as elsewhere), one copy
+ * back; *seconds (may be NULL) = device time of the kernel.
+ * Not built: a Fortran entry, outputs in a narrow type or left on the device, a non-contiguous selection of fits, a prediction band
+ * that adds the noise term, the curves of a plain gfh_fit. */
+int  gfh_batch_eval(gfh_ctx* ctx, const double* pars, int n_act, const int32_t* active_pars, const double* cov,
+                    const double* x_eval, int64_t n_eval, int64_t first_fit, int64_t n_fits_eval,
+                    double* model, double* residual, double* band, double* seconds);
+/* The generated source of the batch kernels (gfh_k_fit_batch, gfh_k_batch_pass, gfh_k_batch_cov, gfh_k_batch_eval: a translation unit of their own, behind the
  * model's point functions) as gfh_model_source, and its compilation without a launch as gfh_model_prepare (needs no GPU). */
 int64_t gfh_batch_source(gfh_ctx* ctx, int n_act, const int32_t* active_pars, char* buf, int64_t cap);
 int  gfh_batch_prepare(gfh_ctx* ctx, int n_act, const int32_t* active_pars);
@@ -459,6 +481,9 @@ int  gfh_set_batch_lanes(gfh_ctx* ctx, int lanes);
 int  gfh_batch_auto_lanes(int n_act, int64_t longest_spectrum);
 /* 64, 16 or 256: the form of the last batch launch of this context (0: none yet).  For tests that assert the dispatch. */
 int  gfh_debug_batch_lanes(gfh_ctx* ctx);
+/* Device time of the kernel of this context's last gfh_batch_pass in seconds (HIP events around the launch; 0: none yet): the
+ * yardstick tools/bench_batch.py --eval holds gfh_batch_eval's kernel against. */
+double gfh_debug_batch_pass_seconds(gfh_ctx* ctx);
 /* A batch as a data cube: n_fits spectra of n_points each on ONE abscissa grid x [n_points], the samples y [n_fits][n_points]
  * spectrum-major in the type y_type names -- 0 double, 1 float, 2 uint16_t, each of which converts to double exactly -- and the
  * weights formed from y on the device, inside the kernels' load, by error_type's rule (the numbers and expressions of

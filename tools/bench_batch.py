@@ -10,6 +10,7 @@ profiles/r05_small_fits.txt: 1000 points, a Gaussian on a background, 4 paramete
     python tools/bench_batch.py --cube [--cells gauss4:64:16384:1000,...] [--registers] [--out profiles/batch_cube.json]
     python tools/bench_batch.py --frames [--cells uint16:1:64:131072:1000,...] [--out profiles/batch_frames.json]
     python tools/bench_batch.py --cov [--sizes 16384,131072] [--points 1000] [--lanes 64] [--out profiles/batch_cov.json]
+    python tools/bench_batch.py --eval [--cells gauss4:64:16384:1000,...] [--registers] [--observed FILE] [--out profiles/batch_eval.json]
 
 Per batch size: warm-up launches, then the median of the timed launches -- device time from the HIP events around the kernel
 (gfh_fit_batch's `seconds`) and wall time around the whole call (parameters down, launch, results back).  Two yardsticks, neither of
@@ -58,7 +59,16 @@ first yardstick), fit_batch_errors, and the route a caller had before (the secon
 parameters, numpy.linalg.inv over the batch on the host.  Wall time around each route, and the device time the library reports for
 fit_batch and for fit_batch_errors (HIP events around the one launch and around the two): their difference is what gfh_k_batch_cov
 adds on the device.  The library takes no events around gfh_k_batch_pass, so that kernel's own device time is not in the record.  No
-ratio is asserted; the medians and the min-max are written down."""
+ratio is asserted; the medians and the min-max are written down.
+--eval: the curves of a batch (gfh_batch_eval: the kernel gfh_k_batch_eval) at the cells of the cube table, on the ragged form and on
+the uint16 cube under SQRT_Y of the same counts, at the start parameters with the device's own covariance.  Per cell and form three
+calls alternate on one context: batch_pass (the first yardstick: code of the parent commit with the same loads and the same
+gfh_point_grad, timed by HIP events around its kernel), batch_eval for the model alone, and batch_eval for model, residual and band.
+Device time (events around the kernel; min, median and max over the launches) and wall time around the call.  The second yardstick:
+the bytes the kernel must move -- what the form's load reads per point (ragged 24, the uint16 cube 2: its grid is shared) plus 8 per
+requested output -- divided by the device time, as a fraction of 8 TB/s.  No ratio is asserted.  --registers: only the compiler's
+figures of gfh_k_batch_eval for model_exp2 and model_exp4 at the three lane forms; no GPU is needed.  --observed FILE: the eval_*
+maxima a GADFIT_BATCH_OBSERVE run of tests/test_gpu_batch_eval.py left, into the record; nothing is timed."""
 import argparse
 import json
 import os
@@ -163,7 +173,7 @@ ROW_MODELS = {
 
 
 def kernel_registers(src):
-    """{kernel: {vgprs, agprs, sgprs, scratch_bytes_per_lane, waves_per_simd, lds_bytes_per_block}} of the three batch kernels of a generated source"""
+    """{kernel: {vgprs, agprs, sgprs, scratch_bytes_per_lane, waves_per_simd, lds_bytes_per_block}} of the four batch kernels of a generated source"""
     import re
     import subprocess
     import tempfile
@@ -182,7 +192,7 @@ def kernel_registers(src):
         if not m:
             continue
         if m.group(1) == 'Function Name':
-            name = m.group(2) if m.group(2) in ('gfh_k_fit_batch', 'gfh_k_batch_pass', 'gfh_k_batch_cov') else None
+            name = m.group(2) if m.group(2) in ('gfh_k_fit_batch', 'gfh_k_batch_pass', 'gfh_k_batch_cov', 'gfh_k_batch_eval') else None
             if name:
                 out[name] = {}
         elif name and m.group(1) in keys:
@@ -372,6 +382,110 @@ def cov_main(a):
             with open(a.out, 'w') as fh:
                 json.dump(rec, fh, indent=1, sort_keys=True)
                 fh.write('\n')
+    print('wrote', a.out)
+
+
+EVAL_CELLS = 'gauss4:64:16384:1000,gauss4:64:131072:1000,gauss4:16:131072:64,gauss4:256:256:65536'
+
+
+def eval_registers_record():
+    """{model_lanesN: the compiler's figures of gfh_k_batch_eval}"""
+    from tests import models as M
+    rec = {}
+    c = _lib.Context(-1)
+    for name, fn, n_pars in (('exp2', M.model_exp2, 4), ('exp4', M.model_exp4, 8)):
+        c.set_model(trace_model(fn, n_pars))
+        for lanes in (64, 16, 256):
+            c.set_batch_lanes(lanes)
+            rec['%s_lanes%d' % (name, lanes)] = r = kernel_registers(c.batch_source(list(range(n_pars))))['gfh_k_batch_eval']
+            if r['scratch_bytes_per_lane'] != 0 or r['lds_bytes_per_block'] != 0:
+                sys.exit('gfh_k_batch_eval of %s at %d lanes has scratch or LDS: %s' % (name, lanes, r))
+    c.close()
+    return rec
+
+
+def _spread(v):
+    return dict(median=1e3 * statistics.median(v), min=1e3 * min(v), max=1e3 * max(v))
+
+
+def eval_main(a):
+    """batch_eval against batch_pass on the same batch in the same run, and against the bytes it must move (see the module's text)"""
+    rec = json.load(open(a.out)) if os.path.exists(a.out) else {}
+    rec = {k: v for k, v in rec.items() if k in ('registers', 'observed')}
+    rec['method'] = ('per cell (model, lanes per fit, fits, points per spectrum) and data form -- ragged doubles with precomputed SQRT_Y weights, and '
+                     'the uint16 cube under SQRT_Y of the same counts, round(%g x the model) -- three calls alternating on one context of one card in '
+                     'one run: batch_pass, batch_eval(model) and batch_eval(model, residual, band) at the start parameters with the covariance '
+                     'batch_covariance returns there; min, median and max of %d calls after %d warm-up calls; device = HIP events around the kernel, '
+                     'wall = around the call (parameters and covariances down, launch, outputs back into numpy arrays); bytes_per_point = what the '
+                     "form's load reads per point (ragged 24; uint16 2, the grid is shared) + 8 per requested output; fraction_of_8TBps = bytes_moved "
+                     '/ device time / 8e12; over_batch_pass_device_time = the medians\' ratio; no counter pass was made' % (CUBE_SCALE, a.launches, a.warmup))
+    rec['measurements'] = []
+    for cell in a.cells.split(','):
+        name, lanes, nf, n = cell.split(':')
+        lanes, nf, n = int(lanes), int(nf), int(n)
+        m = ROW_MODELS[name]
+        t0 = time.perf_counter()
+        xs, y, _ = spectra_flat(name, nf, n)
+        x = xs[:n].copy()
+        counts = np.round(CUBE_SCALE * y).reshape(nf, n)
+        del y
+        if counts.min() < 1 or counts.max() > 65535:
+            sys.exit('the counts leave uint16')
+        amp = np.where(np.arange(m['n_pars']) % 2 == 0, CUBE_SCALE, 1.0) if name == 'exp4' else np.array([CUBE_SCALE, 1.0, 1.0, CUBE_SCALE])
+        pars = np.tile(m['start'] * amp, (nf, 1))
+        print('%-6s %3d lanes %6d fits x %5d points: data in %.1f s' % (name, lanes, nf, n, time.perf_counter() - t0), flush=True)
+        ctx = _lib.Context(0)
+        ctx.set_model(trace_model(m['model'], m['n_pars']))
+        ctx.set_batch_lanes(lanes)
+        entry = dict(model=name, what=m['what'], n_active=len(m['active']), lanes=lanes, fits=nf, points=n, forms={})
+        outs = {}
+        for form, read in (('ragged', 24), ('uint16_sqrt_y', 2)):
+            if form == 'ragged':
+                ctx.set_batch_data(np.arange(nf + 1, dtype=np.int64) * n, xs, counts.reshape(-1), (1.0 / np.sqrt(counts)).reshape(-1))
+            else:
+                ctx.set_batch_cube(x, counts.astype(np.uint16), 1)
+            cov, _, info = ctx.batch_covariance(pars, m['active'])
+            if np.any(info != 0):
+                sys.exit('a covariance failed')
+            dev = dict(model=[], all=[]); wall = dict(model=[], all=[]); dev_pass = []
+            for it in range(a.warmup + a.launches):
+                ctx.batch_pass(pars, m['active'])
+                sec_pass = ctx.batch_pass_seconds()
+                t0 = time.perf_counter()
+                o1 = ctx.batch_eval(pars, m['active'])
+                t1 = time.perf_counter()
+                o3 = ctx.batch_eval(pars, m['active'], cov=cov, residuals=True)
+                t2 = time.perf_counter()
+                want = 'ragged' if form == 'ragged' else ('cube', 2, 1)
+                if ctx.batch_lanes_used() != lanes or ctx.batch_form_used() != want:
+                    sys.exit('the launch did not take the form asked for')
+                if it >= a.warmup:
+                    dev_pass.append(sec_pass); dev['model'].append(o1[4]); dev['all'].append(o3[4])
+                    wall['model'].append(t1 - t0); wall['all'].append(t2 - t1)
+            outs[form] = [np.ravel(v) for v in o3[:3]]
+            if not all(np.all(np.isfinite(v)) for v in outs[form]):
+                sys.exit('an output is not finite')
+            del o1, o3
+            e = dict(pass_device_ms=_spread(dev_pass), outputs={})
+            for what, n_out in (('model', 1), ('all', 3)):
+                o = dict(device_ms=_spread(dev[what]), wall_ms=_spread(wall[what]), bytes_per_point=read + 8 * n_out)
+                o['bytes_moved'] = o['bytes_per_point'] * nf * n
+                o['fraction_of_8TBps'] = o['bytes_moved'] / (1e-3 * o['device_ms']['median']) / 8e12
+                o['over_batch_pass_device_time'] = o['device_ms']['median'] / e['pass_device_ms']['median']
+                e['outputs'][what] = o
+            entry['forms'][form] = e
+            print('   %-14s pass %8.3f ms | model %8.3f ms [%.3f, %.3f] %.2f of pass, %.3f of 8 TB/s, wall %8.1f ms | all %8.3f ms [%.3f, %.3f] %.2f of pass, '
+                  '%.3f of 8 TB/s, wall %8.1f ms' % (form, e['pass_device_ms']['median'],
+                  *[v for w_ in ('model', 'all') for o in [e['outputs'][w_]] for v in (o['device_ms']['median'], o['device_ms']['min'], o['device_ms']['max'],
+                                                                                     o['over_batch_pass_device_time'], o['fraction_of_8TBps'], o['wall_ms']['median'])]),
+                  flush=True)
+        ctx.close()
+        entry['the_cube_returns_the_ragged_forms_bits'] = bool(all(np.array_equal(u.view(np.uint64), v.view(np.uint64)) for u, v in zip(outs['ragged'], outs['uint16_sqrt_y'])))
+        rec['measurements'].append(entry)
+        with open(a.out, 'w') as fh:          # (after every cell: a run that is cut short leaves what it measured)
+            json.dump(rec, fh, indent=1, sort_keys=True)
+            fh.write('\n')
+        del xs, counts, outs
     print('wrote', a.out)
 
 
@@ -654,7 +768,8 @@ def main():
     ap.add_argument('--cube', action='store_true', help='a batch as a data cube against the ragged form of the same spectra, into profiles/batch_cube.json')
     ap.add_argument('--frames', action='store_true', help='a stack of frames against the host transpose and the upload alone, into profiles/batch_frames.json')
     ap.add_argument('--cov', action='store_true', help='fit_batch_errors against fit_batch alone and against the host route, into profiles/batch_cov.json')
-    ap.add_argument('--cells', default=None, help='with --cube: model:lanes:fits:points, ...; with --frames: sample type:error type:lanes:fits:points, ...')
+    ap.add_argument('--eval', action='store_true', help='batch_eval against batch_pass and against the bytes it moves, into profiles/batch_eval.json')
+    ap.add_argument('--cells', default=None, help='with --cube and --eval: model:lanes:fits:points, ...; with --frames: sample type:error type:lanes:fits:points, ...')
     ap.add_argument('--models', default='gauss4,exp4', help='with --workgroup: the models measured by this call (the record keeps the others)')
     ap.add_argument('--registers', action='store_true', help='with --rows or --workgroup: only the register figures of the four kernels into the record; no GPU is needed')
     ap.add_argument('--sizes', default='1024,16384,131072')
@@ -668,9 +783,21 @@ def main():
                                                                  'nothing is timed, no GPU is needed')
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'batch_cov.json' if a.cov else 'batch_frames.json' if a.frames else 'batch_cube.json' if a.cube else 'batch_workgroup.json' if a.workgroup else 'batch_rows.json' if a.rows else 'batch_fits.json')
+        a.out = os.path.join(ROOT, 'profiles', 'batch_eval.json' if a.eval else 'batch_cov.json' if a.cov else 'batch_frames.json' if a.frames else 'batch_cube.json' if a.cube else 'batch_workgroup.json' if a.workgroup else 'batch_rows.json' if a.rows else 'batch_fits.json')
     if a.cells is None:
-        a.cells = FRAMES_CELLS if a.frames else CUBE_CELLS
+        a.cells = FRAMES_CELLS if a.frames else EVAL_CELLS if a.eval else CUBE_CELLS
+    if a.eval and (a.registers or a.observed):
+        rec = json.load(open(a.out)) if os.path.exists(a.out) else {}
+        if a.registers:
+            rec['registers'] = eval_registers_record()
+        if a.observed:
+            rec['observed'] = {k: v for k, v in json.load(open(a.observed)).items() if k.startswith('eval_')}
+        with open(a.out, 'w') as fh:
+            json.dump(rec, fh, indent=1, sort_keys=True)
+            fh.write('\n')
+        print(json.dumps({k: rec[k] for k in ('registers', 'observed') if k in rec}, indent=1, sort_keys=True))
+        print('wrote', a.out)
+        return
     if (a.rows or a.workgroup or a.cube) and a.registers:
         rec = json.load(open(a.out)) if os.path.exists(a.out) else {}
         rec['registers'] = cube_registers_record() if a.cube else registers_record((256,) if a.workgroup else (64, 16))
@@ -695,6 +822,8 @@ def main():
         return
     if a.launches < 5:
         sys.exit('at least 5 timed launches')
+    if a.eval:
+        return eval_main(a)
     if a.cov:
         if a.sizes == '1024,16384,131072':
             a.sizes = '16384,131072'
