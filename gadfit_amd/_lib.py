@@ -193,8 +193,12 @@ def ip(a):
 UNSEEN_HANDLER = C.CFUNCTYPE(_i, _vp, _vp, _i, C.POINTER(_i64), _ip, _dp, C.POINTER(C.c_uint64), _ip, _dp)
 
 
-class Context:
-    """One GPU = one image.  device=-1 gives a compile-only context (usable without a GPU)."""
+from ._batch import BatchCalls  # noqa: E402  (down here: it imports the names above)
+
+
+class Context(BatchCalls):
+    """One GPU = one image.  device=-1 gives a compile-only context (usable without a GPU).  The batched independent fits
+    (set_batch_data ... batch_eval) are the methods of _batch.BatchCalls."""
 
     def __init__(self, device=0, devices=None):
         """devices: a list of device indices (or 'all') makes a single-process device group, one member
@@ -507,318 +511,6 @@ class Context:
         self._chk(lib().gfh_fit(self._h, dp(p), a.size, ip(a), ip(g), C.byref(o), C.byref(r)))
         self.umnigh_a = o.umnigh_a
         return p.reshape(np.shape(pars)), r
-
-    # --- batched independent fits (gfh_set_batch_data, gfh_fit_batch, gfh_batch_pass)
-    def set_batch_data(self, offsets, x, y, w):
-        """the spectra of a batch back to back: fit f owns points [offsets[f], offsets[f + 1]); w are the weights of (y - f) * w"""
-        off = np.ascontiguousarray(offsets, dtype=np.int64)
-        x = np.ascontiguousarray(x, dtype=np.float64); y = np.ascontiguousarray(y, dtype=np.float64)
-        w = np.ascontiguousarray(w, dtype=np.float64)
-        if off.ndim != 1 or off.size < 2:
-            raise GadfitHipError('set_batch_data: offsets must hold n_fits + 1 >= 2 values')
-        if not (x.size == y.size == w.size == off[-1]):
-            raise GadfitHipError('set_batch_data: x, y and w must hold offsets[-1] = %d values each, got %d, %d, %d'
-                                 % (off[-1], x.size, y.size, w.size))
-        self.n_fits = 0
-        self._cube_dtype = None
-        self._batch_off, self._batch_points = off.copy(), None
-        try:
-            self._chk(lib().gfh_set_batch_data(self._h, off.size - 1, off.ctypes.data_as(C.POINTER(_i64)), dp(x), dp(y), dp(w)))
-        except GadfitHipError as e:
-            if 'no GPU bound' in str(e):       # (a compile-only context: the library has checked the geometry and keeps it, so does this object)
-                self.n_fits = off.size - 1
-            raise
-        self.n_fits = off.size - 1
-
-    def set_batch_cube(self, x, Y, error_type=0, w=None):
-        """a batch as a cube: every spectrum on the one grid x [n_points], Y [n_fits][n_points] C-contiguous in float64, float32 or
-        uint16 (uploaded as it is; any other dtype is refused, nothing is converted), the weights formed on the device by
-        error_type's rule (init_weights' numbers: 0 NONE, 1 SQRT_Y, 2 PROPTO_Y, 3 INVERSE_Y) or, under 4 (USER), w [n_fits][n_points],
-        the weights as used in (y - f) * w -- gfh_set_batch_cube"""
-        x = np.ascontiguousarray(x, dtype=np.float64)
-        if not isinstance(Y, np.ndarray) or Y.dtype not in _CUBE_TYPES:
-            raise GadfitHipError('set_batch_cube: Y must be a numpy array of float64, float32 or uint16 (it is uploaded as it is), got %s'
-                                 % (Y.dtype if isinstance(Y, np.ndarray) else type(Y).__name__))
-        if Y.ndim != 2 or not Y.flags['C_CONTIGUOUS']:
-            raise GadfitHipError('set_batch_cube: Y must be 2-D [n_fits][n_points] and C-contiguous')
-        if x.ndim != 1 or x.size != Y.shape[1]:
-            raise GadfitHipError('set_batch_cube: x must hold one abscissa per column of Y (%d), got %d' % (Y.shape[1], x.size))
-        if w is not None:
-            w = np.ascontiguousarray(w, dtype=np.float64)
-            if w.shape != Y.shape:
-                raise GadfitHipError('set_batch_cube: w must have the shape of Y %s, got %s' % (Y.shape, w.shape))
-        self.n_fits = 0
-        self._cube_dtype = Y.dtype
-        self._batch_off, self._batch_points = None, Y.shape[1]
-        try:
-            self._chk(lib().gfh_set_batch_cube(self._h, Y.shape[0], Y.shape[1], dp(x), Y.ctypes.data_as(_vp), _CUBE_TYPES[Y.dtype],
-                                               int(error_type), None if w is None else dp(w)))
-        except GadfitHipError as e:
-            if 'no GPU bound' in str(e):       # (a compile-only context keeps the geometry and the form, as under set_batch_data)
-                self.n_fits = Y.shape[0]
-            raise
-        self.n_fits = Y.shape[0]
-
-    # --- a cube from a stack of frames (gfh_batch_frames_begin, gfh_batch_frames_put, gfh_set_batch_frames)
-    def _frames_piece(self, who, what, F, dtype, n_fits):
-        if not isinstance(F, np.ndarray) or F.dtype != dtype:
-            raise GadfitHipError('%s: %s must be a numpy array of %s (it is uploaded as it is), got %s'
-                                 % (who, what, np.dtype(dtype).name, F.dtype if isinstance(F, np.ndarray) else type(F).__name__))
-        if F.ndim != 2 or not F.flags['C_CONTIGUOUS']:
-            raise GadfitHipError('%s: %s must be 2-D [n_frames][n_fits] and C-contiguous' % (who, what))
-        if n_fits is not None and F.shape[1] != n_fits:
-            raise GadfitHipError('%s: %s must hold one sample per fit of the batch in every frame (%d), got %d' % (who, what, n_fits, F.shape[1]))
-
-    def batch_frames_begin(self, x, n_fits, dtype, error_type=0):
-        """begins a cube that is filled frame by frame: the grid x [n_points], n_fits spectra, the sample type dtype (float64, float32
-        or uint16) and the weight rule as set_batch_cube; every frame is missing until batch_frames_put has put it --
-        gfh_batch_frames_begin"""
-        x = np.ascontiguousarray(x, dtype=np.float64)
-        try:
-            dtype = np.dtype(dtype)
-        except TypeError:
-            dtype = None
-        if dtype not in _CUBE_TYPES:
-            raise GadfitHipError('batch_frames_begin: dtype must be float64, float32 or uint16, got %s' % (dtype,))
-        if x.ndim != 1:
-            raise GadfitHipError('batch_frames_begin: x must be 1-D [n_points]')
-        self.n_fits = 0
-        self._cube_dtype = None
-        self._batch_off, self._batch_points = None, x.size
-        try:
-            self._chk(lib().gfh_batch_frames_begin(self._h, int(n_fits), x.size, dp(x), _CUBE_TYPES[dtype], int(error_type)))
-        except GadfitHipError as e:
-            if 'no GPU bound' in str(e):       # (a compile-only context keeps the geometry and the form, as under set_batch_cube)
-                self.n_fits = int(n_fits); self._cube_dtype = dtype
-            raise
-        self.n_fits = int(n_fits); self._cube_dtype = dtype
-
-    def batch_frames_put(self, first_frame, F_piece, w_piece=None):
-        """frames [first_frame, first_frame + len(F_piece)) of the begun batch: F_piece [n_frames][n_fits] C-contiguous in the begun
-        dtype, uploaded as it is; under USER w_piece alike, the weights as used in (y - f) * w.  In any order and any piece sizes; a
-        frame put again holds the later data -- gfh_batch_frames_put"""
-        if self.batch_frames_missing() < 0:
-            raise GadfitHipError('batch_frames_put: no batch has been begun (batch_frames_begin; set_batch_data and set_batch_cube replace a begun batch)')
-        self._frames_piece('batch_frames_put', 'F_piece', F_piece, self._cube_dtype, self.n_fits)
-        if w_piece is not None:
-            w_piece = np.ascontiguousarray(w_piece, dtype=np.float64)
-            if w_piece.shape != F_piece.shape:
-                raise GadfitHipError('batch_frames_put: w_piece must have the shape of F_piece %s, got %s' % (F_piece.shape, w_piece.shape))
-        self._chk(lib().gfh_batch_frames_put(self._h, int(first_frame), F_piece.shape[0], F_piece.ctypes.data_as(_vp),
-                                             None if w_piece is None else dp(w_piece)))
-
-    def set_batch_frames(self, x, F, error_type=0, w=None, frames_per_put=0):
-        """a batch as a stack of frames: every spectrum on the one grid x [n_points], F [n_points][n_fits] C-contiguous in float64,
-        float32 or uint16 -- one image per abscissa, the fit index fastest, uploaded as it is and transposed into the cube on the
-        device; error_type and w (frame-major as F) as set_batch_cube.  frames_per_put: frames per upload, 0 the library's rule (at
-        most 256 MiB of staging).  From here on the batch is the cube set_batch_cube(x, F.T) holds -- gfh_set_batch_frames"""
-        x = np.ascontiguousarray(x, dtype=np.float64)
-        if not isinstance(F, np.ndarray) or F.dtype not in _CUBE_TYPES:
-            raise GadfitHipError('set_batch_frames: F must be a numpy array of float64, float32 or uint16 (it is uploaded as it is), got %s'
-                                 % (F.dtype if isinstance(F, np.ndarray) else type(F).__name__))
-        if F.ndim != 2 or not F.flags['C_CONTIGUOUS']:
-            raise GadfitHipError('set_batch_frames: F must be 2-D [n_points][n_fits] and C-contiguous')
-        if x.ndim != 1 or x.size != F.shape[0]:
-            raise GadfitHipError('set_batch_frames: x must hold one abscissa per frame of F (%d), got %d' % (F.shape[0], x.size))
-        if w is not None:
-            w = np.ascontiguousarray(w, dtype=np.float64)
-            if w.shape != F.shape:
-                raise GadfitHipError('set_batch_frames: w must have the shape of F %s, got %s' % (F.shape, w.shape))
-        self.n_fits = 0
-        self._cube_dtype = None
-        self._batch_off, self._batch_points = None, F.shape[0]
-        try:
-            self._chk(lib().gfh_set_batch_frames(self._h, F.shape[1], F.shape[0], dp(x), F.ctypes.data_as(_vp), _CUBE_TYPES[F.dtype],
-                                                 int(error_type), None if w is None else dp(w), int(frames_per_put)))
-        except GadfitHipError as e:
-            if 'no GPU bound' in str(e):
-                self.n_fits = F.shape[1]; self._cube_dtype = F.dtype
-            raise
-        self.n_fits = F.shape[1]; self._cube_dtype = F.dtype
-
-    def batch_frames_missing(self):
-        """frames of the begun batch not yet put; -1: the batch held was not begun by batch_frames_begin / set_batch_frames --
-        gfh_debug_batch_frames_missing"""
-        return int(lib().gfh_debug_batch_frames_missing(self._h))
-
-    def batch_frames_seconds(self):
-        """device time of the transposing kernels of every put since the batch was begun -- gfh_debug_batch_frames_seconds"""
-        return float(lib().gfh_debug_batch_frames_seconds(self._h))
-
-    def debug_batch_read(self, which, first, count):
-        """elements [first, first + count) of the cube held, row-major [n_fits][n_points], as stored: which 0 the samples in the
-        dtype this object set or began the cube with, 1 the USER weights as float64 -- gfh_debug_batch_read"""
-        dtype = getattr(self, '_cube_dtype', None)
-        if dtype is None or getattr(self, 'n_fits', 0) < 1:
-            raise GadfitHipError('debug_batch_read: this object holds no cube (set_batch_cube, set_batch_frames, batch_frames_begin)')
-        out = np.empty(int(count), dtype=np.float64 if which == 1 else dtype)
-        self._chk(lib().gfh_debug_batch_read(self._h, int(which), int(first), int(count), out.ctypes.data_as(_vp)))
-        return out
-
-    def batch_form_used(self):
-        """the data form of the last batch launch: None (none yet), 'ragged', or ('cube', y_type, error_type) -- gfh_debug_batch_form"""
-        f = int(lib().gfh_debug_batch_form(self._h))
-        return None if f < 0 else 'ragged' if f == 0 else ('cube', (f - 1) % 3, (f - 1) // 3)
-
-    def _batch_args(self, who, pars, active):
-        p = np.ascontiguousarray(pars, dtype=np.float64).copy()
-        a = np.ascontiguousarray(active, dtype=np.int32)
-        n = getattr(self, 'n_fits', 0)
-        if n < 1:
-            raise GadfitHipError(who + ': no batch data (set_batch_data, set_batch_cube)')
-        if p.size != n * self.n_pars:
-            raise GadfitHipError('%s: pars must hold n_fits x n_pars = %d x %d values, got %d' % (who, n, self.n_pars, p.size))
-        if a.size < 1 or a.min() < 0 or a.max() >= self.n_pars:
-            raise GadfitHipError('%s: active parameter indices must lie in [0, %d)' % (who, self.n_pars))
-        return p.reshape(n, self.n_pars), a, n
-
-    def set_batch_lanes(self, lanes):
-        """lanes per fit of the batch kernels from here on: 64 a wave per fit (the default), 16 a DPP row per fit and four fits per
-        wave (short spectra), 256 a workgroup of four waves per fit (few, long spectra), 0 auto (batch_auto_lanes of the active count
-        and the longest spectrum: 16 or 64, never 256) -- gfh_set_batch_lanes"""
-        self._chk(lib().gfh_set_batch_lanes(self._h, int(lanes)))
-
-    def batch_pass_seconds(self):
-        """device time of the kernel of this context's last batch_pass (0.0: none yet) -- gfh_debug_batch_pass_seconds"""
-        return float(lib().gfh_debug_batch_pass_seconds(self._h))
-
-    def batch_lanes_used(self):
-        """64, 16 or 256: the form of the last batch launch (0: none yet) -- gfh_debug_batch_lanes"""
-        return int(lib().gfh_debug_batch_lanes(self._h))
-
-    def fit_batch(self, pars, active, DTD_min=None, lanes_per_fit=None, **kw):
-        """every spectrum of the batch fitted in one launch.  pars [n_fits][n_pars]; keyword arguments as fit(); lanes_per_fit: as
-        set_batch_lanes (it stays set), None leaves the context's setting.  Returns the fitted parameters, a numpy record array of
-        BatchResult [n_fits] and the device time of the launch in seconds."""
-        p, a, n = self._batch_args('fit_batch', pars, active)
-        if lanes_per_fit is not None:
-            self.set_batch_lanes(lanes_per_fit)
-        o, _keep = self._batch_options('fit_batch', a, DTD_min, kw)
-        res = np.zeros(n, dtype=BATCH_RESULT_DTYPE)
-        sec = C.c_double()
-        self._chk(lib().gfh_fit_batch(self._h, dp(p), a.size, ip(a), C.byref(o), res.ctypes.data_as(C.POINTER(BatchResult)),
-                                      C.cast(C.byref(sec), _dp)))
-        return p, res.view(np.recarray), sec.value
-
-    def _batch_options(self, who, a, DTD_min, kw):
-        """the FitOptions of a batch fit from fit()'s keyword arguments, and what must outlive the call with them"""
-        o = FitOptions()
-        for k, v in kw.items():
-            if v is None:
-                continue
-            name = 'lambda' if k in ('lambda_', 'lam', 'lambda') else k
-            if 'has_' + name not in _FIT_OPTION_FIELDS:
-                raise GadfitHipError('%s: unknown fit argument %r' % (who, k))
-            setattr(o, 'lambda_' if name == 'lambda' else name, v)
-            setattr(o, 'has_' + name, 1)
-        o.umnigh_a = 0.5
-        dm = None
-        if DTD_min is not None:
-            dm = np.ascontiguousarray(DTD_min, dtype=np.float64)
-            if dm.size != a.size:
-                raise GadfitHipError('%s: DTD_min must hold one value per active parameter (%d), got %d' % (who, a.size, dm.size))
-            o.DTD_min = dp(dm)
-        return o, dm
-
-    def fit_batch_errors(self, pars, active, scale=False, DTD_min=None, lanes_per_fit=None, **kw):
-        """fit_batch and, behind it on the device, each fit's parameter covariance at the fitted parameters: returns the fitted
-        parameters, the records, (cov [n_fits][na][na], sigma [n_fits][na], info [n_fits]) as batch_covariance returns them and the
-        device time of the two launches in seconds.  The parameters and records are fit_batch's bits -- gfh_fit_batch_errors"""
-        p, a, n = self._batch_args('fit_batch_errors', pars, active)
-        if lanes_per_fit is not None:
-            self.set_batch_lanes(lanes_per_fit)
-        o, _keep = self._batch_options('fit_batch_errors', a, DTD_min, kw)
-        res = np.zeros(n, dtype=BATCH_RESULT_DTYPE)
-        cov = np.zeros((n, a.size, a.size)); sigma = np.zeros((n, a.size)); info = np.zeros(n, dtype=np.int32)
-        sec = C.c_double()
-        self._chk(lib().gfh_fit_batch_errors(self._h, dp(p), a.size, ip(a), C.byref(o), res.ctypes.data_as(C.POINTER(BatchResult)),
-                                             int(scale), dp(cov), dp(sigma), ip(info), C.cast(C.byref(sec), _dp)))
-        return p, res.view(np.recarray), (cov, sigma, info), sec.value
-
-    def batch_covariance(self, pars, active, scale=False, lanes_per_fit=None):
-        """(cov [n_fits][na][na], sigma [n_fits][na], info [n_fits]) of every spectrum at pars [n_fits][n_pars]: cov = (J^T J)^-1
-        (the reference's LMsolver::getInvJTJ), under scale=True times the fit's chi2 / dof; sigma = sqrt of its diagonal; info 0, or
-        j + 1 where pivot j of the Cholesky factor failed (that fit's cov and sigma are NaN).  Rows and columns in the order of
-        `active`; lanes_per_fit as fit_batch -- gfh_batch_covariance"""
-        p, a, n = self._batch_args('batch_covariance', pars, active)
-        if lanes_per_fit is not None:
-            self.set_batch_lanes(lanes_per_fit)
-        cov = np.zeros((n, a.size, a.size)); sigma = np.zeros((n, a.size)); info = np.zeros(n, dtype=np.int32)
-        self._chk(lib().gfh_batch_covariance(self._h, dp(p), a.size, ip(a), int(scale), dp(cov), dp(sigma), ip(info)))
-        return cov, sigma, info
-
-    def batch_pass(self, pars, active, lanes_per_fit=None):
-        """(JTJ [n_fits][na][na], JTres [n_fits][na], chi2 [n_fits]) of every spectrum at pars [n_fits][n_pars] -- gfh_batch_pass;
-        lanes_per_fit as fit_batch"""
-        p, a, n = self._batch_args('batch_pass', pars, active)
-        if lanes_per_fit is not None:
-            self.set_batch_lanes(lanes_per_fit)
-        JTJ = np.zeros((n, a.size, a.size)); JTr = np.zeros((n, a.size)); chi2 = np.zeros(n)
-        self._chk(lib().gfh_batch_pass(self._h, dp(p), a.size, ip(a), dp(JTJ), dp(JTr), dp(chi2)))
-        return JTJ, JTr, chi2
-
-    def batch_eval(self, pars, active, cov=None, x_eval=None, residuals=False, first_fit=0, n_fits=None, lanes_per_fit=None, model=True):
-        """the fitted curves of fits [first_fit, first_fit + n_fits) of the batch held (n_fits None: to its end), computed on the
-        device: returns (model, residual or None, band or None, offsets, seconds).  pars [n_fits][n_pars] and cov [n_fits][na][na]
-        (batch_covariance's, or None: no band) hold the rows of the evaluated fits only.  x_eval None: on the fits' own points, in
-        the data's layout -- a cube gives [n_fits][n_points], the ragged form flat arrays that `offsets` [n_fits + 1] (relative to
-        the range) splits; model = f(x_i), residual = (y_i - f) w_i under residuals=True, band = sqrt(g^T C g) with g the gradient by
-        the active parameters in the order of `active`.  x_eval [n_eval]: model and band on that grid, [n_fits][n_eval]; residuals
-        are refused.  model=False leaves the model out (None).  A fit whose cov is NaN gets NaN bands alone.  seconds: the device
-        time of the kernel; lanes_per_fit as fit_batch -- gfh_batch_eval"""
-        nb = getattr(self, 'n_fits', 0)
-        if nb < 1:
-            raise GadfitHipError('batch_eval: no batch data (set_batch_data, set_batch_cube)')
-        first = int(first_fit)
-        n = nb - first if n_fits is None else int(n_fits)
-        a = np.ascontiguousarray(active, dtype=np.int32)
-        if a.size < 1 or a.min() < 0 or a.max() >= self.n_pars:
-            raise GadfitHipError('batch_eval: active parameter indices must lie in [0, %d)' % self.n_pars)
-        p = np.ascontiguousarray(pars, dtype=np.float64)
-        xe = None if x_eval is None else np.ascontiguousarray(x_eval, dtype=np.float64).ravel()
-        ok = first >= 0 and n >= 1 and first + n <= nb
-        if ok and p.size != n * self.n_pars:
-            raise GadfitHipError('batch_eval: pars must hold the rows of the evaluated fits, n_fits x n_pars = %d x %d values, got %d' % (n, self.n_pars, p.size))
-        if cov is not None:
-            cov = np.ascontiguousarray(cov, dtype=np.float64)
-            if ok and cov.size != n * a.size * a.size:
-                raise GadfitHipError('batch_eval: cov must hold the rows of the evaluated fits, n_fits x na x na = %d x %d x %d values, got %d'
-                                     % (n, a.size, a.size, cov.size))
-        if lanes_per_fit is not None:
-            self.set_batch_lanes(lanes_per_fit)
-        offsets = None
-        if not ok:
-            shape = (0,)          # (the library words the refusal)
-        elif xe is not None:
-            shape = (n, xe.size)
-        elif self._batch_off is None:
-            shape = (n, self._batch_points)
-        else:
-            offsets = self._batch_off[first:first + n + 1] - self._batch_off[first]
-            shape = (int(offsets[-1]),)
-        if offsets is None and ok:
-            offsets = np.arange(n + 1, dtype=np.int64) * shape[1]
-        out_m = np.empty(shape) if model else None
-        out_r = np.empty(shape) if residuals else None
-        out_b = np.empty(shape) if cov is not None else None
-        sec = C.c_double()
-        self._chk(lib().gfh_batch_eval(self._h, dp(p), a.size, ip(a), None if cov is None else dp(cov), None if xe is None else dp(xe),
-                                       0 if xe is None else xe.size, first, n, *[None if v is None else dp(v) for v in (out_m, out_r, out_b)],
-                                       C.cast(C.byref(sec), _dp)))
-        return out_m, out_r, out_b, offsets, sec.value
-
-    def batch_source(self, active):
-        a = np.ascontiguousarray(active, dtype=np.int32)
-        n = lib().gfh_batch_source(self._h, a.size, ip(a), None, 0)
-        if n < 0:
-            self._chk(1)
-        buf = C.create_string_buffer(n)
-        lib().gfh_batch_source(self._h, a.size, ip(a), buf, n)
-        return buf.value.decode()
-
-    def batch_prepare(self, active):
-        a = np.ascontiguousarray(active, dtype=np.int32)
-        self._chk(lib().gfh_batch_prepare(self._h, a.size, ip(a)))
 
     def lm_iterate(self, pars, active, is_global, n_iter, state3, DTD):
         """n_iter LM iterations without convergence exits; pars, state3, DTD are updated in place."""

@@ -182,9 +182,10 @@ struct gfh_ctx {
     bool pending = false;           // the Jacobian buffer was (re)allocated and is large: the next sweep that writes it times candidates first
   } place;
   hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  // batched independent fits (batch.cpp): the geometry gfh_set_batch_data was given (kept on the host: the argument checks of the
-  // launches read it before the device is asked for), the spectra back to back, and one block each for what a launch takes and
-  // returns -- io = [pars n_fits x n_pars | result records], img = the images of gfh_batch_pass
+  // batched independent fits: the geometry and form of the batch held (batch_data.cpp records them on the host: the argument checks
+  // of the calls read them before the device is asked for), its data on the device, and two blocks that the five launching calls
+  // share, each call sizing them for itself -- io what goes down (under gfh_fit_batch also what comes back), img what the other
+  // calls bring back; their layouts by call are at the head of batch_calls.cpp
   struct Batch {
     int64_t n_fits = 0;
     std::vector<int64_t> off;       // [n_fits + 1]

@@ -84,9 +84,7 @@ int place_jacobian_now(gfh_ctx* c, bool fused);
 extern std::recursive_mutex g_handler_mutex;
 int status_check(gfh_ctx* c, int st);
 
-// batch.cpp: nothing crosses its boundary but the C ABI (gfh_set_batch_data, gfh_set_batch_cube, gfh_batch_frames_begin / _put,
-// gfh_set_batch_frames, gfh_fit_batch, gfh_batch_pass, gfh_batch_source, gfh_batch_prepare); its generated kernels live in the
-// context's kernel cache, its one static kernel in frames.hip (kernels.h) and its blocks in gfh_ctx::batch
+// batch_data.cpp, batch_calls.cpp: what the two share is in batch_internal.h; nothing of theirs is used outside them
 
 // inspect.cpp
 double ev_ms(hipEvent_t a, hipEvent_t b);

@@ -82,7 +82,7 @@ void gfh::dev_release(int device, DevBuf& b) {
   dev_free(b);
 }
 
-// the blocks of a batch of independent fits (context.h, Batch; batch.cpp fills them): dropped together by the next
+// the blocks of a batch of independent fits (context.h, Batch; batch_data.cpp and batch_calls.cpp fill them): dropped together by the next
 // gfh_set_batch_data or gfh_set_batch_cube, and what gfh_device_memory reports of them (a cube holds its grid in x, its narrow
 // samples in y, w under USER alone and no offsets; while gfh_batch_frames_put fills it, the staging blocks of a piece as well)
 void gfh::batch_free(gfh_ctx* c) {

@@ -1,5 +1,5 @@
 // lm_options.h -- the optional arguments of gadf_fit (gadfit.F90:502-510) resolved once into what a Levenberg-Marquardt loop reads:
-// the host loop of gfh_fit (lm.cpp) and the device loop behind gfh_fit_batch (batch.cpp, which refuses what its kernels do not carry
+// the host loop of gfh_fit (lm.cpp) and the device loop behind gfh_fit_batch (batch_calls.cpp, which refuses what its kernels do not carry
 // before it comes here).  The exit tests, accth's value, max_iter and DTD_min are read from gfh_fit_options where they are used.
 #pragma once
 #include "../../include/gadfit_hip.h"

@@ -13,7 +13,7 @@ struct ModelKernels {
   hipModule_t module = nullptr;
   hipFunction_t sweep = nullptr, sweep_gram = nullptr, chi2 = nullptr, omega = nullptr;
   hipFunction_t omega_jt = nullptr;   // optional: absent for models with integrate() and with a robust loss
-  hipFunction_t fit_batch = nullptr, batch_pass = nullptr, batch_cov = nullptr, batch_eval = nullptr;   // optional: translation units generated with GenConfig::batch (batch.cpp)
+  hipFunction_t fit_batch = nullptr, batch_pass = nullptr, batch_cov = nullptr, batch_eval = nullptr;   // optional: translation units generated with GenConfig::batch (batch_calls.cpp)
   int n_active = 0;       // size of the active set the translation unit was generated for
   int omega_grid = 0;     // workgroups of gfh_k_omega resident at once (filled at its first launch)
   int kernarg_pars = 0;   // > 0: these kernels take the parameter block by value (GenConfig::kernarg_pars)

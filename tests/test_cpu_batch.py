@@ -212,6 +212,103 @@ def test_models_and_contexts_a_batch_cannot_have():
             c.close()
 
 
+def _held_nothing(c):
+    pass
+
+
+def _held_short(c):
+    _data(c, sizes=(10, 3, 9))
+
+
+def _held_begun(c):          # three spectra of six frames, none of them put
+    x = np.linspace(0.5, 9.5, 6)
+    with pytest.raises(_lib.GadfitHipError, match='no GPU'):
+        c._chk(_lib.lib().gfh_batch_frames_begin(c._h, 3, 6, _lib.dp(x), 0, 0))
+
+
+def test_of_two_refusals_the_first_in_order_wins():
+    """calls that are wrong in two ways at once, as (name, the batch held, the C call, the refusal that wins): the order of the
+    refusals of every entry point is part of what it promises"""
+    L = _lib.lib()
+    p = np.tile(M.EXP2_TRUTH, (3, 1)); P = _lib.dp(p)
+    a4 = np.arange(4, dtype=np.int32); A4 = _lib.ip(a4)
+    twice = np.array([1, 1], dtype=np.int32)
+    res = np.zeros(3, dtype=_lib.BATCH_RESULT_DTYPE); R = res.ctypes.data_as(C.POINTER(_lib.BatchResult))
+    cov = np.zeros((3, 4, 4)); sig = np.zeros((3, 4)); info = np.zeros(3, dtype=np.int32)
+    E = (_lib.dp(cov), _lib.dp(sig), _lib.ip(info))
+    img = np.zeros(3 * 21); I = _lib.dp(img)
+    x = np.linspace(0.5, 9.5, 6); X = _lib.dp(x)
+
+    def opts(**kw):
+        o = _lib.FitOptions()
+        for k, v in kw.items():
+            setattr(o, k, v); setattr(o, 'has_' + k, 1)
+        return C.byref(o)
+    bounded = opts(max_iter=1)
+    cases = [
+        # null pars and no batch held: the null argument wins over `no batch data`, under every launching call
+        ('fit_null_pars', _held_nothing, lambda c: L.gfh_fit_batch(c, None, 4, A4, bounded, R, None), 'gfh_fit_batch: null argument'),
+        ('fit_errors_null_pars', _held_nothing, lambda c: L.gfh_fit_batch_errors(c, None, 4, A4, bounded, R, 0, *E, None),
+         'gfh_fit_batch_errors: null argument'),
+        ('covariance_null_pars', _held_nothing, lambda c: L.gfh_batch_covariance(c, None, 4, A4, 0, *E), 'gfh_batch_covariance: null argument'),
+        ('pass_null_pars', _held_nothing, lambda c: L.gfh_batch_pass(c, None, 4, A4, I, I, I), 'gfh_batch_pass: null argument'),
+        ('eval_null_pars', _held_nothing, lambda c: L.gfh_batch_eval(c, None, 4, A4, None, None, 0, 0, 3, I, None, None, None),
+         'gfh_batch_eval: null argument (pars is required)'),
+        # the active set is looked at before the call's own pointers
+        ('pass_twice_null_out', _data, lambda c: L.gfh_batch_pass(c, P, 2, _lib.ip(twice), None, I, I),
+         'gfh_batch_pass: an active parameter is listed twice'),
+        ('fit_twice_null_out', _data, lambda c: L.gfh_fit_batch(c, P, 2, _lib.ip(twice), bounded, None, None),
+         'gfh_fit_batch: an active parameter is listed twice'),
+        # the options: what the loop does not carry, then the reference's own refusal, then the bound, then the geometry
+        ('fit_uphill_unbounded', _data, lambda c: L.gfh_fit_batch(c, P, 4, A4, opts(uphill=1), R, None),
+         'gfh_fit_batch: uphill != 0 is not carried by the batch kernel'),
+        ('fit_lam_incs_short', _held_short, lambda c: L.gfh_fit_batch(c, P, 4, A4, opts(lam_incs=0, max_iter=1), R, None),
+         'Input parameter lam_incs must be at least 1.'),
+        ('fit_lam_incs_unbounded', _data, lambda c: L.gfh_fit_batch(c, P, 4, A4, opts(lam_incs=0), R, None),
+         'Input parameter lam_incs must be at least 1.'),
+        ('fit_unbounded_short', _held_short, lambda c: L.gfh_fit_batch(c, P, 4, A4, opts(chi2_rel=1e-6), R, None),
+         'gfh_fit_batch: max_iter is required'),
+        # scale before the geometry, under both calls that take one
+        ('covariance_scale_short', _held_short, lambda c: L.gfh_batch_covariance(c, P, 4, A4, 2, *E),
+         'gfh_batch_covariance: scale is 0 (the inverse of J^T J) or 1 (that times chi2 / dof), got 2'),
+        ('fit_errors_scale_short', _held_short, lambda c: L.gfh_fit_batch_errors(c, P, 4, A4, bounded, R, 2, *E, None),
+         'gfh_fit_batch_errors: scale is 0 (the inverse of J^T J) or 1 (that times chi2 / dof), got 2'),
+        # a batch begun and not put: the call's own arguments first
+        ('pass_begun_null_pars', _held_begun, lambda c: L.gfh_batch_pass(c, None, 4, A4, I, I, I), 'gfh_batch_pass: null argument'),
+        ('eval_begun_null_pars', _held_begun, lambda c: L.gfh_batch_eval(c, None, 4, A4, None, None, 0, 0, 3, I, None, None, None),
+         'gfh_batch_eval: null argument (pars is required)'),
+        ('eval_begun_bad_range', _held_begun, lambda c: L.gfh_batch_eval(c, P, 4, A4, None, None, 0, 2, 3, I, None, None, None),
+         'gfh_batch_eval: 6 of 6 frames of the batch begun by gfh_batch_frames_begin have not been put'),
+        # the calls that set a batch
+        ('cube_null_y_no_fits', _data, lambda c: L.gfh_set_batch_cube(c, 0, 6, X, None, 0, 0, None),
+         'gfh_set_batch_cube: null argument (x and y are required)'),
+        ('put_negative_null_y', _held_begun, lambda c: L.gfh_batch_frames_put(c, -1, 1, None, None),
+         'gfh_batch_frames_put: first_frame is negative (-1)'),
+        ('put_not_begun_null_y', _data, lambda c: L.gfh_batch_frames_put(c, -1, 1, None, None),
+         'gfh_batch_frames_put: no batch has been begun'),
+        ('frames_y_type_per_put', _data, lambda c: L.gfh_set_batch_frames(c, 3, 6, X, X, 3, 0, None, -1),
+         'gfh_set_batch_frames: unknown y_type 3 (0 double, 1 float, 2 uint16_t)'),
+        ('frames_per_put_kept', _data, lambda c: L.gfh_set_batch_frames(c, 3, 6, X, X, 0, 0, None, -1),
+         'gfh_set_batch_frames: frames_per_put is negative'),
+    ]
+    wrong = []
+    for name, held, call, wins in cases:
+        c = _ctx()
+        try:
+            held(c)
+            rc = call(c._h)
+            said = L.gfh_last_error(c._h).decode()
+            if rc == 0 or not said.startswith(wins):
+                wrong.append((name, rc, said))
+            if name == 'frames_per_put_kept':          # refused before the batch held was replaced: it is still the ragged one
+                assert L.gfh_debug_batch_frames_missing(c._h) == -1
+                with pytest.raises(_lib.GadfitHipError, match='no GPU'):
+                    c.batch_pass(p, [0, 1, 2, 3])
+        finally:
+            c.close()
+    assert not wrong, wrong
+
+
 def test_python_api_checks_its_session():
     import gadfit_amd
     from gadfit_amd import gadfit as gf
