@@ -6,4 +6,4 @@ on gfx950 behind the C ABI in include/gadfit_hip.h.
 """
 from .ad import advar, Real, INFINITY, integrate  # noqa: F401
 from .fitfunction import fitfunc  # noqa: F401
-from .gadfit import gadf_fit_batch, gadf_fit_cube, gadf_fit_frames, gadf_batch_curves  # noqa: F401
+from .gadfit import gadf_fit_batch, gadf_fit_cube, gadf_fit_frames, gadf_batch_curves, gadf_errors, gadf_curves  # noqa: F401

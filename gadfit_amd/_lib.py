@@ -101,6 +101,13 @@ SYMBOLS = {
     'gfh_omega': (_i, [_vp, _dp, _dp, _dp]),
     'gfh_aux': (_i, [_vp, _i, _dp, _dp]),
     'gfh_fit': (_i, [_vp, _dp, _i, _ip, _ip, C.POINTER(FitOptions), C.POINTER(FitResult)]),
+    'gfh_covariance': (_i, [_vp, _dp, _i, _ip, _ip, _i, _dp, _dp, _ip]),
+    'gfh_fit_errors': (_i, [_vp, _dp, _i, _ip, _ip, C.POINTER(FitOptions), C.POINTER(FitResult), _i, _dp, _dp, _ip]),
+    'gfh_invert_normal': (_i, [_i, _dp, _i, _i, _ip, _i, C.c_double, _dp, _dp, _ip, _ip]),
+    'gfh_eval': (_i, [_vp, _dp, _i, _ip, _ip, _i, _dp, _dp, _i64, _dp, _dp, _dp, _dp]),
+    'gfh_eval_source': (_i64, [_vp, _i, _ip, C.c_char_p, _i64]),
+    'gfh_eval_prepare': (_i, [_vp, _i, _ip]),
+    'gfh_debug_eval_launches': (_i, [_vp, _i]),
     'gfh_set_batch_data': (_i, [_vp, _i64, C.POINTER(_i64), _dp, _dp, _dp]),
     'gfh_fit_batch': (_i, [_vp, _dp, _i, _ip, C.POINTER(FitOptions), C.POINTER(BatchResult), _dp]),
     'gfh_batch_pass': (_i, [_vp, _dp, _i, _ip, _dp, _dp, _dp]),
@@ -482,16 +489,78 @@ class Context(BatchCalls):
             self._chk(lib().gfh_aux(self._h, 1, dp(d), dp(out)))
         return out
 
-    def fit(self, pars, active, is_global, DTD_min=None, verbosity=0, umnigh_a=0.5, **kw):
+    def _sized_args(self, who, pars, active, is_global):
+        """(pars copy, active, is_global) of a call on the plain fit's path.  The C ABI takes plain pointers: the lengths it will
+        read and write are checked here"""
         p = np.ascontiguousarray(pars, dtype=np.float64).copy()
         a = np.ascontiguousarray(active, dtype=np.int32); g = np.ascontiguousarray(is_global, dtype=np.int32)
-        # the C ABI takes plain pointers: the lengths it will read and write are checked here
         if p.size != self.nd * self.n_pars:
-            raise GadfitHipError('fit: pars must hold n_datasets x n_pars = %d x %d values, got %d' % (self.nd, self.n_pars, p.size))
+            raise GadfitHipError('%s: pars must hold n_datasets x n_pars = %d x %d values, got %d' % (who, self.nd, self.n_pars, p.size))
         if g.size != self.n_pars:
-            raise GadfitHipError('fit: is_global must hold one flag per parameter (%d), got %d' % (self.n_pars, g.size))
+            raise GadfitHipError('%s: is_global must hold one flag per parameter (%d), got %d' % (who, self.n_pars, g.size))
         if a.size < 1 or a.min() < 0 or a.max() >= self.n_pars:
-            raise GadfitHipError('fit: active parameter indices must lie in [0, %d)' % self.n_pars)
+            raise GadfitHipError('%s: active parameter indices must lie in [0, %d)' % (who, self.n_pars))
+        return p, a, g
+
+    def covariance(self, pars, active, is_global, scale=False):
+        """(cov [dim][dim], sigma [dim], info) of the plain fit's path at pars [n_datasets][n_pars]: cov = (J^T J)^-1 (the reference's
+        LMsolver::getInvJTJ) from one sweep, under scale=True times chi2 / dof; sigma = sqrt of its diagonal; info 0, or j + 1 where
+        the pivot of column j failed (cov and sigma are then NaN).  Rows and columns in the order of jacobian_indices(active,
+        is_global) -- gfh_covariance"""
+        p, a, g = self._sized_args('covariance', pars, active, is_global)
+        dim = self.jacobian_indices(a, g)[1]
+        cov = np.zeros((dim, dim)); sigma = np.zeros(dim); info = np.zeros(1, dtype=np.int32)
+        self._chk(lib().gfh_covariance(self._h, dp(p), a.size, ip(a), ip(g), int(scale), dp(cov), dp(sigma), ip(info)))
+        return cov, sigma, int(info[0])
+
+    def eval(self, pars, active, is_global, cov=None, x_eval=None, residuals=False, model=True):
+        """the fitted curves of the plain fit's path, computed on the device: returns (model, residual or None, band or None,
+        seconds).  pars [n_datasets][n_pars]; cov [dim][dim] as covariance() returns it (None: no band).  x_eval None: on the data's
+        own points, local_count() values each in the order of residuals(): model = f(x_i), residual = (y_i - f) w_i under
+        residuals=True, band = sqrt(g^T C g) with g the gradient by the active parameters and C the dataset's block of cov.  x_eval
+        [n_eval]: model and band on that grid for every dataset, [n_datasets][n_eval]; residuals are refused.  model=False leaves the
+        model out (None).  seconds: the device time of the kernel -- gfh_eval"""
+        p, a, g = self._sized_args('eval', pars, active, is_global)
+        jac, dim = self.jacobian_indices(a, g)
+        if cov is not None:
+            cov = np.ascontiguousarray(cov, dtype=np.float64)
+            if cov.size != dim * dim:
+                raise GadfitHipError('eval: cov must hold dim x dim = %d x %d values, got %d' % (dim, dim, cov.size))
+        xe = None if x_eval is None else np.ascontiguousarray(x_eval, dtype=np.float64).ravel()
+        shape = (self.nd, xe.size) if xe is not None else (max(0, int(self.local_count())) if self.device >= 0 else 0,)
+        out_m = np.empty(shape) if model else None
+        out_r = np.empty(shape) if residuals else None
+        out_b = np.empty(shape) if cov is not None else None
+        sec = C.c_double()
+        self._chk(lib().gfh_eval(self._h, dp(p), a.size, ip(a), ip(jac), dim, None if cov is None else dp(cov), None if xe is None else dp(xe),
+                                 0 if xe is None else xe.size, *[None if v is None else dp(v) for v in (out_m, out_r, out_b)],
+                                 C.cast(C.byref(sec), _dp)))
+        return out_m, out_r, out_b, sec.value
+
+    def eval_source(self, active):
+        a = np.ascontiguousarray(active, dtype=np.int32)
+        n = lib().gfh_eval_source(self._h, a.size, ip(a), None, 0)
+        if n < 0:
+            self._chk(1)
+        buf = C.create_string_buffer(n)
+        lib().gfh_eval_source(self._h, a.size, ip(a), buf, n)
+        return buf.value.decode()
+
+    def eval_prepare(self, active):
+        a = np.ascontiguousarray(active, dtype=np.int32)
+        self._chk(lib().gfh_eval_prepare(self._h, a.size, ip(a)))
+
+    def debug_eval_launches(self, n):
+        """bench hook: the kernel of every later eval() is launched n times back to back, seconds is the last launch's -- gfh_debug_eval_launches"""
+        self._chk(lib().gfh_debug_eval_launches(self._h, int(n)))
+
+    def fit_errors(self, pars, active, is_global, scale=False, **kw):
+        """fit(), then covariance() at the fitted parameters: returns the fitted parameters, the FitResult and (cov, sigma, info); the
+        parameters and the result are fit()'s bits -- gfh_fit_errors"""
+        return self.fit(pars, active, is_global, _errors=int(scale), **kw)
+
+    def fit(self, pars, active, is_global, DTD_min=None, verbosity=0, umnigh_a=0.5, _errors=None, **kw):
+        p, a, g = self._sized_args('fit', pars, active, is_global)
         o = FitOptions()
         for k, v in kw.items():
             if v is None:
@@ -508,9 +577,15 @@ class Context(BatchCalls):
                 raise GadfitHipError('fit: DTD_min must hold dim = %d values, got %d' % (dim, dm.size))
             o.DTD_min = dp(dm)
         r = FitResult()
-        self._chk(lib().gfh_fit(self._h, dp(p), a.size, ip(a), ip(g), C.byref(o), C.byref(r)))
+        if _errors is None:
+            self._chk(lib().gfh_fit(self._h, dp(p), a.size, ip(a), ip(g), C.byref(o), C.byref(r)))
+            self.umnigh_a = o.umnigh_a
+            return p.reshape(np.shape(pars)), r
+        dim = self.jacobian_indices(a, g)[1]
+        cov = np.zeros((dim, dim)); sigma = np.zeros(dim); info = np.zeros(1, dtype=np.int32)
+        self._chk(lib().gfh_fit_errors(self._h, dp(p), a.size, ip(a), ip(g), C.byref(o), C.byref(r), _errors, dp(cov), dp(sigma), ip(info)))
         self.umnigh_a = o.umnigh_a
-        return p.reshape(np.shape(pars)), r
+        return p.reshape(np.shape(pars)), r, (cov, sigma, int(info[0]))
 
     def lm_iterate(self, pars, active, is_global, n_iter, state3, DTD):
         """n_iter LM iterations without convergence exits; pars, state3, DTD are updated in place."""
@@ -674,6 +749,21 @@ def solve_damped(jac_idx, dim, JTJ, DTD, lambda_, rhs, use_structure=True):
                               1 if use_structure else 0) != 0:
         raise GadfitHipError(lib().gfh_last_error(None).decode())
     return out
+
+
+def invert_normal(jac_idx, dim, JTJ, use_structure=True, factor=1.0):
+    """(cov [dim][dim], sigma [dim], info, form) = the covariance algebra of Context.covariance without a context: the inverse of
+    the symmetric JTJ through its upper Cholesky factor, dense (form 0) or block by block through the arrow structure of a global fit
+    (form 1), every entry times factor; info 0, or j + 1 where the pivot of column j failed (cov and sigma NaN) -- gfh_invert_normal"""
+    jac = np.ascontiguousarray(jac_idx, dtype=np.int32)
+    a = np.ascontiguousarray(JTJ, dtype=np.float64)
+    if jac.ndim != 2 or a.size != dim * dim:
+        raise GadfitHipError('invert_normal: jac_idx must be [n_datasets][n_act] and JTJ hold dim x dim = %d x %d values' % (dim, dim))
+    cov = np.zeros((dim, dim)); sigma = np.zeros(dim); info = np.zeros(1, dtype=np.int32); form = np.zeros(1, dtype=np.int32)
+    if lib().gfh_invert_normal(dim, dp(a), jac.shape[0], jac.shape[1], ip(jac), 1 if use_structure else 0, float(factor), dp(cov), dp(sigma),
+                               ip(info), ip(form)) != 0:
+        raise GadfitHipError(lib().gfh_last_error(None).decode())
+    return cov, sigma, int(info[0]), int(form[0])
 
 
 def potr(a, b):

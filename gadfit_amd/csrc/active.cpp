@@ -23,8 +23,6 @@ void gfh::apply_ws_plan(gfh_ctx* c) {
   }
 }
 
-constexpr int kMaxKernargPars = 480;   // doubles; the kernel-argument segment holds 4 KiB
-
 static int get_kernels_variant(gfh_ctx* c, const std::vector<int32_t>& active, bool load, int kernarg_pars) {
   // loaded kernels are keyed by the active set and the generator options that can change per context
   std::vector<int32_t> key = active;

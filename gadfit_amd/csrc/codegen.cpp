@@ -8,7 +8,7 @@
 // Only what depends on the tape is generated here: the point functions, the quadrature call sites, the selector and the
 // #defines in front of them (emit_ad.cpp unrolls a tape, emit_quadrature.cpp and emit_branching.cpp write what integrate() and a
 // branching eval() add).  The kernels themselves are hand-written HIP that no tape changes; they are plain files under
-// device/ (sweep.hip, fused_sweep_gram.hip, chi2.hip, omega.hip, omega_jt.hip, batch_fit.hip, batch_cov.hip, batch_eval.hip, batch_wg_sum.hip, batch_cube.hip, ...), embedded by
+// device/ (sweep.hip, fused_sweep_gram.hip, chi2.hip, omega.hip, omega_jt.hip, batch_fit.hip, batch_cov.hip, batch_eval.hip, batch_wg_sum.hip, batch_cube.hip, eval.hip, ...), embedded by
 // device_text.cpp and streamed into the translation unit by generate_source as they are.  Loading and validating a tape is
 // model.cpp.
 #include "codegen_internal.h"
@@ -295,6 +295,13 @@ bool generate_source(const Model& m, const std::vector<int32_t>& active, const G
   emit_signature_macros(u);
   if (m.branching() && !emit_selector(m, u.s, err)) return false;
   emit_point_functions(u);
+  if (cfg.eval) {                   // eval.hip: the curves of a plain fit stand alone behind the point functions
+    if (m.has_integrals()) { *err = "eval kernels: models with integrate() are not carried"; return false; }
+    if (u.NA < 1) { *err = "eval kernels: at least one active parameter"; return false; }
+    u.s << "\n#define GFH_EVAL 1\n#define GFH_EVAL_GRID " << (!m.branching() && m.n_aux == 0 ? 1 : 0) << "\n" << kEval;
+    *src = u.s.str();
+    return true;
+  }
   // ---- the hand-written kernels, in this order (the model body above is the only generated part)
   u.s << kSweep << kWaveSum << kFusedSweepGram << kChi2 << kOmega;
   if (unit_carries_omega_jt(m, cfg, u.NA)) {

@@ -35,7 +35,13 @@ struct GenConfig {
                           // units of their own: the ragged ones carry none of the three macros
   int batch_y_type = 0;   // 0 double, 1 float, 2 uint16_t
   int batch_error_type = 0; // gfh_init_weights' numbers: 0 NONE, 1 SQRT_Y, 2 PROPTO_Y, 3 INVERSE_Y, 4 USER (a plain load of w)
+  bool eval = false;      // the curves of a plain fit (eval.cpp): behind the point functions stand gfh_k_eval / gfh_k_eval_band and, for models a
+                          // grid carries, gfh_k_eval_grid / gfh_k_eval_grid_band (eval.hip) INSTEAD of the kernels of a fit.  A translation
+                          // unit of its own once more: the default one does not change by a byte
 };
+// The band of gfh_eval is carried up to this many active parameters per dataset (the block of the covariance is n^2 doubles per
+// dataset, read through the scalar cache, and the band's 2 (n^2 + n) operations are unrolled); beyond it a band is refused.
+constexpr int kEvalBandMax = 64;
 
 // Where the quadrature workspaces of a translation unit live (numerical_integration.F90:40-51, 128-134: the reference's are heap arrays
 // of the user's size).  Up to kScratchBudget bytes per lane they are private scratch (the fast form: the user's sizes capped at `fast`

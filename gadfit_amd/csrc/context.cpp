@@ -215,7 +215,7 @@ void gfh_destroy(gfh_ctx* c) {
                       &c->gb_ds, &c->ds_first_gb, &c->partial, &c->G, &c->chi2_partial, &c->packed, &c->pars, &c->dpars,
                       &c->inv, &c->dl, &c->vec, &c->slice, &c->counters, &c->tail_dev, &c->aux, &c->disp.mesh, &c->disp.tile_cost, &c->disp.tile_order, &c->disp.gb_order, &c->owner, &c->nz_row, &c->nz_col, &c->gs_meta, &c->gs_list, &c->ws.wsg,
                       &c->batch.x, &c->batch.y, &c->batch.w, &c->batch.off_d, &c->batch.io, &c->batch.img,
-                      &c->batch.stage_y, &c->batch.stage_w};
+                      &c->batch.stage_y, &c->batch.stage_w, &c->curves.io, &c->curves.out};
     for (DevBuf* b : bufs) dev_release(c->device, *b);
     // stream, events, status word and pinned buffers: parked for the next context of this device (one set), else given back
     if (!base_park(c)) {

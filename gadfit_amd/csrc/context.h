@@ -211,6 +211,10 @@ struct gfh_ctx {
     gfh::DevBuf stage_y, stage_w;
     std::vector<char> host;         // where the one device-to-host copy of a call lands
   } batch;
+  // the curves of a plain fit (gfh_eval, eval.cpp): io what goes down with the parameters -- the datasets' blocks of the covariance
+  // [n_datasets][n_act * n_act], then the caller's grid --, out the requested outputs back to back -- padded [n_slots] each on the
+  // data's own points, [n_datasets][n_eval] each on a grid.  Sized by the call at hand, kept for the next, counted by gfh_device_memory.
+  struct Curves { gfh::DevBuf io, out; int launches = 1; } curves;      // (launches: gfh_debug_eval_launches)
 };
 
 namespace gfh {

@@ -33,6 +33,7 @@ void dev_free(DevBuf& b);
 void dev_release(int device, DevBuf& b);
 void batch_free(gfh_ctx* c);
 size_t batch_bytes(const gfh_ctx* c);
+size_t curves_bytes(const gfh_ctx* c);
 int pinned_reserve(gfh_ctx* c, size_t bytes);
 int pinned_stage(gfh_ctx* c, double*& p, size_t& have, size_t bytes);
 bool base_adopt(gfh_ctx* c);
@@ -54,6 +55,7 @@ int ensure_tile_table(gfh_ctx* c);
 int set_geometry(gfh_ctx* c, int64_t n_total, int nd, const int64_t* dp);
 
 // active.cpp
+constexpr int kMaxKernargPars = 480;   // doubles of a parameter block passed by value; the kernel-argument segment holds 4 KiB
 void apply_ws_plan(gfh_ctx* c);
 int get_kernels(gfh_ctx* c, const std::vector<int32_t>& active, bool load);
 ModelKernels* nostore_kernels(gfh_ctx* c);
@@ -83,6 +85,7 @@ int place_jacobian_now(gfh_ctx* c, bool fused);
 // passes.cpp
 extern std::recursive_mutex g_handler_mutex;
 int status_check(gfh_ctx* c, int st);
+int repeat_pass(gfh_ctx* c, int rc, const double* pars);      // after kUnseen / kGrowWs / kIntegrandPath: 0 repeat the pass, 1 failed
 
 // batch_data.cpp, batch_calls.cpp: what the two share is in batch_internal.h; nothing of theirs is used outside them
 
@@ -91,5 +94,6 @@ double ev_ms(hipEvent_t a, hipEvent_t b);
 bool timed_launch(const gfh_ctx* c, long n_so_far);
 double scaled_time(double t_timed, long n_all, long n_timed);
 void harvest_events(gfh_ctx* c);
+int unpad(gfh_ctx* c, const double* dev, double* out);        // a padded device array [n_slots] into this rank's `count` points, in the caller's order
 
 }  // namespace gfh

@@ -49,5 +49,8 @@ const char kBatchCov[] = {
 const char kBatchEval[] = {
 #embed "device/batch_eval.hip"
 , 0};
+const char kEval[] = {
+#embed "device/eval.hip"
+, 0};
 
 }  // namespace gfh

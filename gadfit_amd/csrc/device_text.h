@@ -19,5 +19,6 @@ extern const char kBatchCube[];        // batch_cube.hip: the data form and the 
 extern const char kBatchFit[];         // batch_fit.hip: gfh_k_fit_batch, gfh_k_batch_pass
 extern const char kBatchCov[];         // batch_cov.hip: gfh_k_batch_cov, each fit's parameter covariance and standard errors
 extern const char kBatchEval[];        // batch_eval.hip: gfh_k_batch_eval, the fitted curves, residuals and error bands of a range of fits
+extern const char kEval[];             // eval.hip: gfh_k_eval and its three neighbours, the curves of a plain fit (units of GenConfig::eval alone)
 
 }  // namespace gfh

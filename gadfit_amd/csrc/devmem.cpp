@@ -94,6 +94,8 @@ size_t gfh::batch_bytes(const gfh_ctx* c) {
   return c->batch.x.bytes + c->batch.y.bytes + c->batch.w.bytes + c->batch.off_d.bytes + c->batch.io.bytes + c->batch.img.bytes +
          c->batch.stage_y.bytes + c->batch.stage_w.bytes;
 }
+// the blocks of gfh_eval (context.h, Curves), as gfh_device_memory counts them
+size_t gfh::curves_bytes(const gfh_ctx* c) { return c->curves.io.bytes + c->curves.out.bytes; }
 
 int gfh::pinned_reserve(gfh_ctx* c, size_t bytes) {
   if (c->h_pinned_bytes >= bytes) return 0;

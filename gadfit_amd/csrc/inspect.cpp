@@ -37,7 +37,7 @@ void gfh::harvest_events(gfh_ctx* c) {
 }
 
 // ------------------------------------------------------------------------- debug read-back
-static int unpad(gfh_ctx* c, const double* dev, double* out) {
+int gfh::unpad(gfh_ctx* c, const double* dev, double* out) {
   std::vector<double> h((size_t)c->n_slots);
   if (c->n_slots) HIPCHK(c, hipMemcpy(h.data(), dev, sizeof(double) * (size_t)c->n_slots, hipMemcpyDeviceToHost));
   for (int d = 0; d < c->nd; d++) {
@@ -276,7 +276,7 @@ int gfh_device_memory(gfh_ctx* c, int64_t* out3) {
   out3[0] = (int64_t)free_b; out3[1] = (int64_t)total_b; out3[2] = 0;
   const int n = c->grp ? gfh_group_size(c) : 1;
   for (int r = 0; r < n; r++) out3[2] += (int64_t)(c->grp ? gfh::group_member(c, r) : c)->ws.wsg.bytes;
-  out3[2] += (int64_t)batch_bytes(c);
+  out3[2] += (int64_t)batch_bytes(c) + (int64_t)curves_bytes(c);
   return 0;
 }
 

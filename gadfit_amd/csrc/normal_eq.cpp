@@ -237,4 +237,134 @@ void DampedSolver::solve(const double* rhs, double* out) {
   potrs_upper(dim, lin.data(), out);
 }
 
+// ---- the covariance (J^T J)^-1 of a fit (LMsolver::getInvJTJ, lm_solver.cpp:551-585: dpptrf + dpptri there).  The three steps are
+// those of the batch kernel gfh_k_batch_cov (device/batch_cov.hip), operation for operation: the upper factor with every pivot
+// held to "positive and finite", V = U^-1 over it, C = V V^T with every entry formed once.  No contraction: one rounding per operation.
+namespace {
+#pragma clang fp contract(off)
+int factor_checked(int n, double* a) {                    // a = U^T U, the upper triangle in place; j + 1: pivot j failed
+  auto A = [&](int i, int j) -> double& { return a[(size_t)j * n + i]; };
+  for (int j = 0; j < n; j++) {
+    double ajj = A(j, j);
+    for (int k = 0; k < j; k++) ajj -= A(k, j) * A(k, j);
+    if (!(ajj > 0.0 && ajj < HUGE_VAL)) return j + 1;
+    ajj = std::sqrt(ajj); A(j, j) = ajj;
+    const double rinv = 1.0 / ajj;
+    for (int c = j + 1; c < n; c++) {
+      double t = A(j, c);
+      for (int k = 0; k < j; k++) t -= A(k, j) * A(k, c);
+      A(j, c) = t * rinv;
+    }
+  }
+  return 0;
+}
+void invert_upper(int n, double* a) {                     // V = U^-1 over U, column by column
+  auto V = [&](int i, int j) -> double& { return a[(size_t)j * n + i]; };
+  for (int j = 0; j < n; j++) {
+    const double vjj = 1.0 / V(j, j);
+    for (int i = 0; i < j; i++) {
+      double t = V(i, i) * V(i, j);
+      for (int k = i + 1; k < j; k++) t += V(i, k) * V(k, j);
+      V(i, j) = -(t * vjj);
+    }
+    V(j, j) = vjj;
+  }
+}
+void times_transpose(int n, double* a) {                  // C = V V^T over V: each entry once, written to both triangles
+  auto V = [&](int i, int j) -> double& { return a[(size_t)j * n + i]; };
+  for (int b = 0; b < n; b++)
+    for (int r = 0; r <= b; r++) {
+      double t = V(r, b) * V(b, b);
+      for (int k = b + 1; k < n; k++) t += V(r, k) * V(b, k);
+      V(r, b) = t; V(b, r) = t;                           // (row b of V right of the diagonal is read until C(b, b), the last of column b)
+    }
+}
+}  // namespace
+
+int cholesky_inverse(int n, double* a) {
+  if (const int info = factor_checked(n, a)) return info;
+  invert_upper(n, a);
+  times_transpose(n, a);
+  return 0;
+}
+
+// The arrow form: with the local columns of dataset d as block A_d, their coupling to the global columns B_d and the global block S,
+//   S' = S - sum_d W_d^T W_d, W_d = U_d^-T B_d (the Schur complement, as factor_arrow forms it), C_gg = S'^-1,
+//   X_d = A_d^-1 B_d = V_d W_d,  Y_d = X_d C_gg,  C_dg = -Y_d,  C_dd' = [d = d'] A_d^-1 + Y_d X_d'^T.
+int DampedSolver::invert_arrow(const double* A, double* cov) const {
+#pragma clang fp contract(off)
+  const int ng = (int)gcols.size();
+  auto at = [&](int r, int c) { return r <= c ? A[(size_t)c * dim + r] : A[(size_t)r * dim + c]; };      // the upper triangle, as the dense form reads it
+  auto out = [&](int r, int c, double v) { cov[(size_t)c * dim + r] = v; cov[(size_t)r * dim + c] = v; };
+  std::vector<double> S((size_t)ng * ng), X((size_t)(wdoff.empty() ? 0 : wdoff[nd])), Y(X.size()), Ai((size_t)(udoff.empty() ? 0 : udoff[nd])), W;
+  for (int a = 0; a < ng; a++) for (int b = 0; b < ng; b++) S[(size_t)b * ng + a] = at(gcols[a], gcols[b]);
+  for (int d = 0; d < nd; d++) {
+    const int nl = loff[d + 1] - loff[d];
+    if (!nl) continue;
+    const int* lc = lcols.data() + loff[d];
+    double* U = Ai.data() + udoff[d]; double* Xd = X.data() + wdoff[d];
+    for (int a = 0; a < nl; a++) for (int b = 0; b < nl; b++) U[(size_t)b * nl + a] = at(lc[a], lc[b]);
+    if (const int info = factor_checked(nl, U)) return lc[info - 1] + 1;
+    W.assign((size_t)nl * ng, 0.0);
+    for (int g = 0; g < ng; g++) {                        // column g of W = U^-T B by forward substitution
+      double* wg = W.data() + (size_t)g * nl;
+      for (int a = 0; a < nl; a++) {
+        double t = at(lc[a], gcols[g]);
+        for (int k = 0; k < a; k++) t -= U[(size_t)a * nl + k] * wg[k];
+        wg[a] = t / U[(size_t)a * nl + a];
+      }
+    }
+    for (int g = 0; g < ng; g++) for (int h = 0; h <= g; h++) {
+      double t = 0.0;
+      for (int k = 0; k < nl; k++) t += W[(size_t)h * nl + k] * W[(size_t)g * nl + k];
+      S[(size_t)g * ng + h] -= t;                         // (the upper triangle is what the factorisation reads)
+    }
+    invert_upper(nl, U);                                  // V_d
+    for (int g = 0; g < ng; g++) for (int a = 0; a < nl; a++) {
+      double t = 0.0;
+      for (int k = a; k < nl; k++) t += U[(size_t)k * nl + a] * W[(size_t)g * nl + k];
+      Xd[(size_t)g * nl + a] = t;
+    }
+    times_transpose(nl, U);                               // A_d^-1
+  }
+  if (ng) if (const int info = cholesky_inverse(ng, S.data())) return gcols[info - 1] + 1;
+  for (int a = 0; a < ng; a++) for (int b = a; b < ng; b++) out(gcols[a], gcols[b], S[(size_t)b * ng + a]);
+  for (int d = 0; d < nd; d++) {                          // Y_d = X_d C_gg, and the coupling blocks
+    const int nl = loff[d + 1] - loff[d];
+    const int* lc = lcols.data() + loff[d]; const double* Xd = X.data() + wdoff[d]; double* Yd = Y.data() + wdoff[d];
+    for (int a = 0; a < nl; a++) for (int g = 0; g < ng; g++) {
+      double t = 0.0;
+      for (int h = 0; h < ng; h++) t += Xd[(size_t)h * nl + a] * S[(size_t)g * ng + h];
+      Yd[(size_t)g * nl + a] = t;
+      out(lc[a], gcols[g], -t);
+    }
+  }
+  for (int d = 0; d < nd; d++) {
+    const int nl = loff[d + 1] - loff[d];
+    for (int e = d; e < nd; e++) {
+      const int ne = loff[e + 1] - loff[e];
+      for (int a = 0; a < nl; a++) for (int b = (e == d ? a : 0); b < ne; b++) {
+        double t = e == d ? Ai[udoff[d] + (size_t)b * nl + a] : 0.0;
+        for (int g = 0; g < ng; g++) t += Y[wdoff[d] + (size_t)g * nl + a] * X[wdoff[e] + (size_t)g * ne + b];
+        out(lcols[loff[d] + a], lcols[loff[e] + b], t);
+      }
+    }
+  }
+  return 0;
+}
+
+int DampedSolver::invert(const double* A, double factor, double* cov, double* sigma) {
+  const size_t n2 = (size_t)dim * dim;
+  int info;
+  if (arrow_) { std::fill(cov, cov + n2, 0.0); info = invert_arrow(A, cov); }      // (columns no dataset uses stay zero)
+  else { std::copy(A, A + n2, cov); info = cholesky_inverse(dim, cov); }
+  if (info) {
+    std::fill(cov, cov + n2, std::nan("")); std::fill(sigma, sigma + dim, std::nan(""));
+    return info;
+  }
+  if (factor != 1.0) for (size_t k = 0; k < n2; k++) cov[k] *= factor;
+  for (int j = 0; j < dim; j++) sigma[j] = std::sqrt(cov[(size_t)j * dim + j]);
+  return 0;
+}
+
 }  // namespace gfh

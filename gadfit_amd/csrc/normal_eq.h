@@ -44,6 +44,14 @@ class DampedSolver {
   int factor(const double* JTJ, const double* DTD, double lambda);      // 1: not positive definite
   void solve(const double* rhs, double* out);                           // rhs and out [dim], distinct
   bool arrow() const { return arrow_; }
+  // The covariance of the fit (LMsolver::getInvJTJ, lm_solver.cpp:551-585): cov [dim * dim] = (J^T J)^-1 of the matrix itself, no
+  // damping and no DTD, dense, both triangles, symmetric bit for bit; sigma [dim] = sqrt of its diagonal.  The upper Cholesky factor
+  // U, V = U^-1 and C = V V^T with every entry formed once -- densely, or where the arrow form is on block by block: the local blocks
+  // one by one, the Schur complement of the global columns, then the blocks of the inverse from them.  Returns 0, or j + 1 where
+  // the pivot of column j was not positive and finite (cov and sigma are then NaN throughout); under the arrow form the local
+  // columns are eliminated first, dataset by dataset, and j is the failing pivot's column in the caller's numbering.  Every entry
+  // is multiplied by `factor` (1: as it is) before sigma is taken.  Throws std::bad_alloc where its work space cannot be had.
+  int invert(const double* JTJ, double factor, double* cov, double* sigma);
 
  private:
   int nd = 0, na = 0, dim = 0;
@@ -65,6 +73,12 @@ class DampedSolver {
   double Mat(int row, int col, double lambda) const { return JTJ[(size_t)col * dim + row] + (row == col ? lambda * DTD[col] : 0.0); }
   int factor_arrow(double lambda);
   void solve_arrow(const double* rhs, double* out);
+  int invert_arrow(const double* A, double* cov) const;
 };
+
+// In place, column-major n x n: the upper triangle of a symmetric matrix on entry, its inverse in both triangles on return (U, then
+// V = U^-1 over it, then V V^T; one rounding per operation, sums in ascending index).  0, or j + 1 where pivot j was not positive and
+// finite; the contents are then unspecified.
+int cholesky_inverse(int n, double* a);
 
 }  // namespace gfh

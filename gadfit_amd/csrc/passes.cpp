@@ -112,7 +112,7 @@ static int recover_integrand_path(gfh_ctx* c, const double* pars) {
   return 0;
 }
 
-static int repeat_pass(gfh_ctx* c, int rc, const double* pars) {      // 0: repeat the pass; 1: failed
+int gfh::repeat_pass(gfh_ctx* c, int rc, const double* pars) {      // 0: repeat the pass; 1: failed
   if (rc == kUnseen) return recover_unseen(c, pars);
   if (rc == kGrowWs) return grow_workspace(c);
   if (rc == kIntegrandPath) return recover_integrand_path(c, pars);

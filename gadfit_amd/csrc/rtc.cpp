@@ -107,6 +107,22 @@ bool load_kernels(const std::vector<char>& code, ModelKernels* mk, std::string* 
   return true;
 }
 
+// a translation unit generated with GenConfig::eval: gfh_k_eval behind the point functions and, for models a grid carries, gfh_k_eval_grid
+bool load_eval_kernels(const std::vector<char>& code, ModelKernels* mk, std::string* err) {
+  hipError_t e = hipModuleLoadData(&mk->module, code.data());
+  if (e != hipSuccess) { *err = std::string("hipModuleLoadData: ") + hipGetErrorString(e); return false; }
+  struct { const char* n; hipFunction_t* f; bool required; } fs[] = {{"gfh_k_eval", &mk->eval, true}, {"gfh_k_eval_band", &mk->eval_band, true},
+                                                                     {"gfh_k_eval_grid", &mk->eval_grid, false}, {"gfh_k_eval_grid_band", &mk->eval_grid_band, false}};
+  for (auto& x : fs) {
+    e = hipModuleGetFunction(x.f, mk->module, x.n);
+    if (e == hipSuccess) continue;
+    (void)hipGetLastError();
+    *x.f = nullptr;
+    if (x.required) { *err = std::string("hipModuleGetFunction(") + x.n + "): " + hipGetErrorString(e); unload_kernels(mk); return false; }
+  }
+  return true;
+}
+
 void unload_kernels(ModelKernels* mk) {
   if (mk->module) hipModuleUnload(mk->module);
   *mk = ModelKernels();

@@ -457,6 +457,56 @@ def gadf_batch_curves(pars, cov=None, x=None, residuals=False, first_fit=0, n_fi
     return dict(model=model, residual=residual, band=band, offsets=offsets)
 
 
+def _plain_call():
+    """(context, pars [n_datasets][n_pars], active, is_global) of a call on the session's fit at its current parameters"""
+    _need_init()
+    active = [i for i, a in enumerate(_S.active) if a]
+    if not active:
+        raise GadfitError('There are no active parameters.')
+    _ensure_device()
+    _S.ctx.set_loss(_S.loss)
+    return _S.ctx, np.array([[p.val for p in g.pars] for g in _S.fitfuncs]), active, [int(g) for g in _S.is_global]
+
+
+def gadf_errors(scaled=False):
+    """The parameter covariance and the standard errors of the session's fit at its current parameters -- what gadf_fit left, or
+    what gadf_set set -- with the active and global sets gadf_set left, under the loss of gadf_set_loss and the use_ad of the last
+    gadf_fit: (J^T J)^-1 from one sweep on the device (the reference's LMsolver::getInvJTJ; gfh_covariance), under ``scaled=True``
+    times chi2 / dof.  Returns a dict: ``cov`` [dim][dim]; ``sigma`` [dim], the square roots of its diagonal; ``info``, 0, or j + 1
+    where the pivot of column j failed (cov and sigma are then NaN); ``columns`` [dim], the (dataset, parameter) of every column,
+    both 1-based as gadf_set takes them, the dataset 0 for a global parameter."""
+    ctx, pars, active, is_global = _plain_call()
+    try:
+        cov, sigma, info = ctx.covariance(pars, active, is_global, scale=bool(scaled))
+    except _lib.GadfitHipError as e:
+        raise GadfitError(str(e))
+    jac, dim = ctx.jacobian_indices(active, is_global)
+    columns = [None] * dim
+    for d in range(jac.shape[0]):
+        for j, p in enumerate(active):
+            columns[jac[d, j]] = (0 if is_global[p] else d + 1, p + 1)
+    return dict(cov=cov, sigma=sigma, info=info, columns=columns)
+
+
+def gadf_curves(cov=None, x=None, residuals=False):
+    """The fitted curves of the session's fit at its current parameters, computed on the device from the data held there and the
+    session's model (gfh_eval).  Returns a dict of lists with one array per dataset, split at the data positions: ``model`` f(x_i);
+    ``residual`` (y_i - f) w_i under ``residuals=True``, else None; ``band``, the 1-sigma band sqrt(g^T C g) of each curve with C
+    the dataset's block of ``cov`` [dim][dim] as gadf_errors returned it, else None.  ``x`` None: on the data's own points.  ``x``
+    [n_eval]: ``model`` and ``band`` of every dataset on that grid; residuals are refused there."""
+    ctx, pars, active, is_global = _plain_call()
+    try:
+        model, residual, band, _ = ctx.eval(pars, active, is_global, cov=cov, x_eval=x, residuals=residuals)
+    except _lib.GadfitHipError as e:
+        raise GadfitError(str(e))
+    if x is None:
+        pos = np.concatenate([[0], np.cumsum([len(d[0]) for d in _S.datasets])])
+        split = lambda v: None if v is None else [v[pos[i]:pos[i + 1]] for i in range(_S.n_datasets)]
+    else:
+        split = lambda v: None if v is None else [v[i] for i in range(_S.n_datasets)]
+    return dict(model=split(model), residual=split(residual), band=split(band))
+
+
 def gadf_print(begin=None, end=None, points=None, output=None, grouped=None, logplot=None):
     """gadfit.F90:1255-1395 writes curve / parameter files; here only the parameter table."""
     _need_init()

@@ -386,6 +386,66 @@ int  gfh_set_lookahead(gfh_ctx* ctx, int on);
 int  gfh_fit(gfh_ctx* ctx, double* pars, int n_act, const int32_t* active_pars,
              const int32_t* is_global, gfh_fit_options* opt, gfh_fit_result* res);
 
+/* ---- Errors and curves of a plain fit: what gfh_batch_covariance and gfh_batch_eval give a fit of a batch, for gfh_fit's own path --
+ * one fit, possibly global over several datasets.  Same definitions, same order of operations.
+ *
+ * gfh_covariance: the parameter covariance (J^T J)^-1 and the standard errors at pars [n_datasets][n_pars] (LMsolver::getJTJ /
+ * getInvJTJ, lm_solver.cpp:551-585).  One STEP 1 + 2 pass through gfh_sweep's route -- the pars hook, a repeated pass after an unseen
+ * path, the sum over ranks and device groups, the robust loss and finite differences as set -- then on the host (normal_eq.cpp) the
+ * upper Cholesky factor of J^T J itself (no damping, no DTD; a pivot is accepted only if it is positive and finite), V = U^-1 and
+ * C = V V^T with every entry formed once; for a global fit block by block through the arrow structure the damped solve uses
+ * (gfh_solve_damped), where that applies.  cov [dim * dim], dense, both triangles, symmetric bit for bit, rows and columns in the
+ * order of gfh_jacobian_indices; sigma [dim] = sqrt of its diagonal; *info 0, or j + 1 where the pivot of column j failed -- cov and
+ * sigma are then NaN throughout (under the arrow form the local columns are eliminated first, so j may differ from the dense form's).
+ * scale 0: the reference's getInvJTJ (under a robust loss the inverse of the scaled J^T J, as there); scale 1: every entry times
+ * chi2 / dof, chi2 what gfh_chi2 returns at pars -- the sweep's own sum r^2 where that is bitwise the same (linear loss, fused
+ * kernel: nothing more is launched), else a chi2 pass in front of the sweep -- and dof gfh_fit's (gadfit.F90:648-657; 1 where it
+ * would be 0).  The context is left as gfh_sweep at pars leaves it.  A dim whose dense image cannot be allocated is refused.
+ * gfh_fit_errors: gfh_fit, then gfh_covariance at the fitted parameters; pars and the result are gfh_fit's bits.
+ * gfh_invert_normal: the algebra alone, without a context (host code, needs no GPU; errors through gfh_last_error(NULL)): JTJ
+ * [dim * dim] symmetric, jac_idx [n_datasets][n_act]; use_structure as gfh_solve_damped; every entry times factor (1: as it is);
+ * *form (may be NULL) 1 where the arrow form was taken, 0 the dense one. */
+int  gfh_covariance(gfh_ctx* ctx, const double* pars, int n_act, const int32_t* active_pars, const int32_t* is_global, int scale,
+                    double* cov, double* sigma, int32_t* info);
+int  gfh_fit_errors(gfh_ctx* ctx, double* pars, int n_act, const int32_t* active_pars, const int32_t* is_global, gfh_fit_options* opt,
+                    gfh_fit_result* res, int scale, double* cov, double* sigma, int32_t* info);
+int  gfh_invert_normal(int dim, const double* JTJ, int n_datasets, int n_act, const int32_t* jac_idx, int use_structure, double factor,
+                       double* cov, double* sigma, int32_t* info, int32_t* form);
+/* gfh_eval: the fitted model, the weighted residuals and the 1-sigma band of the curve, computed on the device by generated kernels
+ * of their own translation unit (gfh_k_eval, gfh_k_eval_band and on a grid gfh_k_eval_grid, gfh_k_eval_grid_band: device/eval.hip
+ * behind the model's point functions) from the data the context holds.  pars [n_datasets][n_pars]; cov [dim * dim] as
+ * gfh_covariance returns it with jac_idx [n_datasets][n_act] and dim of gfh_jacobian_indices (NULL without a band): dataset d's band
+ * is formed with its n_act x n_act block cov[jac_idx[d][a]][jac_idx[d][b]], which holds its global and local columns and their coupling.
+ *   x_eval NULL, n_eval 0: on the data's own points, this rank's gfh_local_count points in the order of gfh_get_residuals:
+ *       model    = f(x_i; P_d)
+ *       residual = (y_i - f) w_i, chi2()'s plain residual (gadfit.F90:682-683), also under a robust loss; without a band bit for bit
+ *                  what gfh_get_residuals returns after gfh_chi2 at pars
+ *       band     = sqrt(g^T C_d g), g[a] = df / dp_active_pars[a] (unweighted; under use_ad = 0 the sweep's forward difference):
+ *                  t_a = sum_b C[a][b] g[b] with b ascending, s2 = sum_a g[a] t_a with a ascending, without contraction; a negative
+ *                  s2 gives 0, NaN propagates -- a NaN cov gives NaN bands, model and residuals stay finite.
+ *     Carried: plain and branching models (decided per point on the device; an unseen path is handled as gfh_chi2 handles it),
+ *     auxiliary columns, the pars hook, automatic differentiation and use_ad = 0.
+ *   x_eval [n_eval]: on a grid shared by all datasets, each with its own parameter row: model and band as [n_datasets][n_eval];
+ *     residual must be NULL.  Carried: what the batch kernels carry -- one recorded path, no auxiliary columns.
+ * model, residual, band: each may be NULL, at least one is not.  Without a band the value is computed without the gradient: the last
+ * bits of model may differ between a call with a band and one without.  A band is carried up to 64 active parameters per dataset
+ * and refused beyond, with the count.  Refused as well, each with its own message before the device is asked for: models with
+ * integrate(), group handles and contexts that are one of several ranks.  The context's residuals, Jacobian and active set are left
+ * as they were; the two blocks of the call (the covariance blocks and the grid; the outputs) are counted by gfh_device_memory.
+ * *seconds (may be NULL) = device time of the kernel.
+ * gfh_eval_source / gfh_eval_prepare: the generated source of that unit and its compilation without a launch, as gfh_model_source /
+ * gfh_model_prepare (need no GPU).
+ * Not built: a Fortran entry, outputs left on the device or in a narrow type, a prediction band that adds the noise term, curve
+ * files as gadf_print writes them, gfh_eval over several ranks or a device group, models with integrate(). */
+int  gfh_eval(gfh_ctx* ctx, const double* pars, int n_act, const int32_t* active_pars, const int32_t* jac_idx, int dim, const double* cov,
+              const double* x_eval, int64_t n_eval, double* model, double* residual, double* band, double* seconds);
+int64_t gfh_eval_source(gfh_ctx* ctx, int n_act, const int32_t* active_pars, char* buf, int64_t cap);
+int  gfh_eval_prepare(gfh_ctx* ctx, int n_act, const int32_t* active_pars);
+/* Bench hook: the kernel of every later gfh_eval of this context is launched n (1 ... 1000) times back to back, with the same arguments
+ * and the same outputs, and *seconds is the device time of the last of them (tools/bench_eval.py: past the slow launches after an
+ * idle gap).  1: as it was. */
+int  gfh_debug_eval_launches(gfh_ctx* ctx, int n);
+
 /* n_iter iterations of the basic LM scheme without convergence exits (bench / profiling):
  * each = gfh_sweep + damped solve + parameter update + chi2 at the trial parameters (gfh_chi2,
  * or with look-ahead the sweep at the trial point, which an accepted step hands to the next
@@ -434,8 +494,8 @@ int  gfh_batch_pass(gfh_ctx* ctx, const double* pars, int n_act, const int32_t* 
  * gfh_fit_batch_errors: gfh_fit_batch, then the covariance at the fitted parameters on the same stream -- the parameter block stays
  * on the device between the two launches and everything returns in one copy.  pars, results are the bits of gfh_fit_batch; *seconds
  * (may be NULL) = device time of both launches.
- * Not built: the covariance of a plain gfh_fit, a Fortran entry, a covariance under a robust loss
- * (a batch carries the linear loss alone). */
+ * Not built: a Fortran entry, a covariance under a robust loss (a batch carries the linear loss alone).  The covariance of a plain
+ * gfh_fit is gfh_covariance. */
 int  gfh_batch_covariance(gfh_ctx* ctx, const double* pars, int n_act, const int32_t* active_pars, int scale, double* cov,
                           double* sigma, int32_t* info);
 int  gfh_fit_batch_errors(gfh_ctx* ctx, double* pars, int n_act, const int32_t* active_pars, const gfh_fit_options* opt,
@@ -458,7 +518,7 @@ int  gfh_fit_batch_errors(gfh_ctx* ctx, double* pars, int n_act, const int32_t* 
  * gfh_batch_pass's checks and refusals under its own name; one upload, one launch (gfh_set_batch_lanes as elsewhere), one copy
  * back; *seconds (may be NULL) = device time of the kernel.
  * Not built: a Fortran entry, outputs in a narrow type or left on the device, a non-contiguous selection of fits, a prediction band
- * that adds the noise term, the curves of a plain gfh_fit. */
+ * that adds the noise term.  The curves of a plain gfh_fit are gfh_eval. */
 int  gfh_batch_eval(gfh_ctx* ctx, const double* pars, int n_act, const int32_t* active_pars, const double* cov,
                     const double* x_eval, int64_t n_eval, int64_t first_fit, int64_t n_fits_eval,
                     double* model, double* residual, double* band, double* seconds);
