@@ -1,5 +1,5 @@
 """The batch methods of _lib.Context: batched independent fits behind gfh_set_batch_data / _cube / _frames (the batch a context holds)
-and gfh_fit_batch, gfh_fit_batch_errors, gfh_batch_covariance, gfh_batch_pass, gfh_batch_eval (what is done with it).  The C ABI
+and gfh_fit_batch, gfh_fit_batch_errors, gfh_fit_batch_bounded, gfh_batch_covariance, gfh_batch_pass, gfh_batch_eval (what is done with it).  The C ABI
 takes plain pointers, so the lengths it will read and write are checked here; everything else is the library's to refuse."""
 import ctypes as C
 
@@ -227,6 +227,25 @@ class BatchCalls:
         self._chk(lib().gfh_fit_batch_errors(*args, int(scale), dp(cov), dp(sigma), ip(info), C.cast(C.byref(sec), _dp)))
         return p, res.view(np.recarray), (cov, sigma, info), sec.value
 
+    def fit_batch_bounded(self, pars, active, lower, upper, DTD_min=None, lanes_per_fit=None, **kw):
+        """fit_batch inside one box per batch: lower and upper hold one value per active parameter, in the order of `active`, -inf /
+        +inf for no bound on that side.  Returns the fitted parameters, the records, at_bound [n_fits] (int32: bit j where the
+        returned active parameter j equals lower[j], bit 8 + j where it equals upper[j]) and the device time of the launch in seconds.
+        With no finite bound the parameters and records are fit_batch's bits -- gfh_fit_batch_bounded"""
+        who = 'fit_batch_bounded'
+        p, a, n = self._batch_args(who, pars, active, lanes_per_fit)
+        lo = np.ascontiguousarray(lower, dtype=np.float64); hi = np.ascontiguousarray(upper, dtype=np.float64)
+        for name, v in (('lower', lo), ('upper', hi)):
+            if v.ndim != 1 or v.size != a.size:
+                raise GadfitHipError('%s: %s must hold one value per active parameter (%d), got %d' % (who, name, a.size, v.size))
+        o, _keep = self._batch_options(who, a, DTD_min, kw)
+        res = np.zeros(n, dtype=BATCH_RESULT_DTYPE)
+        at = np.zeros(n, dtype=np.int32)
+        sec = C.c_double()
+        self._chk(lib().gfh_fit_batch_bounded(self._h, dp(p), a.size, ip(a), dp(lo), dp(hi), C.byref(o), res.ctypes.data_as(C.POINTER(BatchResult)),
+                                              ip(at), C.cast(C.byref(sec), _dp)))
+        return p, res.view(np.recarray), at, sec.value
+
     def fit_batch_errors(self, pars, active, scale=False, DTD_min=None, lanes_per_fit=None, **kw):
         """fit_batch and, behind it on the device, each fit's parameter covariance at the fitted parameters: returns the fitted
         parameters, the records, (cov [n_fits][na][na], sigma [n_fits][na], info [n_fits]) as batch_covariance returns them and the
@@ -296,15 +315,17 @@ class BatchCalls:
                                        C.cast(C.byref(sec), _dp)))
         return out_m, out_r, out_b, offsets, sec.value
 
-    def batch_source(self, active):
+    def batch_source(self, active, bounded=False):
+        """the text of the batch unit of an active set; bounded=True: of the unit that holds gfh_k_fit_batch_bounded"""
+        source = lib().gfh_batch_source_bounded if bounded else lib().gfh_batch_source
         a = np.ascontiguousarray(active, dtype=np.int32)
-        n = lib().gfh_batch_source(self._h, a.size, ip(a), None, 0)
+        n = source(self._h, a.size, ip(a), None, 0)
         if n < 0:
             self._chk(1)
         buf = C.create_string_buffer(n)
-        lib().gfh_batch_source(self._h, a.size, ip(a), buf, n)
+        source(self._h, a.size, ip(a), buf, n)
         return buf.value.decode()
 
-    def batch_prepare(self, active):
+    def batch_prepare(self, active, bounded=False):
         a = np.ascontiguousarray(active, dtype=np.int32)
-        self._chk(lib().gfh_batch_prepare(self._h, a.size, ip(a)))
+        self._chk((lib().gfh_batch_prepare_bounded if bounded else lib().gfh_batch_prepare)(self._h, a.size, ip(a)))

@@ -114,6 +114,9 @@ SYMBOLS = {
     'gfh_batch_covariance': (_i, [_vp, _dp, _i, _ip, _i, _dp, _dp, _ip]),
     'gfh_fit_batch_errors': (_i, [_vp, _dp, _i, _ip, C.POINTER(FitOptions), C.POINTER(BatchResult), _i, _dp, _dp, _ip, _dp]),
     'gfh_batch_eval': (_i, [_vp, _dp, _i, _ip, _dp, _dp, _i64, _i64, _i64, _dp, _dp, _dp, _dp]),
+    'gfh_fit_batch_bounded': (_i, [_vp, _dp, _i, _ip, _dp, _dp, C.POINTER(FitOptions), C.POINTER(BatchResult), _ip, _dp]),
+    'gfh_batch_source_bounded': (_i64, [_vp, _i, _ip, C.c_char_p, _i64]),
+    'gfh_batch_prepare_bounded': (_i, [_vp, _i, _ip]),
     'gfh_batch_source': (_i64, [_vp, _i, _ip, C.c_char_p, _i64]),
     'gfh_batch_prepare': (_i, [_vp, _i, _ip]),
     'gfh_set_batch_lanes': (_i, [_vp, _i]),

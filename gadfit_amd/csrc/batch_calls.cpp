@@ -1,5 +1,6 @@
 // batch_calls.cpp -- what is done with the batch a context holds (batch_data.cpp): many Levenberg-Marquardt fits of ONE model in ONE
-// kernel launch, each with its own data, start parameters, lambda history and exit (gfh_fit_batch, gfh_fit_batch_errors), and their
+// kernel launch, each with its own data, start parameters, lambda history and exit (gfh_fit_batch, gfh_fit_batch_errors,
+// gfh_fit_batch_bounded: the same loop inside one box per batch, device/batch_fit_bounded.hip, in a unit of its own), and their
 // neighbours at given parameters (gfh_batch_pass, gfh_batch_covariance, gfh_batch_eval); gfh_batch_source, gfh_batch_prepare and
 // gfh_set_batch_lanes.  The loop itself (gadfit.F90:670-915) is the generated kernel gfh_k_fit_batch (device/batch_fit.hip; codegen.cpp,
 // emit_batch_kernels), a wave per fit or -- gfh_set_batch_lanes(16) -- a DPP row of 16 lanes per fit and four fits per wave, or --
@@ -11,6 +12,7 @@
 // (context.h, Batch) by call, each the size of the call at hand:
 //   gfh_fit_batch         io = [pars n_fits x n_pars | records n_fits], down its head, back whole
 //   gfh_fit_batch_errors  io = [pars | records | ErrorBlock], likewise
+//   gfh_fit_batch_bounded io = [pars | records | at_bound n_fits], likewise
 //   gfh_batch_covariance  io = [pars] down, img = ErrorBlock back
 //   gfh_batch_pass        io = [pars] down, img = n_fits records [J^T J na x na | J^T r na | chi2] back
 //   gfh_batch_eval        io = [pars | cov | x_eval] of the evaluated fits down, staged in batch.host; img = [model | residual | band],
@@ -18,6 +20,7 @@
 #include "batch_internal.h"
 #include "lm_options.h"
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <exception>
 #include <initializer_list>
@@ -75,11 +78,12 @@ int check_held(gfh_ctx* c, const char* who, int na) {
 
 // the translation unit of an active set with the four batch kernels: generated, compiled and (load) loaded once per context, kept
 // in the context's kernel cache under a key no plain active set has, so that a new model or gfh_destroy releases it with the rest
-GenConfig batch_config(const gfh_ctx* c, int lanes) {
+GenConfig batch_config(const gfh_ctx* c, int lanes, bool bounded) {
   GenConfig cfg;                    // the defaults, not the context's current switches: one form per (model, active set, lanes per fit)
   cfg.fast_div = c->gen.fast_div;
   cfg.batch = true;
   cfg.batch_lanes = lanes;
+  cfg.batch_bounded = bounded;      // gfh_k_fit_batch_bounded in place of the four kernels: a unit of its own
   cfg.batch_cube = c->batch.cube;   // the data form held: a cube's sample type and weight rule are part of the text (batch_cube.hip)
   if (c->batch.cube) { cfg.batch_y_type = c->batch.y_type; cfg.batch_error_type = c->batch.error_type; }
   return cfg;
@@ -89,15 +93,15 @@ int batch_lanes(const gfh_ctx* c, int na) {
   if (c->batch.lanes != 0) return c->batch.lanes;
   return c->batch.n_fits < 1 ? 64 : gfh_batch_auto_lanes(na, c->batch.max_points);
 }
-int batch_kernels(gfh_ctx* c, const std::vector<int32_t>& active, int lanes, bool load, ModelKernels** out) {
+int batch_kernels(gfh_ctx* c, const std::vector<int32_t>& active, int lanes, bool bounded, bool load, ModelKernels** out) {
   std::vector<int32_t> key = active;
-  key.push_back(-(1 << 30));        // (no plain active set holds a negative entry)
+  key.push_back(bounded ? -(1 << 30) - 2 : -(1 << 30));      // (no plain active set holds a negative entry; an eval unit holds -(1 << 30) - 1 here)
   key.push_back(lanes);             // both forms of one active set can be resident
   if (c->batch.cube) key.push_back(data_form(c));      // ... and so can its cube forms beside the ragged one (whose key stays what it was)
   auto it = c->kernel_cache.find(key);
   if (it != c->kernel_cache.end()) { if (out) *out = &it->second; return 0; }
   std::string src, err;
-  if (!generate_source(c->model, active, batch_config(c, lanes), &src, &err)) return fail(c, err);
+  if (!generate_source(c->model, active, batch_config(c, lanes, bounded), &src, &err)) return fail(c, err);
   ModelKernels mk;
   const uint64_t skey = load ? source_key(src) : 0;
   if (!(load && acquire_loaded(c->device, skey, &mk))) {
@@ -107,7 +111,7 @@ int batch_kernels(gfh_ctx* c, const std::vector<int32_t>& active, int lanes, boo
     if (!load_kernels(code, &mk, &err)) return fail(c, err);
     publish_loaded(c->device, skey, mk);
   }
-  if (!mk.fit_batch || !mk.batch_pass || !mk.batch_cov || !mk.batch_eval) { release_loaded(c->device, &mk); return fail(c, "the batch kernels are missing from their code object"); }
+  if (bounded ? !mk.fit_batch_bounded : !mk.fit_batch || !mk.batch_pass || !mk.batch_cov || !mk.batch_eval) { release_loaded(c->device, &mk); return fail(c, "the batch kernels are missing from their code object"); }
   mk.n_active = (int)active.size();
   ModelKernels* p = &c->kernel_cache.emplace(key, mk).first->second;
   if (out) *out = p;
@@ -116,11 +120,11 @@ int batch_kernels(gfh_ctx* c, const std::vector<int32_t>& active, int lanes, boo
 
 // The device side of a call, opened under the caller's name: the GPU, the batch on it, the lane form and its loaded kernels
 struct Opened { ModelKernels* mk = nullptr; int lanes = 0; };
-int open_device(gfh_ctx* c, const char* who, int na, const int32_t* active, Opened* k) {
+int open_device(gfh_ctx* c, const char* who, int na, const int32_t* active, Opened* k, bool bounded = false) {
   NEED_GPU(c);
   if (!c->batch.on_device) return fail(c, std::string(who) + ": no batch data on the device (gfh_set_batch_data, gfh_set_batch_cube)");
   k->lanes = batch_lanes(c, na);
-  return batch_kernels(c, std::vector<int32_t>(active, active + na), k->lanes, true, &k->mk);
+  return batch_kernels(c, std::vector<int32_t>(active, active + na), k->lanes, bounded, true, &k->mk);
 }
 // One launch of a batch kernel over n fits of the batch held, on the context's stream: workgroups of 256 threads, 256 / lanes fits
 // each.  Every kernel's arguments are the data's four (GFH_BARGS: x, y, w and the offsets -- of a cube, n_points in their place),
@@ -221,9 +225,79 @@ int fit_batch(gfh_ctx* c, const char* who_, double* pars, int na, const int32_t*
   return 0;
 }
 
+// the text of a batch unit, the four kernels' or the bounded one, into the caller's buffer
+int64_t batch_source(gfh_ctx* c, const char* who, int na, const int32_t* active, bool bounded, char* buf, int64_t cap) {
+  if (check_batchable(c, who, na, active)) return -1;
+  std::string src, err;
+  if (!generate_source(c->model, std::vector<int32_t>(active, active + na), batch_config(c, batch_lanes(c, na), bounded), &src, &err)) { fail(c, err); return -1; }
+  if (buf && cap > 0) { const size_t n = std::min<size_t>((size_t)cap - 1, src.size()); memcpy(buf, src.data(), n); buf[n] = 0; }
+  return (int64_t)src.size() + 1;
+}
+
+// The box of gfh_fit_batch_bounded as the kernel takes it by value (batch_fit_bounded.hip: gfh_batch_box), and its refusals
+struct BatchBox { double lo[kValuGramMax], hi[kValuGramMax]; };
+static_assert(sizeof(BatchBox) == 2 * 8 * kValuGramMax && kValuGramMax <= 8, "layout shared with the generated kernel; at_bound holds 8 + 8 bits");
+int batch_box(gfh_ctx* c, const std::string& who, int na, const double* lower, const double* upper, BatchBox* out) {
+  BatchBox b;
+  for (int j = 0; j < kValuGramMax; j++) { b.lo[j] = -HUGE_VAL; b.hi[j] = HUGE_VAL; }
+  for (int j = 0; j < na; j++) {
+    const std::string pj = "active parameter " + std::to_string(j);
+    if (std::isnan(lower[j]) || std::isnan(upper[j])) return fail(c, who + ": a bound of " + pj + " is NaN (-inf / +inf: no bound on that side)");
+    if (lower[j] == HUGE_VAL) return fail(c, who + ": the lower bound of " + pj + " is +inf (-inf: no lower bound)");
+    if (upper[j] == -HUGE_VAL) return fail(c, who + ": the upper bound of " + pj + " is -inf (+inf: no upper bound)");
+    if (lower[j] >= upper[j])
+      return fail(c, who + ": the box of " + pj + " is empty or a single value (lower " + std::to_string(lower[j]) + " >= upper " +
+                     std::to_string(upper[j]) + "); make that parameter passive instead");
+    b.lo[j] = lower[j]; b.hi[j] = upper[j];
+  }
+  *out = b;
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+// gfh_fit_batch inside one box per batch: lower[na] <= p <= upper[na] in the order of active, -inf / +inf for no bound on that side,
+// by the projected loop gfh_k_fit_batch_bounded (device/batch_fit_bounded.hip states the rule).  at_bound [n_fits]: bit j where the
+// returned active parameter j == lower[j], bit 8 + j where it == upper[j].  One launch; at_bound rides in io behind the records.
+int gfh_fit_batch_bounded(gfh_ctx* c, double* pars, int na, const int32_t* active, const double* lower, const double* upper,
+                          const gfh_fit_options* o, gfh_batch_result* results, int32_t* at_bound, double* seconds) try {
+  const char* who_ = "gfh_fit_batch_bounded";
+  const std::string who(who_);
+  if (check_batchable(c, who_, na, active)) return 1;
+  if (!pars || !lower || !upper || !results || !at_bound) return fail(c, who + ": null argument");
+  BatchBox box; BatchOpts bo;
+  if (batch_box(c, who, na, lower, upper, &box) || batch_options(c, who, o, na, &bo) || check_held(c, who_, na)) return 1;
+  const int64_t nf = c->batch.n_fits;
+  const int np = c->model.n_pars;
+  for (int64_t f = 0; f < nf; f++)
+    for (int j = 0; j < na; j++) {
+      const double p = pars[(size_t)f * np + active[j]];
+      if (p < lower[j] || p > upper[j])
+        return fail(c, who + ": the start of fit " + std::to_string((long long)f) + " lies outside the box at active parameter " + std::to_string(j) +
+                       " (parameter " + std::to_string(active[j]) + ")");
+    }
+  gfh::Range range("gadfit gfh_fit_batch_bounded");
+  Opened k;
+  if (open_device(c, who_, na, active, &k, true)) return 1;
+  const size_t pb = sizeof(double) * (size_t)nf * (size_t)np, rb = sizeof(gfh_batch_result) * (size_t)nf, ab = sizeof(int32_t) * (size_t)nf;
+  if (dev_alloc(c, c->batch.io, pb + rb + ab)) return 1;
+  c->batch.host.resize(pb + rb + ab);
+  harvest_events(c);
+  HIPCHK(c, hipMemcpyAsync(c->batch.io.p, pars, pb, hipMemcpyHostToDevice, c->stream));
+  void* dp = c->batch.io.p; void* recs = c->batch.io.as<char>() + pb; void* at = c->batch.io.as<char>() + pb + rb; long long n = nf;
+  HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+  if (launch_batch(c, k.mk->fit_batch_bounded, k.lanes, nf, {&dp, &bo, &box, &recs, &at, &n})) return 1;
+  HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->batch.host.data(), c->batch.io.p, pb + rb + ab, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  memcpy(pars, c->batch.host.data(), pb);
+  memcpy(results, c->batch.host.data() + pb, rb);
+  memcpy(at_bound, c->batch.host.data() + pb + rb, ab);
+  if (seconds) *seconds = 1e-3 * ev_ms(c->ev[0], c->ev[1]);
+  return 0;
+} catch (const std::exception& e) { return fail(c, std::string("gfh_fit_batch_bounded: ") + e.what()); }
 
 // gadf_fit (gadfit.F90:502-1035) for every spectrum of the batch at once: STEP 1+2, the damped solve (potr_f08,
 // gadfit_linalg.F90:36-57), STEP 3 under accth, STEP 4 with its retrials and STEP 5 run on the device, a wave or -- gfh_set_batch_lanes --
@@ -357,18 +431,23 @@ int gfh_batch_eval(gfh_ctx* c, const double* pars, int na, const int32_t* active
 // The generated source of the batch translation unit for the current model and an active set, as gfh_model_source: in the form of
 // the context's setting (under auto: what the rule gives for the geometry held, 64 without one); gfh_batch_prepare alike.
 int64_t gfh_batch_source(gfh_ctx* c, int na, const int32_t* active, char* buf, int64_t cap) try {
-  if (check_batchable(c, "gfh_batch_source", na, active)) return -1;
-  std::string src, err;
-  if (!generate_source(c->model, std::vector<int32_t>(active, active + na), batch_config(c, batch_lanes(c, na)), &src, &err)) { fail(c, err); return -1; }
-  if (buf && cap > 0) { const size_t n = std::min<size_t>((size_t)cap - 1, src.size()); memcpy(buf, src.data(), n); buf[n] = 0; }
-  return (int64_t)src.size() + 1;
+  return batch_source(c, "gfh_batch_source", na, active, false, buf, cap);
 } catch (const std::exception& e) { fail(c, std::string("gfh_batch_source: ") + e.what()); return -1; }
+// ... and of the bounded unit (gfh_k_fit_batch_bounded behind the same point functions and passes)
+int64_t gfh_batch_source_bounded(gfh_ctx* c, int na, const int32_t* active, char* buf, int64_t cap) try {
+  return batch_source(c, "gfh_batch_source_bounded", na, active, true, buf, cap);
+} catch (const std::exception& e) { fail(c, std::string("gfh_batch_source_bounded: ") + e.what()); return -1; }
 
 // Compiles the batch translation unit (or finds it in the cache) without launching, as gfh_model_prepare; needs no GPU.
 int gfh_batch_prepare(gfh_ctx* c, int na, const int32_t* active) try {
   if (check_batchable(c, "gfh_batch_prepare", na, active)) return 1;
-  return batch_kernels(c, std::vector<int32_t>(active, active + na), batch_lanes(c, na), false, nullptr);
+  return batch_kernels(c, std::vector<int32_t>(active, active + na), batch_lanes(c, na), false, false, nullptr);
 } catch (const std::exception& e) { return fail(c, std::string("gfh_batch_prepare: ") + e.what()); }
+// ... and the bounded unit's
+int gfh_batch_prepare_bounded(gfh_ctx* c, int na, const int32_t* active) try {
+  if (check_batchable(c, "gfh_batch_prepare_bounded", na, active)) return 1;
+  return batch_kernels(c, std::vector<int32_t>(active, active + na), batch_lanes(c, na), true, false, nullptr);
+} catch (const std::exception& e) { return fail(c, std::string("gfh_batch_prepare_bounded: ") + e.what()); }
 
 // Lanes per fit of the batch kernels from here on: 64 (the default) a wave per fit, 16 a DPP row per fit and four fits per wave, 256
 // a workgroup per fit (few, long spectra), 0 auto -- gfh_batch_auto_lanes at every call, which chooses between 16 and 64 only.  A setting, not a launch: needs no GPU and no model.

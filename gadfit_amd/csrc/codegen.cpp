@@ -75,7 +75,12 @@ static bool emit_batch_kernels(const Model& m, const std::vector<int32_t>& activ
     s << "#define GFH_BCUBE 1\n#define GFH_BYTYPE " << cfg.batch_y_type << "\n#define GFH_BERR " << cfg.batch_error_type << "\n" << kBatchCube;
   }
   if (cfg.batch_lanes == 256) s << kBatchWgSum;          // batch_wg_sum.hip: LDS and a barrier, in the text of the workgroup form alone
-  s << kBatchFit;                   // batch_fit.hip: gfh_k_fit_batch, gfh_k_batch_pass, written once against GFH_BLANES
+  s << kBatchFit;                   // batch_fit.hip: the passes and the solve of a fit, written once against GFH_BLANES
+  if (cfg.batch_bounded) {          // the bounded unit: gfh_k_fit_batch_bounded alone behind them (batch_fit_bounded.hip)
+    s << kBatchFitBounded;
+    return true;
+  }
+  s << kBatchFitKernels;            // batch_fit_kernels.hip: gfh_k_fit_batch, gfh_k_batch_pass
   s << kBatchCov;                   // batch_cov.hip: gfh_k_batch_cov, behind them in every form
   s << kBatchEval;                  // batch_eval.hip: gfh_k_batch_eval, behind that
   return true;

@@ -35,6 +35,8 @@ struct GenConfig {
                           // units of their own: the ragged ones carry none of the three macros
   int batch_y_type = 0;   // 0 double, 1 float, 2 uint16_t
   int batch_error_type = 0; // gfh_init_weights' numbers: 0 NONE, 1 SQRT_Y, 2 PROPTO_Y, 3 INVERSE_Y, 4 USER (a plain load of w)
+  bool batch_bounded = false; // ... the unit holds gfh_k_fit_batch_bounded (batch_fit_bounded.hip: the loop inside a box) INSTEAD of the four kernels:
+                          // a translation unit of its own once more, so that the text of the four kernels' unit does not change by a byte
   bool eval = false;      // the curves of a plain fit (eval.cpp): behind the point functions stand gfh_k_eval / gfh_k_eval_band and, for models a
                           // grid carries, gfh_k_eval_grid / gfh_k_eval_grid_band (eval.hip) INSTEAD of the kernels of a fit.  A translation
                           // unit of its own once more: the default one does not change by a byte

@@ -43,6 +43,12 @@ const char kBatchCube[] = {
 const char kBatchFit[] = {
 #embed "device/batch_fit.hip"
 , 0};
+const char kBatchFitKernels[] = {
+#embed "device/batch_fit_kernels.hip"
+, 0};
+const char kBatchFitBounded[] = {
+#embed "device/batch_fit_bounded.hip"
+, 0};
 const char kBatchCov[] = {
 #embed "device/batch_cov.hip"
 , 0};

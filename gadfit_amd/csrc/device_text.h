@@ -16,7 +16,9 @@ extern const char kOmega[];            // omega.hip: the tangent block of STEP 3
 extern const char kOmegaJt[];          // omega_jt.hip: gfh_k_omega_jt
 extern const char kBatchWgSum[];       // batch_wg_sum.hip: gfh_b_sum_n, the cross-wave reducer of the 256-lane form of the batch kernels
 extern const char kBatchCube[];        // batch_cube.hip: the data form and the load of the cube forms of the batch kernels (gfh_set_batch_cube)
-extern const char kBatchFit[];         // batch_fit.hip: gfh_k_fit_batch, gfh_k_batch_pass
+extern const char kBatchFit[];         // batch_fit.hip: what the loops of the batch kernels share -- the data form, the three passes of a fit, the damped solve
+extern const char kBatchFitKernels[];  // batch_fit_kernels.hip: gfh_k_fit_batch, gfh_k_batch_pass (behind batch_fit.hip: the two are the one text they were)
+extern const char kBatchFitBounded[];  // batch_fit_bounded.hip: gfh_k_fit_batch_bounded, the loop inside a box -- in the bounded unit alone
 extern const char kBatchCov[];         // batch_cov.hip: gfh_k_batch_cov, each fit's parameter covariance and standard errors
 extern const char kBatchEval[];        // batch_eval.hip: gfh_k_batch_eval, the fitted curves, residuals and error bands of a range of fits
 extern const char kEval[];             // eval.hip: gfh_k_eval and its three neighbours, the curves of a plain fit (units of GenConfig::eval alone)

@@ -104,6 +104,7 @@ bool load_kernels(const std::vector<char>& code, ModelKernels* mk, std::string* 
   if (hipModuleGetFunction(&mk->batch_pass, mk->module, "gfh_k_batch_pass") != hipSuccess) { mk->batch_pass = nullptr; (void)hipGetLastError(); }
   if (hipModuleGetFunction(&mk->batch_cov, mk->module, "gfh_k_batch_cov") != hipSuccess) { mk->batch_cov = nullptr; (void)hipGetLastError(); }
   if (hipModuleGetFunction(&mk->batch_eval, mk->module, "gfh_k_batch_eval") != hipSuccess) { mk->batch_eval = nullptr; (void)hipGetLastError(); }
+  if (hipModuleGetFunction(&mk->fit_batch_bounded, mk->module, "gfh_k_fit_batch_bounded") != hipSuccess) { mk->fit_batch_bounded = nullptr; (void)hipGetLastError(); }
   return true;
 }
 

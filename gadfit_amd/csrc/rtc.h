@@ -14,6 +14,7 @@ struct ModelKernels {
   hipFunction_t sweep = nullptr, sweep_gram = nullptr, chi2 = nullptr, omega = nullptr;
   hipFunction_t omega_jt = nullptr;   // optional: absent for models with integrate() and with a robust loss
   hipFunction_t fit_batch = nullptr, batch_pass = nullptr, batch_cov = nullptr, batch_eval = nullptr;   // optional: translation units generated with GenConfig::batch (batch_calls.cpp)
+  hipFunction_t fit_batch_bounded = nullptr;   // optional: the unit generated with GenConfig::batch_bounded holds this one in place of those four
   hipFunction_t eval = nullptr, eval_band = nullptr, eval_grid = nullptr, eval_grid_band = nullptr;   // translation units generated with GenConfig::eval (eval.cpp): these and nothing else; the grid pair where the model is one a grid carries
   int n_active = 0;       // size of the active set the translation unit was generated for
   int omega_grid = 0;     // workgroups of gfh_k_omega resident at once (filled at its first launch)

@@ -310,8 +310,32 @@ def _batch_errors(who, errors):
     return _BATCH_ERRORS[errors]
 
 
-def _batch_fit(pars, active, scale, **kw):
-    """fit_batch, or fit_batch_errors under errors=: what the batch calls return"""
+def _batch_bounds(who, bounds, errors):
+    """the ``bounds`` argument of the batch calls: None, or (lower, upper), each one number per active parameter in the order of the
+    active set gadf_set left, None or -inf / +inf for no bound on that side; returned as two float64 arrays"""
+    if bounds is None:
+        return None
+    if errors is not None:
+        raise GadfitError('%s: bounds together with errors= is not carried in this version (the covariance of a fit with pinned parameters is '
+                          'that of its free ones only, and the pinned set differs from fit to fit); call batch_covariance afterwards' % who)
+    na = sum(1 for a in _S.active if a)
+    try:
+        lower, upper = bounds
+        lower = np.array([-np.inf if v is None else v for v in lower], dtype=np.float64)
+        upper = np.array([np.inf if v is None else v for v in upper], dtype=np.float64)
+    except (TypeError, ValueError):
+        raise GadfitError('%s: bounds must be (lower, upper), each a sequence of one number (or None) per active parameter' % who)
+    if lower.shape != (na,) or upper.shape != (na,):
+        raise GadfitError('%s: bounds must hold one lower and one upper value per active parameter (%d), got %d and %d'
+                          % (who, na, lower.size, upper.size))
+    return lower, upper
+
+
+def _batch_fit(pars, active, scale, bounds, **kw):
+    """fit_batch, fit_batch_errors under errors= or fit_batch_bounded under bounds=: what the batch calls return"""
+    if bounds is not None:
+        out, res, at, _ = _S.ctx.fit_batch_bounded(pars, active, bounds[0], bounds[1], **kw)
+        return out, res, dict(at_bound=at)
     if scale is None:
         out, res, _ = _S.ctx.fit_batch(pars, active, **kw)
         return out, res
@@ -320,7 +344,7 @@ def _batch_fit(pars, active, scale, **kw):
 
 
 def gadf_fit_batch(xs, ys, ws, pars, lambda_=None, lam_up=None, lam_down=None, accth=None, rel_error=None, chi2_rel=None,
-                   chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, lanes_per_fit=None, errors=None, **kw):
+                   chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, lanes_per_fit=None, errors=None, bounds=None, **kw):
     """Many independent fits of the session's model in one kernel launch (gfh_fit_batch): gadf_fit's loop (gadfit.F90:670-915) per
     spectrum, each with its own data, start parameters, lambda history and exit.  On a session initialised with one dataset slot
     (``gadf_init(f)``); the active set is the one ``gadf_set`` left.  ``xs, ys, ws``: one array per spectrum (``ws``: the weights as
@@ -331,9 +355,13 @@ def gadf_fit_batch(xs, ys, ws, pars, lambda_=None, lam_up=None, lam_down=None, a
     iterations, exit_reason, n_sweeps, n_chi2, n_omega, dof, lambda_, chi2).  ``errors``: None, or 'unscaled' / 'scaled' for a third
     element, a dict of each fit's parameter covariance ``cov`` [n_fits][na][na] at the fitted parameters -- the inverse of J^T J, under
     'scaled' times chi2 / dof --, the standard errors ``sigma`` [n_fits][na] and ``info`` [n_fits] (0, or j + 1: pivot j of that fit's
-    factor failed and its cov and sigma are NaN), computed on the device behind the fit (gfh_fit_batch_errors)."""
+    factor failed and its cov and sigma are NaN), computed on the device behind the fit (gfh_fit_batch_errors).  ``bounds``: None, or
+    (lower, upper) -- one box for all fits, each a sequence of one number per active parameter in the order of the active set, None
+    or -inf / +inf for no bound on that side: the projected loop of gfh_fit_batch_bounded, and a third element ``dict(at_bound=...)``
+    [n_fits] (bit j: the returned active parameter j equals lower[j], bit 8 + j: upper[j]).  ``bounds`` with ``errors`` is refused."""
     _need_init()
     scale = _batch_errors('gadf_fit_batch', errors)
+    bounds = _batch_bounds('gadf_fit_batch', bounds, errors)
     if 'lambda' in kw:
         lambda_ = kw.pop('lambda')
     if _S.n_datasets != 1:
@@ -355,7 +383,7 @@ def gadf_fit_batch(xs, ys, ws, pars, lambda_=None, lam_up=None, lam_down=None, a
     np.cumsum([v.size for v in xs], out=off[1:])
     try:
         _S.ctx.set_batch_data(off, np.concatenate(xs), np.concatenate(ys), np.concatenate(ws))
-        return _batch_fit(pars, active, scale, DTD_min=DTD_min, lanes_per_fit=lanes_per_fit, lambda_=_f32(lambda_), lam_up=_f32(lam_up), lam_down=_f32(lam_down),
+        return _batch_fit(pars, active, scale, bounds, DTD_min=DTD_min, lanes_per_fit=lanes_per_fit, lambda_=_f32(lambda_), lam_up=_f32(lam_up), lam_down=_f32(lam_down),
                           accth=_f32(accth), rel_error=_f32(rel_error), chi2_rel=_f32(chi2_rel), chi2_abs=_f32(chi2_abs),
                           lam_incs=lam_incs, max_iter=max_iter, damp_max=None if damp_max is None else int(damp_max),
                           **{k: v for k, v in kw.items() if v is not None})
@@ -363,10 +391,11 @@ def gadf_fit_batch(xs, ys, ws, pars, lambda_=None, lam_up=None, lam_down=None, a
         raise GadfitError(str(e))
 
 
-def _fit_cube(who, frames, x, Y, pars, sigma, DTD_min, lanes_per_fit, frames_per_put, errors, kw):
+def _fit_cube(who, frames, x, Y, pars, sigma, DTD_min, lanes_per_fit, frames_per_put, errors, bounds, kw):
     """gadf_fit_cube and gadf_fit_frames: one body, the data spectrum-major (Y [n_fits][n_points]) or frame-major (F [n_points][n_fits])"""
     _need_init()
     scale = _batch_errors(who, errors)
+    bounds = _batch_bounds(who, bounds, errors)
     if _S.n_datasets != 1:
         raise GadfitError('%s needs a session with one dataset slot: gadf_init(f)' % who)
     active = [i for i, a in enumerate(_S.active) if a]
@@ -397,7 +426,7 @@ def _fit_cube(who, frames, x, Y, pars, sigma, DTD_min, lanes_per_fit, frames_per
             _S.ctx.set_batch_frames(x, Y, _S.error_type, None if sigma is None else 1.0 / sigma, frames_per_put)
         else:
             _S.ctx.set_batch_cube(x, Y, _S.error_type, None if sigma is None else 1.0 / sigma)
-        return _batch_fit(pars, active, scale, DTD_min=DTD_min, lanes_per_fit=lanes_per_fit, **kw)
+        return _batch_fit(pars, active, scale, bounds, DTD_min=DTD_min, lanes_per_fit=lanes_per_fit, **kw)
     except _lib.GadfitHipError as e:
         raise GadfitError(str(e))
 
@@ -411,25 +440,25 @@ def _cube_fit_args(lambda_, lam_up, lam_down, accth, rel_error, chi2_rel, chi2_a
 
 
 def gadf_fit_cube(x, Y, pars, sigma=None, lambda_=None, lam_up=None, lam_down=None, accth=None, rel_error=None, chi2_rel=None,
-                  chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, lanes_per_fit=None, errors=None, **kw):
+                  chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, lanes_per_fit=None, errors=None, bounds=None, **kw):
     """gadf_fit_batch over a data cube (gfh_set_batch_cube): every spectrum on the one grid ``x`` [n_points], ``Y`` [n_fits][n_points] a
     C-contiguous numpy array of float64, float32 or uint16 that is uploaded as it is.  The weights follow from ``Y`` on the device by
     the session's ``gadf_set_errors`` type (NONE, SQRT_Y, PROPTO_Y, INVERSE_Y: no weight array exists anywhere; gadf_fit_batch ignores
     that type, this call takes it); under USER ``sigma`` [n_fits][n_points] is required and 1 / sigma is passed.  ``pars``, the fit
-    arguments, ``lanes_per_fit``, ``errors`` and what is returned are gadf_fit_batch's."""
-    return _fit_cube('gadf_fit_cube', False, x, Y, pars, sigma, DTD_min, lanes_per_fit, 0, errors,
+    arguments, ``lanes_per_fit``, ``errors``, ``bounds`` and what is returned are gadf_fit_batch's."""
+    return _fit_cube('gadf_fit_cube', False, x, Y, pars, sigma, DTD_min, lanes_per_fit, 0, errors, bounds,
                      _cube_fit_args(lambda_, lam_up, lam_down, accth, rel_error, chi2_rel, chi2_abs, lam_incs, max_iter, damp_max, kw))
 
 
 def gadf_fit_frames(x, F, pars, sigma=None, lambda_=None, lam_up=None, lam_down=None, accth=None, rel_error=None, chi2_rel=None,
                     chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, lanes_per_fit=None, frames_per_put=0, errors=None,
-                    **kw):
+                    bounds=None, **kw):
     """gadf_fit_cube for a stack of frames (gfh_set_batch_frames): ``F`` [n_points][n_fits], one image per abscissa of ``x`` with the
     fit (pixel) index fastest, as instruments deliver it -- C-contiguous in float64, float32 or uint16, uploaded as it is and
     transposed into the cube on the device, so no ``np.ascontiguousarray(F.T)`` runs on the host.  ``sigma`` (under USER) is
     frame-major as ``F``; ``frames_per_put``: frames per upload, 0 the library's rule.  Everything else, and what is returned (the
     bits included), is gadf_fit_cube's on the transposed arrays."""
-    return _fit_cube('gadf_fit_frames', True, x, F, pars, sigma, DTD_min, lanes_per_fit, frames_per_put, errors,
+    return _fit_cube('gadf_fit_frames', True, x, F, pars, sigma, DTD_min, lanes_per_fit, frames_per_put, errors, bounds,
                      _cube_fit_args(lambda_, lam_up, lam_down, accth, rel_error, chi2_rel, chi2_abs, lam_incs, max_iter, damp_max, kw))
 
 

@@ -500,6 +500,21 @@ int  gfh_batch_covariance(gfh_ctx* ctx, const double* pars, int n_act, const int
                           double* sigma, int32_t* info);
 int  gfh_fit_batch_errors(gfh_ctx* ctx, double* pars, int n_act, const int32_t* active_pars, const gfh_fit_options* opt,
                           gfh_batch_result* results, int scale, double* cov, double* sigma, int32_t* info, double* seconds);
+/* Bounds of a batch: gfh_fit_batch inside ONE box per batch, lower[n_act] <= p <= upper[n_act] in the order of active_pars, the same
+ * for every fit; -inf / +inf: no bound on that side.  A projected Levenberg-Marquardt loop with an active set (the kernel
+ * gfh_k_fit_batch_bounded, in a translation unit of its own): after STEP 1+2 an active parameter that sits on a wall (P_j == lower_j
+ * or upper_j, exactly) while descent pushes through it (J^T r_j < 0 at the lower, > 0 at the upper wall) is pinned for that
+ * iteration -- its row and column leave every damped solve, so its step is exactly 0 --, every trial point is clamped into the box
+ * coordinate by coordinate, and a coordinate that sits on a bound does not hold the rel_error exit open.  Everything else is
+ * gfh_fit_batch's loop: with no finite bound pars and results are that call's bits.  results as gfh_fit_batch; at_bound [n_fits]:
+ * bit j set where the returned active parameter j == lower[j], bit 8 + j where it == upper[j].
+ * Refused, each with its own message before the device is asked for, in this order: what gfh_fit_batch refuses of the context, the
+ * model and the active set; NULL arguments; a box with a NaN bound, lower_j = +inf, upper_j = -inf or lower_j >= upper_j (make that
+ * parameter passive instead); the options gfh_fit_batch refuses; no batch held or a spectrum too short; a start outside the box.
+ * Not built: a box per fit, bounds on the plain gfh_fit, linear constraints, a covariance that knows the pinned set
+ * (gfh_batch_covariance at the returned parameters is that of all active parameters), a Fortran entry. */
+int  gfh_fit_batch_bounded(gfh_ctx* ctx, double* pars, int n_act, const int32_t* active_pars, const double* lower, const double* upper,
+                           const gfh_fit_options* opt, gfh_batch_result* results, int32_t* at_bound, double* seconds);
 /* Curves of a batch: the fitted model, the weighted residuals and the 1-sigma band of the curve, computed on the device by a fourth
  * kernel of the batch translation units (gfh_k_batch_eval) from the data held and the model's own point functions, for fits
  * [first_fit, first_fit + n_fits_eval) of the batch held.  pars [n_fits_eval][n_pars] and cov [n_fits_eval][n_act*n_act] (as
@@ -526,6 +541,9 @@ int  gfh_batch_eval(gfh_ctx* ctx, const double* pars, int n_act, const int32_t* 
  * model's point functions) as gfh_model_source, and its compilation without a launch as gfh_model_prepare (needs no GPU). */
 int64_t gfh_batch_source(gfh_ctx* ctx, int n_act, const int32_t* active_pars, char* buf, int64_t cap);
 int  gfh_batch_prepare(gfh_ctx* ctx, int n_act, const int32_t* active_pars);
+/* ... and of the bounded unit (gfh_k_fit_batch_bounded behind the same point functions): the four kernels' unit does not hold it. */
+int64_t gfh_batch_source_bounded(gfh_ctx* ctx, int n_act, const int32_t* active_pars, char* buf, int64_t cap);
+int  gfh_batch_prepare_bounded(gfh_ctx* ctx, int n_act, const int32_t* active_pars);
 /* Lanes per fit of the batch kernels, a setting of the context read by every later gfh_fit_batch, gfh_batch_pass, gfh_batch_source
  * and gfh_batch_prepare.  64 (the default): a wave per fit.  16: a DPP row of 16 lanes per fit, four fits per wave and sixteen per
  * workgroup -- for short spectra, where a wave per fit keeps most lanes on padding; the sums are reduced inside the row, fits of one

@@ -10,6 +10,7 @@ profiles/r05_small_fits.txt: 1000 points, a Gaussian on a background, 4 paramete
     python tools/bench_batch.py --cube [--cells gauss4:64:16384:1000,...] [--registers] [--out profiles/batch_cube.json]
     python tools/bench_batch.py --frames [--cells uint16:1:64:131072:1000,...] [--out profiles/batch_frames.json]
     python tools/bench_batch.py --cov [--sizes 16384,131072] [--points 1000] [--lanes 64] [--out profiles/batch_cov.json]
+    python tools/bench_batch.py --bounds [--sizes 16384] [--points 1000] [--lanes 64] [--out profiles/batch_bounds.json]
     python tools/bench_batch.py --eval [--cells gauss4:64:16384:1000,...] [--registers] [--observed FILE] [--out profiles/batch_eval.json]
 
 Per batch size: warm-up launches, then the median of the timed launches -- device time from the HIP events around the kernel
@@ -60,6 +61,12 @@ parameters, numpy.linalg.inv over the batch on the host.  Wall time around each 
 fit_batch and for fit_batch_errors (HIP events around the one launch and around the two): their difference is what gfh_k_batch_cov
 adds on the device.  The library takes no events around gfh_k_batch_pass, so that kernel's own device time is not in the record.  No
 ratio is asserted; the medians and the min-max are written down.
+--bounds: the bounded loop (gfh_fit_batch_bounded: the kernel gfh_k_fit_batch_bounded, in a unit of its own) against gfh_fit_batch on
+this tool's problem with 4 active parameters and on the four exponentials with 8, 16384 fits of 1000 points at 64 lanes: fit_batch,
+fit_batch_bounded with every bound infinite (the same bits, checked) and fit_batch_bounded with a binding box, alternating call by call
+in one run on one card; device and wall time, median and min-max.  The ratio of the first two is written down with whether it lies
+beyond the two routes' own spread; nothing is asserted on it.
+
 --eval: the curves of a batch (gfh_batch_eval: the kernel gfh_k_batch_eval) at the cells of the cube table, on the ragged form and on
 the uint16 cube under SQRT_Y of the same counts, at the start parameters with the device's own covariance.  Per cell and form three
 calls alternate on one context: batch_pass (the first yardstick: code of the parent commit with the same loads and the same
@@ -192,7 +199,7 @@ def kernel_registers(src):
         if not m:
             continue
         if m.group(1) == 'Function Name':
-            name = m.group(2) if m.group(2) in ('gfh_k_fit_batch', 'gfh_k_batch_pass', 'gfh_k_batch_cov', 'gfh_k_batch_eval') else None
+            name = m.group(2) if m.group(2) in ('gfh_k_fit_batch', 'gfh_k_batch_pass', 'gfh_k_batch_cov', 'gfh_k_batch_eval', 'gfh_k_fit_batch_bounded') else None
             if name:
                 out[name] = {}
         elif name and m.group(1) in keys:
@@ -379,6 +386,75 @@ def cov_main(a):
             print('%-6s %7d fits: wall fit %.2f ms, errors %.2f ms, host route %.2f ms; device fit %.3f ms, fit + cov %.3f ms; sigma differs from the host route by %.1e'
                   % (name, nf, entry['wall_ms_fit']['median'], entry['wall_ms_errors']['median'], entry['wall_ms_host']['median'],
                      entry['device_ms_fit']['median'], entry['device_ms_errors']['median'], entry['worst_relative_sigma_difference_to_the_host_route']), flush=True)
+            with open(a.out, 'w') as fh:
+                json.dump(rec, fh, indent=1, sort_keys=True)
+                fh.write('\n')
+    print('wrote', a.out)
+
+
+# --bounds: one binding box per model -- the amplitude of the gaussian held below its truth of 3.0, the slowest decay time of the four
+# exponentials below its truth of 30; the other sides keep the fits physical without touching them
+BOUNDS_BOXES = {
+    'gauss4': ([0.0, 0.0, 0.1, 0.0], [2.8, 10.0, np.inf, np.inf]),
+    'exp4': ([0.0] * 8, [np.inf] * 7 + [29.0]),
+}
+
+
+def bounds_main(a):
+    """fit_batch against fit_batch_bounded under infinite bounds and under a binding box (see the module's text)"""
+    n_points, lanes = int(a.points or 1000), int(a.lanes or 64)
+    rec = dict(method='per model three routes alternating call by call on one context of one card in one run: fit = fit_batch (the kernel '
+                      'gfh_k_fit_batch, which is the parent commit\'s), bounded_inf = fit_batch_bounded with every bound infinite (gfh_k_fit_batch_bounded; '
+                      'the same bits, checked), bounded_box = fit_batch_bounded with the binding box written down per entry; device time (HIP events '
+                      'around the kernel) and wall time around the call, the median and the min-max of %d calls after %d warm-up calls; %d points per '
+                      'spectrum, %d lanes per fit, lambda0 = %g, max_iter = %d; device_bounded_inf_over_fit = the medians\' ratio, beyond_spread = it '
+                      'differs from 1 by more than the two routes\' min-max spreads together; no counter pass was made'
+                      % (a.launches, a.warmup, n_points, lanes, LAMBDA0, MAX_ITER), measurements=[])
+    kw = dict(lambda_=LAMBDA0, max_iter=MAX_ITER)
+    for name in ('gauss4', 'exp4'):
+        m = ROW_MODELS[name]
+        na = len(m['active'])
+        lo, hi = BOUNDS_BOXES[name]
+        for nf in [int(s) for s in a.sizes.split(',')]:
+            xs, ys, ws = spectra_flat(name, nf, n_points)
+            ctx = _lib.Context(0)
+            ctx.set_model(trace_model(m['model'], m['n_pars']))
+            ctx.set_batch_lanes(lanes)
+            ctx.set_batch_data(np.arange(nf + 1, dtype=np.int64) * n_points, xs, ys, ws)
+            del xs, ys, ws
+            start = np.tile(m['start'], (nf, 1))
+            wall = dict(fit=[], bounded_inf=[], bounded_box=[]); dev = dict(fit=[], bounded_inf=[], bounded_box=[])
+            for it in range(a.warmup + a.launches):
+                t0 = time.perf_counter()
+                p, r, sec = ctx.fit_batch(start, m['active'], **kw)
+                t1 = time.perf_counter()
+                pi, ri, ati, sec_i = ctx.fit_batch_bounded(start, m['active'], [-np.inf] * na, [np.inf] * na, **kw)
+                t2 = time.perf_counter()
+                pb, rb, atb, sec_b = ctx.fit_batch_bounded(start, m['active'], lo, hi, **kw)
+                t3 = time.perf_counter()
+                if it >= a.warmup:
+                    wall['fit'].append(t1 - t0); wall['bounded_inf'].append(t2 - t1); wall['bounded_box'].append(t3 - t2)
+                    dev['fit'].append(sec); dev['bounded_inf'].append(sec_i); dev['bounded_box'].append(sec_b)
+            ctx.close()
+            if not (np.array_equal(p, pi) and np.array_equal(r['chi2'], ri['chi2']) and np.array_equal(r['iterations'], ri['iterations']) and np.all(ati == 0)):
+                sys.exit('infinite bounds changed a fit')
+            A = np.array(m['active'])
+            if not (np.all(pb[:, A] >= lo) and np.all(pb[:, A] <= hi)):
+                sys.exit('a fit left the box')
+            entry = dict(model=name, what=m['what'], n_active=na, fits=nf, points=n_points, lanes=lanes,
+                         box=dict(lower=[float(v) if np.isfinite(v) else str(v) for v in lo], upper=[float(v) if np.isfinite(v) else str(v) for v in hi]),
+                         fits_on_a_bound_under_the_box=int(np.sum(atb != 0)),
+                         passes={k: dict(sweeps=int(q['n_sweeps'].sum()), chi2=int(q['n_chi2'].sum()), omega=int(q['n_omega'].sum()))
+                                 for k, q in (('fit', r), ('bounded_inf', ri), ('bounded_box', rb))})
+            for k in wall:
+                entry['wall_ms_' + k] = _spread(wall[k]); entry['device_ms_' + k] = _spread(dev[k])
+            f, b = entry['device_ms_fit'], entry['device_ms_bounded_inf']
+            entry['device_bounded_inf_over_fit'] = b['median'] / f['median']
+            entry['beyond_spread'] = bool(abs(b['median'] - f['median']) > (f['max'] - f['min']) + (b['max'] - b['min']))
+            rec['measurements'].append(entry)
+            print('%-6s %7d fits: device fit %.3f ms [%.3f, %.3f], bounded (no bound) %.3f ms [%.3f, %.3f], ratio %.4f%s; bounded (box) %.3f ms, %d fits on a bound'
+                  % (name, nf, f['median'], f['min'], f['max'], b['median'], b['min'], b['max'], entry['device_bounded_inf_over_fit'],
+                     ' (beyond the spread)' if entry['beyond_spread'] else '', entry['device_ms_bounded_box']['median'], entry['fits_on_a_bound_under_the_box']), flush=True)
             with open(a.out, 'w') as fh:
                 json.dump(rec, fh, indent=1, sort_keys=True)
                 fh.write('\n')
@@ -768,6 +844,7 @@ def main():
     ap.add_argument('--cube', action='store_true', help='a batch as a data cube against the ragged form of the same spectra, into profiles/batch_cube.json')
     ap.add_argument('--frames', action='store_true', help='a stack of frames against the host transpose and the upload alone, into profiles/batch_frames.json')
     ap.add_argument('--cov', action='store_true', help='fit_batch_errors against fit_batch alone and against the host route, into profiles/batch_cov.json')
+    ap.add_argument('--bounds', action='store_true', help='fit_batch_bounded under infinite bounds and under a binding box against fit_batch, into profiles/batch_bounds.json')
     ap.add_argument('--eval', action='store_true', help='batch_eval against batch_pass and against the bytes it moves, into profiles/batch_eval.json')
     ap.add_argument('--cells', default=None, help='with --cube and --eval: model:lanes:fits:points, ...; with --frames: sample type:error type:lanes:fits:points, ...')
     ap.add_argument('--models', default='gauss4,exp4', help='with --workgroup: the models measured by this call (the record keeps the others)')
@@ -783,7 +860,7 @@ def main():
                                                                  'nothing is timed, no GPU is needed')
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'batch_eval.json' if a.eval else 'batch_cov.json' if a.cov else 'batch_frames.json' if a.frames else 'batch_cube.json' if a.cube else 'batch_workgroup.json' if a.workgroup else 'batch_rows.json' if a.rows else 'batch_fits.json')
+        a.out = os.path.join(ROOT, 'profiles', 'batch_bounds.json' if a.bounds else 'batch_eval.json' if a.eval else 'batch_cov.json' if a.cov else 'batch_frames.json' if a.frames else 'batch_cube.json' if a.cube else 'batch_workgroup.json' if a.workgroup else 'batch_rows.json' if a.rows else 'batch_fits.json')
     if a.cells is None:
         a.cells = FRAMES_CELLS if a.frames else EVAL_CELLS if a.eval else CUBE_CELLS
     if a.eval and (a.registers or a.observed):
@@ -824,6 +901,10 @@ def main():
         sys.exit('at least 5 timed launches')
     if a.eval:
         return eval_main(a)
+    if a.bounds:
+        if a.sizes == '1024,16384,131072':
+            a.sizes = '16384'
+        return bounds_main(a)
     if a.cov:
         if a.sizes == '1024,16384,131072':
             a.sizes = '16384,131072'
