@@ -151,6 +151,30 @@ class BatchCalls:
         """64, 16 or 256: the form of the last batch launch (0: none yet) -- gfh_debug_batch_lanes"""
         return int(lib().gfh_debug_batch_lanes(self._h))
 
+    # --- the loss of a batch (gfh_set_batch_loss) and what the last launch ran under
+    def set_batch_loss(self, loss, scale=1.0):
+        """the loss of the batch calls from here on (it stays set): 0 linear (the default), 1 Cauchy, 2 Huber, switching at |r| = scale in
+        units of the weighted residual r = (y - f) w (scale 1: the reference's costs).  The acceptance test, the records and
+        batch_pass keep the plain chi2; a context's set_loss stays refused in a batch -- gfh_set_batch_loss"""
+        self._chk(lib().gfh_set_batch_loss(self._h, int(loss), float(scale)))
+
+    def batch_loss(self):
+        """(loss, scale) as set_batch_loss left them; (0, 1.0) until it is called -- gfh_get_batch_loss"""
+        scale = C.c_double()
+        return int(lib().gfh_get_batch_loss(self._h, C.cast(C.byref(scale), _dp))), scale.value
+
+    def batch_loss_used(self):
+        """(loss, scale) of the last batch launch that sweeps, None: none yet -- gfh_debug_batch_loss"""
+        scale = C.c_double()
+        loss = int(lib().gfh_debug_batch_loss(self._h, C.cast(C.byref(scale), _dp)))
+        return None if loss < 0 else (loss, scale.value)
+
+    def _loss(self, loss, loss_scale):
+        """loss and loss_scale of a call: as set_batch_loss (they stay set); None leaves that part of the context's setting"""
+        if loss is not None or loss_scale is not None:
+            held = self.batch_loss()          # (the library's own record: the one source of the setting)
+            self.set_batch_loss(held[0] if loss is None else loss, held[1] if loss_scale is None else loss_scale)
+
     def batch_form_used(self):
         """the data form of the last batch launch: None (none yet), 'ragged', or ('cube', y_type, error_type) -- gfh_debug_batch_form"""
         f = int(lib().gfh_debug_batch_form(self._h))
@@ -178,13 +202,14 @@ class BatchCalls:
         if lanes_per_fit is not None:
             self.set_batch_lanes(lanes_per_fit)
 
-    def _batch_args(self, who, pars, active, lanes_per_fit):
+    def _batch_args(self, who, pars, active, lanes_per_fit, loss=None, loss_scale=None):
         """a copy of pars as [n_fits][n_pars], the active set and n_fits of a call on every fit of the batch held"""
         n = self._n_held(who)
         p = np.ascontiguousarray(pars, dtype=np.float64).copy()
         _sized(who, 'pars', p, '', ('n_fits', 'n_pars'), (n, self.n_pars))
         a = self._active(who, active)
         self._lanes(lanes_per_fit)
+        self._loss(loss, loss_scale)
         return p.reshape(n, self.n_pars), a, n
 
     def _batch_options(self, who, a, DTD_min, kw):
@@ -207,15 +232,16 @@ class BatchCalls:
             o.DTD_min = dp(dm)
         return o, dm
 
-    def fit_batch(self, pars, active, DTD_min=None, lanes_per_fit=None, **kw):
+    def fit_batch(self, pars, active, DTD_min=None, lanes_per_fit=None, loss=None, loss_scale=None, **kw):
         """every spectrum of the batch fitted in one launch.  pars [n_fits][n_pars]; keyword arguments as fit(); lanes_per_fit: as
-        set_batch_lanes (it stays set), None leaves the context's setting.  Returns the fitted parameters, a numpy record array of
+        set_batch_lanes (it stays set), None leaves the context's setting; loss, loss_scale: as set_batch_loss (they stay set), None
+        leaves the setting.  Returns the fitted parameters, a numpy record array of
         BatchResult [n_fits] and the device time of the launch in seconds."""
-        return self._fit('fit_batch', pars, active, None, DTD_min, lanes_per_fit, kw)
+        return self._fit('fit_batch', pars, active, None, DTD_min, lanes_per_fit, kw, loss, loss_scale)
 
-    def _fit(self, who, pars, active, scale, DTD_min, lanes_per_fit, kw):
+    def _fit(self, who, pars, active, scale, DTD_min, lanes_per_fit, kw, loss=None, loss_scale=None):
         """fit_batch or fit_batch_errors (who): the same arguments, the second with scale and the error outputs behind them"""
-        p, a, n = self._batch_args(who, pars, active, lanes_per_fit)
+        p, a, n = self._batch_args(who, pars, active, lanes_per_fit, loss, loss_scale)
         o, _keep = self._batch_options(who, a, DTD_min, kw)
         res = np.zeros(n, dtype=BATCH_RESULT_DTYPE)
         sec = C.c_double()
@@ -227,13 +253,14 @@ class BatchCalls:
         self._chk(lib().gfh_fit_batch_errors(*args, int(scale), dp(cov), dp(sigma), ip(info), C.cast(C.byref(sec), _dp)))
         return p, res.view(np.recarray), (cov, sigma, info), sec.value
 
-    def fit_batch_bounded(self, pars, active, lower, upper, DTD_min=None, lanes_per_fit=None, **kw):
+    def fit_batch_bounded(self, pars, active, lower, upper, DTD_min=None, lanes_per_fit=None, loss=None, loss_scale=None, **kw):
         """fit_batch inside one box per batch: lower and upper hold one value per active parameter, in the order of `active`, -inf /
         +inf for no bound on that side.  Returns the fitted parameters, the records, at_bound [n_fits] (int32: bit j where the
         returned active parameter j equals lower[j], bit 8 + j where it equals upper[j]) and the device time of the launch in seconds.
-        With no finite bound the parameters and records are fit_batch's bits -- gfh_fit_batch_bounded"""
+        With no finite bound the parameters and records are fit_batch's bits; loss, loss_scale as fit_batch (under a loss a parameter
+        is pinned on the sign of the loss-scaled J^T r) -- gfh_fit_batch_bounded"""
         who = 'fit_batch_bounded'
-        p, a, n = self._batch_args(who, pars, active, lanes_per_fit)
+        p, a, n = self._batch_args(who, pars, active, lanes_per_fit, loss, loss_scale)
         lo = np.ascontiguousarray(lower, dtype=np.float64); hi = np.ascontiguousarray(upper, dtype=np.float64)
         for name, v in (('lower', lo), ('upper', hi)):
             if v.ndim != 1 or v.size != a.size:
@@ -246,26 +273,28 @@ class BatchCalls:
                                               ip(at), C.cast(C.byref(sec), _dp)))
         return p, res.view(np.recarray), at, sec.value
 
-    def fit_batch_errors(self, pars, active, scale=False, DTD_min=None, lanes_per_fit=None, **kw):
+    def fit_batch_errors(self, pars, active, scale=False, DTD_min=None, lanes_per_fit=None, loss=None, loss_scale=None, **kw):
         """fit_batch and, behind it on the device, each fit's parameter covariance at the fitted parameters: returns the fitted
         parameters, the records, (cov [n_fits][na][na], sigma [n_fits][na], info [n_fits]) as batch_covariance returns them and the
-        device time of the two launches in seconds.  The parameters and records are fit_batch's bits -- gfh_fit_batch_errors"""
-        return self._fit('fit_batch_errors', pars, active, scale, DTD_min, lanes_per_fit, kw)
+        device time of the two launches in seconds.  The parameters and records are fit_batch's bits; loss, loss_scale as fit_batch
+        -- gfh_fit_batch_errors"""
+        return self._fit('fit_batch_errors', pars, active, scale, DTD_min, lanes_per_fit, kw, loss, loss_scale)
 
-    def batch_covariance(self, pars, active, scale=False, lanes_per_fit=None):
+    def batch_covariance(self, pars, active, scale=False, lanes_per_fit=None, loss=None, loss_scale=None):
         """(cov [n_fits][na][na], sigma [n_fits][na], info [n_fits]) of every spectrum at pars [n_fits][n_pars]: cov = (J^T J)^-1
         (the reference's LMsolver::getInvJTJ), under scale=True times the fit's chi2 / dof; sigma = sqrt of its diagonal; info 0, or
         j + 1 where pivot j of the Cholesky factor failed (that fit's cov and sigma are NaN).  Rows and columns in the order of
-        `active`; lanes_per_fit as fit_batch -- gfh_batch_covariance"""
-        p, a, n = self._batch_args('batch_covariance', pars, active, lanes_per_fit)
+        `active`; lanes_per_fit, loss and loss_scale as fit_batch: under a loss J is the loss-scaled Jacobian and the chi2 of
+        scale=True stays the plain one -- gfh_batch_covariance"""
+        p, a, n = self._batch_args('batch_covariance', pars, active, lanes_per_fit, loss, loss_scale)
         cov, sigma, info = _error_outputs(n, a.size)
         self._chk(lib().gfh_batch_covariance(self._h, dp(p), a.size, ip(a), int(scale), dp(cov), dp(sigma), ip(info)))
         return cov, sigma, info
 
-    def batch_pass(self, pars, active, lanes_per_fit=None):
+    def batch_pass(self, pars, active, lanes_per_fit=None, loss=None, loss_scale=None):
         """(JTJ [n_fits][na][na], JTres [n_fits][na], chi2 [n_fits]) of every spectrum at pars [n_fits][n_pars] -- gfh_batch_pass;
-        lanes_per_fit as fit_batch"""
-        p, a, n = self._batch_args('batch_pass', pars, active, lanes_per_fit)
+        lanes_per_fit, loss and loss_scale as fit_batch (under a loss JTJ and JTres are the loss-scaled sums, chi2 the plain one)"""
+        p, a, n = self._batch_args('batch_pass', pars, active, lanes_per_fit, loss, loss_scale)
         JTJ = np.zeros((n, a.size, a.size)); JTr = np.zeros((n, a.size)); chi2 = np.zeros(n)
         self._chk(lib().gfh_batch_pass(self._h, dp(p), a.size, ip(a), dp(JTJ), dp(JTr), dp(chi2)))
         return JTJ, JTr, chi2

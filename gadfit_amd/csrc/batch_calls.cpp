@@ -51,7 +51,7 @@ int check_batchable(gfh_ctx* c, const char* who, int na, const int32_t* active) 
   if (c->model.branching()) return fail(c, w + ": models recorded as variant tapes (a branching eval()) are not carried by the batch kernels");
   if (c->model.n_aux > 0) return fail(c, w + ": models with auxiliary per-point columns are not carried by the batch kernels");
   if (c->pars_fn) return fail(c, w + ": a pars hook (gfh_set_pars_hook) cannot run inside a device-resident loop");
-  if (c->gen.loss != 0) return fail(c, w + ": a robust loss (gfh_set_loss) is not carried by the batch kernels");
+  if (c->gen.loss != 0) return fail(c, w + ": a robust loss (gfh_set_loss) is not carried by the batch kernels: a batch takes its loss and residual scale from gfh_set_batch_loss");
   if (c->gen.finite_diff) return fail(c, w + ": use_ad = 0 (finite differences) is not carried by the batch kernels");
   if (na < 1) return fail(c, "There are no active parameters.");                                       // gadfit.F90:602-603
   if (na > kValuGramMax) return fail(c, w + ": more than " + std::to_string(kValuGramMax) + " active parameters per fit");
@@ -84,6 +84,7 @@ GenConfig batch_config(const gfh_ctx* c, int lanes, bool bounded) {
   cfg.batch = true;
   cfg.batch_lanes = lanes;
   cfg.batch_bounded = bounded;      // gfh_k_fit_batch_bounded in place of the four kernels: a unit of its own
+  cfg.batch_loss = c->batch.loss;   // gfh_set_batch_loss: the batch's own setting (cfg.loss, the plain units' GFH_LOSS, stays 0); the scale is a kernel argument
   cfg.batch_cube = c->batch.cube;   // the data form held: a cube's sample type and weight rule are part of the text (batch_cube.hip)
   if (c->batch.cube) { cfg.batch_y_type = c->batch.y_type; cfg.batch_error_type = c->batch.error_type; }
   return cfg;
@@ -98,6 +99,7 @@ int batch_kernels(gfh_ctx* c, const std::vector<int32_t>& active, int lanes, boo
   key.push_back(bounded ? -(1 << 30) - 2 : -(1 << 30));      // (no plain active set holds a negative entry; an eval unit holds -(1 << 30) - 1 here)
   key.push_back(lanes);             // both forms of one active set can be resident
   if (c->batch.cube) key.push_back(data_form(c));      // ... and so can its cube forms beside the ragged one (whose key stays what it was)
+  if (c->batch.loss) key.push_back(-(1 << 29) - c->batch.loss);      // ... and its loss units beside the linear one (no lane count and no data form is negative)
   auto it = c->kernel_cache.find(key);
   if (it != c->kernel_cache.end()) { if (out) *out = &it->second; return 0; }
   std::string src, err;
@@ -128,15 +130,20 @@ int open_device(gfh_ctx* c, const char* who, int na, const int32_t* active, Open
 }
 // One launch of a batch kernel over n fits of the batch held, on the context's stream: workgroups of 256 threads, 256 / lanes fits
 // each.  Every kernel's arguments are the data's four (GFH_BARGS: x, y, w and the offsets -- of a cube, n_points in their place),
-// the call's own (`middle`: pointers to them, the kernel's fit count among them) and the status block.
-int launch_batch(gfh_ctx* c, hipFunction_t kernel, int lanes, int64_t n, std::initializer_list<void*> middle) {
+// the call's own (`middle`: pointers to them, the kernel's fit count among them), under a loss (gfh_set_batch_loss) inv_c = 1 / scale
+// for the kernels that sweep (`sweeps`: all but gfh_k_batch_eval, which the loss does not reach), and the status block.
+int launch_batch(gfh_ctx* c, hipFunction_t kernel, int lanes, int64_t n, std::initializer_list<void*> middle, bool sweeps = true) {
   void* x = c->batch.x.p; void* y = c->batch.y.p; void* w = c->batch.w.p; void* off = c->batch.off_d.p;
   long long npts = c->batch.max_points; void* stp = c->status.p;
+  double inv_c = 1.0 / c->batch.loss_scale;
   std::vector<void*> args = {&x, &y, &w, c->batch.cube ? (void*)&npts : (void*)&off};
-  args.insert(args.end(), middle); args.push_back(&stp);
+  args.insert(args.end(), middle);
+  if (sweeps && c->batch.loss != 0) args.push_back(&inv_c);
+  args.push_back(&stp);
   const int per_wg = 256 / lanes;
   HIPCHK(c, hipModuleLaunchKernel(kernel, (unsigned)((n + per_wg - 1) / per_wg), 1, 1, 256, 1, 1, 0, c->stream, args.data(), nullptr));
   c->batch.last_lanes = lanes; c->batch.last_form = data_form(c);
+  if (sweeps) { c->batch.last_loss = c->batch.loss; c->batch.last_loss_scale = c->batch.loss_scale; }
   return 0;
 }
 
@@ -419,7 +426,7 @@ int gfh_batch_eval(gfh_ctx* c, const double* pars, int na, const int32_t* active
   for (int j = 0; j < 3; j++) if (outs[j]) { d[j] = out + at; at += ob; }
   long long ne = n_eval, first = first_fit, n = n_fits_eval;
   HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-  if (launch_batch(c, k.mk->batch_eval, k.lanes, n_fits_eval, {&dp, &dc, &dx, &ne, &first, &n, &d[0], &d[1], &d[2]})) return 1;
+  if (launch_batch(c, k.mk->batch_eval, k.lanes, n_fits_eval, {&dp, &dc, &dx, &ne, &first, &n, &d[0], &d[1], &d[2]}, false)) return 1;
   HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
   HIPCHK(c, hipMemcpyAsync(h, out, at, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -458,6 +465,33 @@ int gfh_set_batch_lanes(gfh_ctx* c, int lanes) try {
   c->batch.lanes = lanes;
   return 0;
 } catch (const std::exception& e) { return fail(c, std::string("gfh_set_batch_lanes: ") + e.what()); }
+
+// The loss of the batch kernels from here on (it stays set, as gfh_set_batch_lanes): 0 linear (the default), 1 Cauchy, 2 Huber -- the
+// reference's costs (lm_solver.cpp:255-284), switching at |r| = scale in units of the weighted residual r = (y - f) w; scale 1 is the
+// reference's own.  The loss is part of the batch unit's text, 1 / scale a kernel argument.  A setting, not a launch: needs no GPU and no model.
+int gfh_set_batch_loss(gfh_ctx* c, int loss, double scale) try {
+  if (check_context(c, "gfh_set_batch_loss")) return 1;
+  if (loss < GFH_LOSS_LINEAR || loss > GFH_LOSS_HUBER)
+    return fail(c, "gfh_set_batch_loss: unknown loss " + std::to_string(loss) + " (0: linear, 1: cauchy, 2: huber)");
+  if (std::isnan(scale)) return fail(c, "gfh_set_batch_loss: the residual scale is NaN");
+  if (std::isinf(scale)) return fail(c, "gfh_set_batch_loss: the residual scale is infinite (a loss that never switches is the linear one: loss 0)");
+  if (!(scale > 0.0) || std::isinf(1.0 / scale))          // (the kernels take 1 / scale: a subnormal scale has no finite one)
+    return fail(c, "gfh_set_batch_loss: the residual scale must be positive, with a finite reciprocal, got " + std::to_string(scale));
+  c->batch.loss = loss; c->batch.loss_scale = scale;
+  return 0;
+} catch (const std::exception& e) { return fail(c, std::string("gfh_set_batch_loss: ") + e.what()); }
+// The setting itself: the loss (return value; -1: no context) and *scale (may be NULL) that gfh_set_batch_loss left
+int gfh_get_batch_loss(gfh_ctx* c, double* scale) {
+  if (!c) return -1;
+  if (scale) *scale = c->batch.loss_scale;
+  return c->batch.loss;
+}
+// The loss and scale that the last sweeping batch launch of this context ran under (return -1: none yet; scale may be NULL)
+int gfh_debug_batch_loss(gfh_ctx* c, double* scale) {
+  if (!c) return -1;
+  if (scale) *scale = c->batch.last_loss_scale;
+  return c->batch.last_loss;
+}
 
 // The form of the last batch launch of this context (64, 16 or 256; 0: none yet), so that a test asserts the dispatch.
 int gfh_debug_batch_lanes(gfh_ctx* c) { return c ? c->batch.last_lanes : 0; }

@@ -14,6 +14,7 @@
 #include "codegen_internal.h"
 #include "device_text.h"
 #include <algorithm>
+#include <cstring>
 
 namespace gfh {
 
@@ -61,6 +62,25 @@ static std::string coop_defines(int NA) {
 
 // GenConfig::batch: the four kernels of batched independent fits, behind the point functions of the translation unit (batch.cpp is
 // their host side and refuses what they do not carry before it comes here; the checks below keep the generator honest on its own).
+// A file of the batch text with its `#if GFH_BLOSS` / `#else  // GFH_BLOSS` / `#endif  // GFH_BLOSS` lines resolved HERE, not by the
+// preprocessor: the three directives (whole lines, exactly these) and the arm not taken are left out, so a linear unit is the text it
+// was before a batch had a loss and a loss unit reads as straight as that one.  The regions do not nest; any other directive passes through.
+static std::string resolve_batch_loss(const char* text, bool loss) {
+  std::string out; out.reserve(strlen(text));
+  int arm = 0;                      // 0 outside a region, 1 in its loss arm, 2 in its linear arm
+  for (const char* p = text; *p;) {
+    const char* e = strchr(p, '\n');
+    const size_t n = e ? (size_t)(e - p) + 1 : strlen(p);
+    const std::string line(p, n);
+    p += n;
+    if (line == "#if GFH_BLOSS\n") { arm = 1; continue; }
+    if (arm && line == "#else  // GFH_BLOSS\n") { arm = 2; continue; }
+    if (arm && line == "#endif  // GFH_BLOSS\n") { arm = 0; continue; }
+    if (arm == 0 || (arm == 1) == loss) out += line;
+  }
+  return out;
+}
+
 static bool emit_batch_kernels(const Model& m, const std::vector<int32_t>& active, const GenConfig& cfg, std::ostringstream& s, std::string* err) {
   const int NA = (int)active.size();
   if (NA < 1 || NA > kValuGramMax) { *err = "batch kernels: 1 to " + std::to_string(kValuGramMax) + " active parameters"; return false; }
@@ -70,18 +90,21 @@ static bool emit_batch_kernels(const Model& m, const std::vector<int32_t>& activ
   s << "\n#define GFH_BATCH 1\n#define GFH_BACT {";
   for (int j = 0; j < NA; j++) s << (j ? ", " : "") << active[j];
   s << "}\n#define GFH_BLANES " << cfg.batch_lanes << "\n";
+  if (cfg.batch_loss < 0 || cfg.batch_loss > 2) { *err = "batch kernels: batch_loss is 0 (linear), 1 (cauchy) or 2 (huber)"; return false; }
+  const bool loss = cfg.batch_loss != 0;
+  if (loss) s << "#define GFH_BLOSS " << cfg.batch_loss << "\n";      // in the text of the loss units alone
   if (cfg.batch_cube) {             // batch_cube.hip: the data form and the load of a cube, in the text of the cube forms alone
     if (cfg.batch_y_type < 0 || cfg.batch_y_type > 2 || cfg.batch_error_type < 0 || cfg.batch_error_type > 4) { *err = "batch kernels: a cube's y_type is 0 ... 2, its error_type 0 ... 4"; return false; }
     s << "#define GFH_BCUBE 1\n#define GFH_BYTYPE " << cfg.batch_y_type << "\n#define GFH_BERR " << cfg.batch_error_type << "\n" << kBatchCube;
   }
   if (cfg.batch_lanes == 256) s << kBatchWgSum;          // batch_wg_sum.hip: LDS and a barrier, in the text of the workgroup form alone
-  s << kBatchFit;                   // batch_fit.hip: the passes and the solve of a fit, written once against GFH_BLANES
+  s << resolve_batch_loss(kBatchFit, loss);                   // batch_fit.hip: the passes and the solve of a fit, written once against GFH_BLANES
   if (cfg.batch_bounded) {          // the bounded unit: gfh_k_fit_batch_bounded alone behind them (batch_fit_bounded.hip)
-    s << kBatchFitBounded;
+    s << resolve_batch_loss(kBatchFitBounded, loss);
     return true;
   }
-  s << kBatchFitKernels;            // batch_fit_kernels.hip: gfh_k_fit_batch, gfh_k_batch_pass
-  s << kBatchCov;                   // batch_cov.hip: gfh_k_batch_cov, behind them in every form
+  s << resolve_batch_loss(kBatchFitKernels, loss);            // batch_fit_kernels.hip: gfh_k_fit_batch, gfh_k_batch_pass
+  s << resolve_batch_loss(kBatchCov, loss);                   // batch_cov.hip: gfh_k_batch_cov, behind them in every form
   s << kBatchEval;                  // batch_eval.hip: gfh_k_batch_eval, behind that
   return true;
 }

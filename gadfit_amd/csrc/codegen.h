@@ -37,6 +37,9 @@ struct GenConfig {
   int batch_error_type = 0; // gfh_init_weights' numbers: 0 NONE, 1 SQRT_Y, 2 PROPTO_Y, 3 INVERSE_Y, 4 USER (a plain load of w)
   bool batch_bounded = false; // ... the unit holds gfh_k_fit_batch_bounded (batch_fit_bounded.hip: the loop inside a box) INSTEAD of the four kernels:
                           // a translation unit of its own once more, so that the text of the four kernels' unit does not change by a byte
+  int batch_loss = 0;     // ... the loss of a batch (gfh_set_batch_loss): 0 linear, 1 cauchy, 2 huber.  Non-zero: `#define GFH_BLOSS <n>` in front of the
+                          // batch text, whose kernels then take inv_c = 1 / scale as one more argument; the scale is no part of the text.  The
+                          // text of a linear unit does not change by a byte.  `loss` above (GFH_LOSS of the plain units) stays 0 in a batch unit
   bool eval = false;      // the curves of a plain fit (eval.cpp): behind the point functions stand gfh_k_eval / gfh_k_eval_band and, for models a
                           // grid carries, gfh_k_eval_grid / gfh_k_eval_grid_band (eval.hip) INSTEAD of the kernels of a fit.  A translation
                           // unit of its own once more: the default one does not change by a byte

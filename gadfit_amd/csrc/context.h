@@ -193,6 +193,10 @@ struct gfh_ctx {
     int64_t max_points = 0;         // of the longest: with the active count, all the auto rule of gfh_set_batch_lanes reads
     int lanes = 64;                 // gfh_set_batch_lanes: 64 a wave per fit, 16 a DPP row per fit, 256 a workgroup per fit, 0 auto (gfh_batch_auto_lanes: 16 or 64)
     int last_lanes = 0;             // the form of the last batch launch (gfh_debug_batch_lanes); 0: none yet
+    int loss = 0;                   // gfh_set_batch_loss: 0 linear, 1 cauchy, 2 huber -- the batch's own, part of its unit's text; the plain fit's gfh_set_loss is refused in a batch
+    double loss_scale = 1.0;        // ... and the residual scale c of it (the loss switches at |r| = c); the kernels take 1 / c as an argument
+    int last_loss = -1;             // the loss and scale of the last batch launch that carries one (gfh_debug_batch_loss); -1: none yet
+    double last_loss_scale = 0.0;
     // gfh_set_batch_cube: every spectrum on one grid.  x holds the grid [n_points], y the samples [n_fits][n_points] in y_type
     // (0 double, 1 float, 2 uint16_t), w the weights under error_type 4 (USER) alone, off stays empty (min_points = max_points = n_points)
     bool cube = false;

@@ -16,9 +16,18 @@
 // parameters (GFH_BACT is the order of G[] and so of S).  A fit whose pivot fails gets NaN in all of its cov and sigma; nothing of
 // it reaches another fit.  All point access is the sweep's, through GFH_BLOAD: every data form is carried with nothing further.
 // (256 lanes per fit: the sweep's one barrier is the kernel's one barrier -- the BARRIER INVARIANT above gfh_k_fit_batch.)
+#if GFH_BLOSS
+// Under a loss (GFH_BLOSS) the matrix is J^T J of the loss-scaled Jacobian -- what the reference's getInvJTJ holds after a robust fit --
+// and under scale 1 it is multiplied by the PLAIN chi2 / dof, as gfh_covariance does on the plain path (errors.cpp): the sweep's last
+// sum is the plain sum r^2 under a loss too (gfh_b_sweep), so no further pass is made.
+extern "C" __global__ __launch_bounds__(256)
+void gfh_k_batch_cov(GFH_BARGS, const double* __restrict__ pars, const int scale, double* __restrict__ cov, double* __restrict__ sigma,
+                     int* __restrict__ info, const i64 n_fits, const double inv_c, int* __restrict__ status) {
+#else  // GFH_BLOSS
 extern "C" __global__ __launch_bounds__(256)
 void gfh_k_batch_cov(GFH_BARGS, const double* __restrict__ pars, const int scale, double* __restrict__ cov, double* __restrict__ sigma,
                      int* __restrict__ info, const i64 n_fits, int* __restrict__ status) {
+#endif  // GFH_BLOSS
 #pragma clang fp contract(off)
   const i64 f = GFH_BFIT(threadIdx.x);
   if (f >= n_fits) return;
@@ -27,7 +36,11 @@ void gfh_k_batch_cov(GFH_BARGS, const double* __restrict__ pars, const int scale
 #pragma unroll
   for (int k = 0; k < GFH_NP; k++) P[k] = gfh_uni(pars[f * GFH_NP + k]);
   GFH_BIMG_INIT
+#if GFH_BLOSS
+  gfh_b_sweep(d, P, status, S, inv_c GFH_BIMG);      // (256 lanes per fit: THE barrier, reached by all four waves -- the return above is per workgroup)
+#else  // GFH_BLOSS
   gfh_b_sweep(d, P, status, S GFH_BIMG);      // (256 lanes per fit: THE barrier, reached by all four waves -- the return above is per workgroup)
+#endif  // GFH_BLOSS
   double W[GFH_BNP];                          // U, then V, then C: the packed upper triangle, GFH_BIDX
   int bad = 0;
 #pragma unroll

@@ -85,9 +85,34 @@ struct gfh_bdata { const double* __restrict__ x; const double* __restrict__ y; c
 #define GFH_BLOAD(X, Y, W, i0) { const i64 i_ = (i0) + d.lane; const i64 c_ = i_ < d.e ? i_ : d.e - 1; \
   X = d.x[c_]; Y = d.y[c_]; const double w_ = d.w[c_]; W = i_ < d.e ? w_ : 0.0; }
 #endif
+#if GFH_BLOSS
+// The loss of a batch (GenConfig::batch_loss, gfh_set_batch_loss; DESIGN section 3a, Losses of a batch).  The lines between
+// `#if GFH_BLOSS`, `#else  // GFH_BLOSS` and `#endif  // GFH_BLOSS` are chosen by the GENERATOR (codegen.cpp, resolve_batch_loss), not by the
+// preprocessor: a linear-loss unit holds the #else arms alone and is byte for byte the text it was before a batch had a loss.
+// sqrt(rho'(u^2)) of the reference's costs (lm_solver.cpp:255-284) at u = r / c, r = (y - f) w the weighted residual and inv_c = 1 / c
+// the kernel argument: GFH_BLOSS 1 Cauchy, 2 Huber.  The sweep and the omega pass scale the residual and the Jacobian row by it as
+// GFH_ROBUST (sweep.hip) does at c = 1; nothing is divided by c, and chi2() (gfh_b_chi2) stays the plain sum.  Where ls is 1.0 the
+// two products change no bit.
+static __device__ __forceinline__ double gfh_b_ls(const double r, const double inv_c) {
+#pragma clang fp contract(off)
+  const double u = r * inv_c;
+#if GFH_BLOSS == 1
+  return __builtin_sqrt(1.0 / (1.0 + u * u));
+#else
+  return u * u > 1.0 ? __builtin_sqrt(1.0 / __builtin_fabs(u)) : 1.0;
+#endif
+}
+#endif  // GFH_BLOSS
 
+#if GFH_BLOSS
+// STEP 1 + 2 (gadfit.F90:675-699) of one fit under a loss: S = [J^T J upper triangle, packed | J^T r | sum r^2], J and the r of J^T r
+// scaled by ls (lm_solver.cpp:303-317), the last entry the PLAIN sum r^2 (chi2() of lm_solver.cpp:513-529: what gfh_k_batch_pass
+// returns and gfh_k_batch_cov scales by)
+static __device__ __forceinline__ void gfh_b_sweep(const gfh_bdata& d, const double* __restrict__ P, int* status, double (&S)[GFH_BNACC], const double inv_c GFH_BIMG_DECL) {
+#else  // GFH_BLOSS
 // STEP 1 + 2 (gadfit.F90:675-699) of one fit: S = [J^T J upper triangle, packed | J^T r | sum r^2]
 static __device__ __forceinline__ void gfh_b_sweep(const gfh_bdata& d, const double* __restrict__ P, int* status, double (&S)[GFH_BNACC] GFH_BIMG_DECL) {
+#endif  // GFH_BLOSS
   double av[GFH_BNACC];
 #pragma unroll
   for (int k = 0; k < GFH_BNACC; k++) av[k] = 0.0;
@@ -98,9 +123,23 @@ static __device__ __forceinline__ void gfh_b_sweep(const gfh_bdata& d, const dou
     GFH_BLOAD(Xn, Yn, Wn, i0 + GFH_BLANES < d.e ? i0 + GFH_BLANES : i0)       // next row's inputs (the last row re-reads its own)
     double F, G[GFH_NA];
     gfh_point_grad(Xc, P, F, G, status, (const double*)nullptr, 0 GFH_MESH_NONE GFH_SLOT(i0 + d.lane));
+#if GFH_BLOSS
+    const double r = (Yc - F) * Wc;                            // gadfit.F90:682-683
+    double R, Wl;
+    {
+#pragma clang fp contract(off)
+      const double ls = gfh_b_ls(r, inv_c);                    // lm_solver.cpp:303-317 (a per-lane select inside the point loop: no barrier here)
+      R = r * ls; Wl = Wc * ls;
+    }
+#else  // GFH_BLOSS
     const double R = (Yc - F) * Wc;                            // gadfit.F90:682-683
+#endif  // GFH_BLOSS
 #pragma unroll
+#if GFH_BLOSS
+    for (int a = 0; a < GFH_NA; a++) G[a] = G[a] * Wl;         // gadfit.F90:689-690, lm_solver.cpp:303-317
+#else  // GFH_BLOSS
     for (int a = 0; a < GFH_NA; a++) G[a] = G[a] * Wc;         // gadfit.F90:689-690
+#endif  // GFH_BLOSS
     int p = 0;
 #pragma unroll
     for (int a = 0; a < GFH_NA; a++)
@@ -108,7 +147,11 @@ static __device__ __forceinline__ void gfh_b_sweep(const gfh_bdata& d, const dou
       for (int b = a; b < GFH_NA; b++, p++) av[p] += G[a] * G[b];      // gadfit.F90:697
 #pragma unroll
     for (int a = 0; a < GFH_NA; a++) av[GFH_BNP + a] += G[a] * R;      // gadfit.F90:698
+#if GFH_BLOSS
+    av[GFH_BNP + GFH_NA] += r * r;
+#else  // GFH_BLOSS
     av[GFH_BNP + GFH_NA] += R * R;
+#endif  // GFH_BLOSS
     Xc = Xn; Yc = Yn; Wc = Wn;
   }
 #if GFH_BLANES == 256
@@ -139,8 +182,17 @@ static __device__ __forceinline__ double gfh_b_chi2(const gfh_bdata& d, const do
 #endif
 }
 // STEP 3 (gadfit.F90:715-735): omega_i = -f''_delta1(x_i) w_i and J^T omega with the Jacobian row recomputed, as gfh_k_omega_jt
+#if GFH_BLOSS
+// Under a loss omega stays unscaled and the recomputed row is the sweep's ls g w, ls from the residual at P (the sweep's parameters).
+// gfh_point_dd_grad returns no value, so f comes from gfh_point_value: one more value evaluation per point and no point function of
+// its own.  The compiler's figures decided that (Losses of a batch): a dd_grad that hands out its value keeps it
+// live through the reverse sweep and cost the 8-active Cauchy unit a wave per SIMD that this form keeps.
+static __device__ __forceinline__ void gfh_b_omega(const gfh_bdata& d, const double* __restrict__ P, const double* __restrict__ DP, int* status,
+                                                   double (&JTo)[GFH_NA], const double inv_c GFH_BIMG_DECL) {
+#else  // GFH_BLOSS
 static __device__ __forceinline__ void gfh_b_omega(const gfh_bdata& d, const double* __restrict__ P, const double* __restrict__ DP, int* status,
                                                    double (&JTo)[GFH_NA] GFH_BIMG_DECL) {
+#endif  // GFH_BLOSS
   double acc[GFH_NA], Xc, Yc, Wc;
 #pragma unroll
   for (int a = 0; a < GFH_NA; a++) acc[a] = 0.0;
@@ -149,10 +201,22 @@ static __device__ __forceinline__ void gfh_b_omega(const gfh_bdata& d, const dou
     double Xn, Yn, Wn;
     GFH_BLOAD(Xn, Yn, Wn, i0 + GFH_BLANES < d.e ? i0 + GFH_BLANES : i0)
     double G[GFH_NA];
+#if GFH_BLOSS
+    double Wl;                                                 // (formed in front of dd_grad: fewer values live across the value's body)
+    {
+#pragma clang fp contract(off)
+      const double r = (Yc - gfh_point_value(Xc, P, status, (const double*)nullptr, 0 GFH_MESH_NONE GFH_SLOT(i0 + d.lane))) * Wc;
+      Wl = Wc * gfh_b_ls(r, inv_c);                            // (per-lane, inside the point loop: no barrier here)
+    }
+#endif  // GFH_BLOSS
     const double om = -gfh_point_dd_grad(Xc, P, DP, G, status, (const double*)nullptr, 0 GFH_MESH_NONE GFH_SLOT(i0 + d.lane)) * Wc;   // gadfit.F90:722-723
 #pragma unroll
     for (int a = 0; a < GFH_NA; a++) {
+#if GFH_BLOSS
+      const double j = G[a] * Wl;                              // gadfit.F90:689-690, lm_solver.cpp:303-317
+#else  // GFH_BLOSS
       const double j = G[a] * Wc;                              // gadfit.F90:689-690
+#endif  // GFH_BLOSS
       acc[a] += j * om;                                        // gadfit.F90:734
     }
     Xc = Xn; Yc = Yn; Wc = Wn;

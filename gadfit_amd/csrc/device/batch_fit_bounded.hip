@@ -74,9 +74,17 @@ static __device__ __forceinline__ bool gfh_b_solve_pinned(const double (&S)[GFH_
 // holds no barrier, and its ok is (S) as gfh_b_solve's; gfh_b_clamp selects among P + delta (S) and box (K), so the trial points
 // that gfh_b_chi2 is called at, and new_chi2 < old_chi2 behind it, stay (S); the rel_error exit tests P (S) against box (K);
 // at_bound is written behind the loop under d.lane == 0, which encloses no barrier.  No per-lane value enters any of them.
+#if GFH_BLOSS
+// Under a loss (GFH_BLOSS) rule 1 pins on the sign of the sweep's loss-scaled J^T r -- the gradient of the cost the step descends --
+// and everything else is the rule unchanged.  inv_c (K) reaches only the point loops of gfh_b_sweep and gfh_b_omega, which hold no barrier.
+extern "C" __global__ __launch_bounds__(256)
+void gfh_k_fit_batch_bounded(GFH_BARGS, double* __restrict__ pars, const gfh_batch_opts o, const gfh_batch_box box,
+                             gfh_batch_rec* __restrict__ recs, int* __restrict__ at_bound, const i64 n_fits, const double inv_c, int* __restrict__ status) {
+#else  // GFH_BLOSS
 extern "C" __global__ __launch_bounds__(256)
 void gfh_k_fit_batch_bounded(GFH_BARGS, double* __restrict__ pars, const gfh_batch_opts o, const gfh_batch_box box,
                              gfh_batch_rec* __restrict__ recs, int* __restrict__ at_bound, const i64 n_fits, int* __restrict__ status) {
+#endif  // GFH_BLOSS
 #pragma clang fp contract(off)
   const i64 f = GFH_BFIT(threadIdx.x);
   if (f >= n_fits) return;
@@ -95,7 +103,11 @@ void gfh_k_fit_batch_bounded(GFH_BARGS, double* __restrict__ pars, const gfh_bat
   double old_chi2 = gfh_b_chi2(d, P, status GFH_BIMG), new_chi2 = 0.0, old_old_chi2 = 0.0;             // gadfit.F90:670
   n_chi2++;
   for (;;) {
+#if GFH_BLOSS
+    gfh_b_sweep(d, P, status, S, inv_c GFH_BIMG);                                              // STEP 1 + 2, gadfit.F90:675-701
+#else  // GFH_BLOSS
     gfh_b_sweep(d, P, status, S GFH_BIMG);                                                     // STEP 1 + 2, gadfit.F90:675-701
+#endif  // GFH_BLOSS
     n_sweeps++;
     int pin = 0;
 #pragma unroll
@@ -114,7 +126,11 @@ void gfh_k_fit_batch_bounded(GFH_BARGS, double* __restrict__ pars, const gfh_bat
       for (int k = 0; k < GFH_NP; k++) DP[k] = 0.0;
 #pragma unroll
       for (int j = 0; j < GFH_NA; j++) DP[act[j]] = delta1[j];
+#if GFH_BLOSS
+      gfh_b_omega(d, P, DP, status, JTo, inv_c GFH_BIMG);
+#else  // GFH_BLOSS
       gfh_b_omega(d, P, DP, status, JTo GFH_BIMG);
+#endif  // GFH_BLOSS
       n_omega++;
       if (!gfh_b_solve_pinned(S, DTD, lambda, JTo, pin, delta2)) { exit_reason = 8; break; }  // gadfit.F90:736-738 (the same matrix: the same factor)
       const double acc_ratio = __builtin_sqrt(gfh_b_dtd(delta2, DTD, delta2) / gfh_b_dtd(delta1, DTD, delta1));

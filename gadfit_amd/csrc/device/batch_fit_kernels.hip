@@ -20,9 +20,19 @@
 // and on the lane inside gfh_b_sum_n enclose no barrier.  Lane 0 of wave 0 writes the parameters and the record.
 // The cube's load (batch_cube.hip) adds only per-lane values -- the sample converted to double and the weight formed from it -- and
 // none of them enters a branch that encloses a barrier: its selects (the threshold of SQRT_Y / PROPTO_Y, the clamp) sit inside GFH_BLOAD.
+#if GFH_BLOSS
+// Under a loss (GFH_BLOSS; batch_fit.hip, gfh_b_ls) the kernels take inv_c = 1 / scale (K) behind their own arguments.  The loss adds
+// per-lane selects (Huber's u^2 > 1) and per-lane factors inside the point loops of gfh_b_sweep and gfh_b_omega, which hold no barrier;
+// what comes out of them still goes through gfh_b_sum_n, so S and J^T omega stay (S) and no per-lane value enters a branch that encloses
+// a barrier.  The acceptance test stays on the plain chi2 of gfh_b_chi2 (lm_solver.cpp:438-465), which the loss does not reach.
+extern "C" __global__ __launch_bounds__(256)
+void gfh_k_fit_batch(GFH_BARGS, double* __restrict__ pars, const gfh_batch_opts o,
+                     gfh_batch_rec* __restrict__ recs, const i64 n_fits, const double inv_c, int* __restrict__ status) {
+#else  // GFH_BLOSS
 extern "C" __global__ __launch_bounds__(256)
 void gfh_k_fit_batch(GFH_BARGS, double* __restrict__ pars, const gfh_batch_opts o,
                      gfh_batch_rec* __restrict__ recs, const i64 n_fits, int* __restrict__ status) {
+#endif  // GFH_BLOSS
 #pragma clang fp contract(off)
   const i64 f = GFH_BFIT(threadIdx.x);
   if (f >= n_fits) return;
@@ -41,7 +51,11 @@ void gfh_k_fit_batch(GFH_BARGS, double* __restrict__ pars, const gfh_batch_opts 
   double old_chi2 = gfh_b_chi2(d, P, status GFH_BIMG), new_chi2 = 0.0, old_old_chi2 = 0.0;             // gadfit.F90:670
   n_chi2++;
   for (;;) {
+#if GFH_BLOSS
+    gfh_b_sweep(d, P, status, S, inv_c GFH_BIMG);                                              // STEP 1 + 2, gadfit.F90:675-701
+#else  // GFH_BLOSS
     gfh_b_sweep(d, P, status, S GFH_BIMG);                                                     // STEP 1 + 2, gadfit.F90:675-701
+#endif  // GFH_BLOSS
     n_sweeps++;
 #pragma unroll
     for (int j = 0; j < GFH_NA; j++) {                                                        // gadfit.F90:702-710
@@ -56,7 +70,11 @@ void gfh_k_fit_batch(GFH_BARGS, double* __restrict__ pars, const gfh_batch_opts 
       for (int k = 0; k < GFH_NP; k++) DP[k] = 0.0;
 #pragma unroll
       for (int j = 0; j < GFH_NA; j++) DP[act[j]] = delta1[j];
+#if GFH_BLOSS
+      gfh_b_omega(d, P, DP, status, JTo, inv_c GFH_BIMG);
+#else  // GFH_BLOSS
       gfh_b_omega(d, P, DP, status, JTo GFH_BIMG);
+#endif  // GFH_BLOSS
       n_omega++;
       if (!gfh_b_solve(S, DTD, lambda, JTo, delta2)) { exit_reason = 8; break; }              // gadfit.F90:736-738 (the same matrix: the same factor)
       const double acc_ratio = __builtin_sqrt(gfh_b_dtd(delta2, DTD, delta2) / gfh_b_dtd(delta1, DTD, delta1));
@@ -118,8 +136,13 @@ void gfh_k_fit_batch(GFH_BARGS, double* __restrict__ pars, const gfh_batch_opts 
 // STEP 1 + 2 only, at given parameters: each fit's J^T J [na x na] (both triangles), J^T r [na] and chi2 -- the "one pass" of
 // callers with their own loop.  img [n_fits][na * na + na + 1].
 extern "C" __global__ __launch_bounds__(256)
+#if GFH_BLOSS
+void gfh_k_batch_pass(GFH_BARGS, const double* __restrict__ pars, double* __restrict__ img,
+                      const i64 n_fits, const double inv_c, int* __restrict__ status) {
+#else  // GFH_BLOSS
 void gfh_k_batch_pass(GFH_BARGS, const double* __restrict__ pars, double* __restrict__ img,
                       const i64 n_fits, int* __restrict__ status) {
+#endif  // GFH_BLOSS
   const i64 f = GFH_BFIT(threadIdx.x);
   if (f >= n_fits) return;
   const gfh_bdata d = GFH_BDATA(f);
@@ -127,7 +150,11 @@ void gfh_k_batch_pass(GFH_BARGS, const double* __restrict__ pars, double* __rest
 #pragma unroll
   for (int k = 0; k < GFH_NP; k++) P[k] = gfh_uni(pars[f * GFH_NP + k]);
   GFH_BIMG_INIT
+#if GFH_BLOSS
+  gfh_b_sweep(d, P, status, S, inv_c GFH_BIMG);      // (256 lanes per fit: one barrier, reached by all four waves -- the return above is per workgroup)
+#else  // GFH_BLOSS
   gfh_b_sweep(d, P, status, S GFH_BIMG);      // (256 lanes per fit: one barrier, reached by all four waves -- the return above is per workgroup)
+#endif  // GFH_BLOSS
   if (d.lane == 0) {
     double* __restrict__ out = img + f * (GFH_NA * GFH_NA + GFH_NA + 1);
 #pragma unroll

@@ -331,6 +331,18 @@ def _batch_bounds(who, bounds, errors):
     return lower, upper
 
 
+def _batch_loss(who, loss, loss_scale):
+    """the ``loss`` and ``loss_scale`` arguments of the batch calls as set_batch_loss takes them: None is the linear loss and scale 1, so
+    that every call sets the batch loss itself and nothing stays behind from an earlier one"""
+    loss = LOSS_LINEAR if loss is None else loss
+    if isinstance(loss, bool) or not isinstance(loss, (int, np.integer)) or loss not in (LOSS_LINEAR, LOSS_CAUCHY, LOSS_HUBER):
+        raise GadfitError('%s: loss must be None, LOSS_LINEAR, LOSS_CAUCHY or LOSS_HUBER, got %r' % (who, loss))
+    scale = 1.0 if loss_scale is None else loss_scale
+    if isinstance(scale, bool) or not isinstance(scale, (int, float, np.integer, np.floating)) or not (np.isfinite(scale) and scale > 0):
+        raise GadfitError('%s: loss_scale must be a finite number > 0 (the weighted residual at which the loss switches), got %r' % (who, loss_scale))
+    return int(loss), float(scale)
+
+
 def _batch_fit(pars, active, scale, bounds, **kw):
     """fit_batch, fit_batch_errors under errors= or fit_batch_bounded under bounds=: what the batch calls return"""
     if bounds is not None:
@@ -344,7 +356,8 @@ def _batch_fit(pars, active, scale, bounds, **kw):
 
 
 def gadf_fit_batch(xs, ys, ws, pars, lambda_=None, lam_up=None, lam_down=None, accth=None, rel_error=None, chi2_rel=None,
-                   chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, lanes_per_fit=None, errors=None, bounds=None, **kw):
+                   chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, lanes_per_fit=None, errors=None, bounds=None,
+                   loss=None, loss_scale=None, **kw):
     """Many independent fits of the session's model in one kernel launch (gfh_fit_batch): gadf_fit's loop (gadfit.F90:670-915) per
     spectrum, each with its own data, start parameters, lambda history and exit.  On a session initialised with one dataset slot
     (``gadf_init(f)``); the active set is the one ``gadf_set`` left.  ``xs, ys, ws``: one array per spectrum (``ws``: the weights as
@@ -358,8 +371,12 @@ def gadf_fit_batch(xs, ys, ws, pars, lambda_=None, lam_up=None, lam_down=None, a
     factor failed and its cov and sigma are NaN), computed on the device behind the fit (gfh_fit_batch_errors).  ``bounds``: None, or
     (lower, upper) -- one box for all fits, each a sequence of one number per active parameter in the order of the active set, None
     or -inf / +inf for no bound on that side: the projected loop of gfh_fit_batch_bounded, and a third element ``dict(at_bound=...)``
-    [n_fits] (bit j: the returned active parameter j equals lower[j], bit 8 + j: upper[j]).  ``bounds`` with ``errors`` is refused."""
+    [n_fits] (bit j: the returned active parameter j equals lower[j], bit 8 + j: upper[j]).  ``bounds`` with ``errors`` is refused.
+    ``loss``: None or LOSS_LINEAR, LOSS_CAUCHY, LOSS_HUBER -- the batch's own robust cost (gfh_set_batch_loss), set by this call for this
+    call -- and ``loss_scale`` the weighted residual |(y - f) w| at which it switches (None: 1, the reference's costs); the steps are
+    accepted on the plain chi2, which is also the records'.  The session's ``gadf_set_loss`` is the plain fit's and stays refused here."""
     _need_init()
+    batch_loss = _batch_loss('gadf_fit_batch', loss, loss_scale)
     scale = _batch_errors('gadf_fit_batch', errors)
     bounds = _batch_bounds('gadf_fit_batch', bounds, errors)
     if 'lambda' in kw:
@@ -383,7 +400,7 @@ def gadf_fit_batch(xs, ys, ws, pars, lambda_=None, lam_up=None, lam_down=None, a
     np.cumsum([v.size for v in xs], out=off[1:])
     try:
         _S.ctx.set_batch_data(off, np.concatenate(xs), np.concatenate(ys), np.concatenate(ws))
-        return _batch_fit(pars, active, scale, bounds, DTD_min=DTD_min, lanes_per_fit=lanes_per_fit, lambda_=_f32(lambda_), lam_up=_f32(lam_up), lam_down=_f32(lam_down),
+        return _batch_fit(pars, active, scale, bounds, DTD_min=DTD_min, lanes_per_fit=lanes_per_fit, loss=batch_loss[0], loss_scale=batch_loss[1], lambda_=_f32(lambda_), lam_up=_f32(lam_up), lam_down=_f32(lam_down),
                           accth=_f32(accth), rel_error=_f32(rel_error), chi2_rel=_f32(chi2_rel), chi2_abs=_f32(chi2_abs),
                           lam_incs=lam_incs, max_iter=max_iter, damp_max=None if damp_max is None else int(damp_max),
                           **{k: v for k, v in kw.items() if v is not None})
@@ -391,9 +408,10 @@ def gadf_fit_batch(xs, ys, ws, pars, lambda_=None, lam_up=None, lam_down=None, a
         raise GadfitError(str(e))
 
 
-def _fit_cube(who, frames, x, Y, pars, sigma, DTD_min, lanes_per_fit, frames_per_put, errors, bounds, kw):
+def _fit_cube(who, frames, x, Y, pars, sigma, DTD_min, lanes_per_fit, frames_per_put, errors, bounds, loss, loss_scale, kw):
     """gadf_fit_cube and gadf_fit_frames: one body, the data spectrum-major (Y [n_fits][n_points]) or frame-major (F [n_points][n_fits])"""
     _need_init()
+    batch_loss = _batch_loss(who, loss, loss_scale)
     scale = _batch_errors(who, errors)
     bounds = _batch_bounds(who, bounds, errors)
     if _S.n_datasets != 1:
@@ -426,7 +444,7 @@ def _fit_cube(who, frames, x, Y, pars, sigma, DTD_min, lanes_per_fit, frames_per
             _S.ctx.set_batch_frames(x, Y, _S.error_type, None if sigma is None else 1.0 / sigma, frames_per_put)
         else:
             _S.ctx.set_batch_cube(x, Y, _S.error_type, None if sigma is None else 1.0 / sigma)
-        return _batch_fit(pars, active, scale, bounds, DTD_min=DTD_min, lanes_per_fit=lanes_per_fit, **kw)
+        return _batch_fit(pars, active, scale, bounds, DTD_min=DTD_min, lanes_per_fit=lanes_per_fit, loss=batch_loss[0], loss_scale=batch_loss[1], **kw)
     except _lib.GadfitHipError as e:
         raise GadfitError(str(e))
 
@@ -440,25 +458,27 @@ def _cube_fit_args(lambda_, lam_up, lam_down, accth, rel_error, chi2_rel, chi2_a
 
 
 def gadf_fit_cube(x, Y, pars, sigma=None, lambda_=None, lam_up=None, lam_down=None, accth=None, rel_error=None, chi2_rel=None,
-                  chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, lanes_per_fit=None, errors=None, bounds=None, **kw):
+                  chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, lanes_per_fit=None, errors=None, bounds=None,
+                  loss=None, loss_scale=None, **kw):
     """gadf_fit_batch over a data cube (gfh_set_batch_cube): every spectrum on the one grid ``x`` [n_points], ``Y`` [n_fits][n_points] a
     C-contiguous numpy array of float64, float32 or uint16 that is uploaded as it is.  The weights follow from ``Y`` on the device by
     the session's ``gadf_set_errors`` type (NONE, SQRT_Y, PROPTO_Y, INVERSE_Y: no weight array exists anywhere; gadf_fit_batch ignores
     that type, this call takes it); under USER ``sigma`` [n_fits][n_points] is required and 1 / sigma is passed.  ``pars``, the fit
-    arguments, ``lanes_per_fit``, ``errors``, ``bounds`` and what is returned are gadf_fit_batch's."""
-    return _fit_cube('gadf_fit_cube', False, x, Y, pars, sigma, DTD_min, lanes_per_fit, 0, errors, bounds,
+    arguments, ``lanes_per_fit``, ``errors``, ``bounds``, ``loss``, ``loss_scale`` and what is returned are gadf_fit_batch's; the weights
+    are formed on the device, so ``loss_scale`` is the one way to move a loss's threshold here."""
+    return _fit_cube('gadf_fit_cube', False, x, Y, pars, sigma, DTD_min, lanes_per_fit, 0, errors, bounds, loss, loss_scale,
                      _cube_fit_args(lambda_, lam_up, lam_down, accth, rel_error, chi2_rel, chi2_abs, lam_incs, max_iter, damp_max, kw))
 
 
 def gadf_fit_frames(x, F, pars, sigma=None, lambda_=None, lam_up=None, lam_down=None, accth=None, rel_error=None, chi2_rel=None,
                     chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, lanes_per_fit=None, frames_per_put=0, errors=None,
-                    bounds=None, **kw):
+                    bounds=None, loss=None, loss_scale=None, **kw):
     """gadf_fit_cube for a stack of frames (gfh_set_batch_frames): ``F`` [n_points][n_fits], one image per abscissa of ``x`` with the
     fit (pixel) index fastest, as instruments deliver it -- C-contiguous in float64, float32 or uint16, uploaded as it is and
     transposed into the cube on the device, so no ``np.ascontiguousarray(F.T)`` runs on the host.  ``sigma`` (under USER) is
     frame-major as ``F``; ``frames_per_put``: frames per upload, 0 the library's rule.  Everything else, and what is returned (the
     bits included), is gadf_fit_cube's on the transposed arrays."""
-    return _fit_cube('gadf_fit_frames', True, x, F, pars, sigma, DTD_min, lanes_per_fit, frames_per_put, errors, bounds,
+    return _fit_cube('gadf_fit_frames', True, x, F, pars, sigma, DTD_min, lanes_per_fit, frames_per_put, errors, bounds, loss, loss_scale,
                      _cube_fit_args(lambda_, lam_up, lam_down, accth, rel_error, chi2_rel, chi2_abs, lam_incs, max_iter, damp_max, kw))
 
 

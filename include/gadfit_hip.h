@@ -559,6 +559,24 @@ int  gfh_set_batch_lanes(gfh_ctx* ctx, int lanes);
 int  gfh_batch_auto_lanes(int n_act, int64_t longest_spectrum);
 /* 64, 16 or 256: the form of the last batch launch of this context (0: none yet).  For tests that assert the dispatch. */
 int  gfh_debug_batch_lanes(gfh_ctx* ctx);
+/* The loss of every batch call from here on (it stays set, as gfh_set_batch_lanes; no GPU and no model needed): GFH_LOSS_LINEAR (the
+ * default), GFH_LOSS_CAUCHY or GFH_LOSS_HUBER -- the reference's robust costs (lm_solver.cpp:255-284), as gfh_set_loss gives the plain
+ * fit -- and a residual scale c > 0 (the f_scale of other least-squares libraries; 1: the reference's own).  With r = (y - f) w the
+ * weighted residual and u = r / c, STEP 1+2 scale r and its Jacobian row by ls = sqrt(1 / (1 + u^2)) (Cauchy) or u^2 > 1 ?
+ * sqrt(1 / |u|) : 1 (Huber); nothing is divided by c.  STEP 3's omega stays unscaled and its J^T omega takes the scaled rows.  chi2 stays
+ * the plain sum r^2 everywhere: the trial chi2 of STEP 4, the acceptance test new < old (the reference's rule: a robust step is accepted
+ * on the plain chi2), the record's chi2 and gfh_batch_pass's.  gfh_batch_covariance / gfh_fit_batch_errors invert J^T J of the scaled
+ * Jacobian (the reference's getInvJTJ after a robust fit) and multiply, under scale 1, by the plain chi2 / dof as gfh_covariance does;
+ * gfh_fit_batch_bounded pins on the sign of the scaled J^T r; gfh_batch_eval's residual stays the plain (y - f) w.  With c = 2^k every
+ * sum equals 4^k times that of c = 1 with the weights times 2^-k: the same parameters, counts and lambda bit for bit.  A cube forms its
+ * weights on the device, so c is the one way to move the threshold there.  Refused: an unknown loss; a scale that is NaN, infinite, or
+ * not positive.  The context's gfh_set_loss != 0 stays refused by every batch call: a batch is built from its own settings.  One loss
+ * and one scale per batch; the loss is part of the unit's text (units of all losses stay loaded side by side), 1 / c a kernel argument. */
+int  gfh_set_batch_loss(gfh_ctx* ctx, int loss, double scale);
+/* The setting as it stands: the loss (return value; -1: ctx is NULL) and *scale (may be NULL).  0 and 1.0 until it is set. */
+int  gfh_get_batch_loss(gfh_ctx* ctx, double* scale);
+/* The loss (return value; -1: none yet) and *scale (may be NULL) of the last batch launch of this context that sweeps. */
+int  gfh_debug_batch_loss(gfh_ctx* ctx, double* scale);
 /* Device time of the kernel of this context's last gfh_batch_pass in seconds (HIP events around the launch; 0: none yet): the
  * yardstick tools/bench_batch.py --eval holds gfh_batch_eval's kernel against. */
 double gfh_debug_batch_pass_seconds(gfh_ctx* ctx);

@@ -11,6 +11,7 @@ profiles/r05_small_fits.txt: 1000 points, a Gaussian on a background, 4 paramete
     python tools/bench_batch.py --frames [--cells uint16:1:64:131072:1000,...] [--out profiles/batch_frames.json]
     python tools/bench_batch.py --cov [--sizes 16384,131072] [--points 1000] [--lanes 64] [--out profiles/batch_cov.json]
     python tools/bench_batch.py --bounds [--sizes 16384] [--points 1000] [--lanes 64] [--out profiles/batch_bounds.json]
+    python tools/bench_batch.py --loss [--registers] [--sizes 16384] [--points 1000] [--lanes 64] [--out profiles/batch_loss.json]
     python tools/bench_batch.py --eval [--cells gauss4:64:16384:1000,...] [--registers] [--observed FILE] [--out profiles/batch_eval.json]
 
 Per batch size: warm-up launches, then the median of the timed launches -- device time from the HIP events around the kernel
@@ -66,6 +67,14 @@ this tool's problem with 4 active parameters and on the four exponentials with 8
 fit_batch_bounded with every bound infinite (the same bits, checked) and fit_batch_bounded with a binding box, alternating call by call
 in one run on one card; device and wall time, median and min-max.  The ratio of the first two is written down with whether it lies
 beyond the two routes' own spread; nothing is asserted on it.
+--loss: the loss units of the batch kernels (gfh_set_batch_loss: Cauchy and Huber at c = 1) against the linear unit -- the parent
+commit's kernels, whose text did not change -- on this tool's problem with 4 active parameters and on the four exponentials with 8,
+16384 fits of 1000 points at 64 lanes.  The weights are 1 / sigma with sigma = 1e-3, the amplitude of the spectra's ripple, and 1 % of
+the samples (a fixed pattern) are displaced by +12 sigma.  Linear, Cauchy and Huber alternate call by call on one context; per loss
+batch_pass (the per-pass cost, free of the iteration counts; HIP events around its kernel) and fit_batch (events around its kernel,
+with the fits' total sweeps, chi2 passes and omega passes beside it, under accth so that the omega pass is in it); median and min-max.
+No ratio is asserted.  --registers: only the compiler's figures of the linear and the loss units of model_exp2 (4 active) and
+model_exp4 (8 active) at the three lane forms, the bounded unit included; no GPU is needed.
 
 --eval: the curves of a batch (gfh_batch_eval: the kernel gfh_k_batch_eval) at the cells of the cube table, on the ragged form and on
 the uint16 cube under SQRT_Y of the same counts, at the start parameters with the device's own covariance.  Per cell and form three
@@ -192,7 +201,7 @@ def kernel_registers(src):
                             '-ffp-contract=on', '--cuda-device-only', '-c', f, '-o', os.path.join(d, 'unit.o'),
                             '-Rpass-analysis=kernel-resource-usage'], capture_output=True, text=True, check=True)
     out, name = {}, None
-    keys = {'VGPRs': 'vgprs', 'AGPRs': 'agprs', 'TotalSGPRs': 'sgprs', 'ScratchSize [bytes/lane]': 'scratch_bytes_per_lane',
+    keys = {'VGPRs': 'vgprs', 'AGPRs': 'agprs', 'TotalSGPRs': 'sgprs', 'SGPRs Spill': 'sgprs_spilled', 'VGPRs Spill': 'vgprs_spilled', 'ScratchSize [bytes/lane]': 'scratch_bytes_per_lane',
             'Occupancy [waves/SIMD]': 'waves_per_simd', 'LDS Size [bytes/block]': 'lds_bytes_per_block'}
     for line in r.stderr.splitlines():
         m = re.search(r'remark:\s+(.*?): (\S+) \[-Rpass', line)
@@ -455,6 +464,85 @@ def bounds_main(a):
             print('%-6s %7d fits: device fit %.3f ms [%.3f, %.3f], bounded (no bound) %.3f ms [%.3f, %.3f], ratio %.4f%s; bounded (box) %.3f ms, %d fits on a bound'
                   % (name, nf, f['median'], f['min'], f['max'], b['median'], b['min'], b['max'], entry['device_bounded_inf_over_fit'],
                      ' (beyond the spread)' if entry['beyond_spread'] else '', entry['device_ms_bounded_box']['median'], entry['fits_on_a_bound_under_the_box']), flush=True)
+            with open(a.out, 'w') as fh:
+                json.dump(rec, fh, indent=1, sort_keys=True)
+                fh.write('\n')
+    print('wrote', a.out)
+
+
+# --loss
+LOSS_SIGMA, LOSS_NAMES = 1.0e-3, ('linear', 'cauchy', 'huber')
+
+
+def loss_registers_record():
+    """{model_lanesN_<loss>: the compiler's figures of the unit's kernels, gfh_k_fit_batch_bounded (a unit of its own) among them}"""
+    from tests import models as M
+    rec = {}
+    c = _lib.Context(-1)
+    for name, fn, n_pars in (('exp2', M.model_exp2, 4), ('exp4', M.model_exp4, 8)):
+        c.set_model(trace_model(fn, n_pars))
+        for lanes in (64, 16, 256):
+            c.set_batch_lanes(lanes)
+            for loss, lname in enumerate(LOSS_NAMES):
+                c.set_batch_loss(loss, 1.0)
+                r = kernel_registers(c.batch_source(list(range(n_pars))))
+                r.update(kernel_registers(c.batch_source(list(range(n_pars)), bounded=True)))
+                r.pop('gfh_k_batch_eval', None)
+                rec['%s_lanes%d_%s' % (name, lanes, lname)] = r
+    c.close()
+    return rec
+
+
+def loss_main(a):
+    """the linear, Cauchy and Huber units against each other (see the module's text)"""
+    n_points, lanes = int(a.points or 1000), int(a.lanes or 64)
+    rec = json.load(open(a.out)) if os.path.exists(a.out) else {}
+    rec.update(method='per model the three losses alternating call by call on one context of one card in one run: linear = the unit of the parent '
+                      'commit, whose text did not change; cauchy, huber = set_batch_loss(1 / 2, 1.0).  weights 1 / sigma with sigma = %g (the ripple of '
+                      'the spectra), every sample with (7919 k + 104729 i) %% 100 == 0 (k the fit, i the point: 1 %%) displaced by +12 sigma.  pass = '
+                      'batch_pass at the start parameters, fit = fit_batch with lambda0 = %g, max_iter = %d, accth = 0.9; device time (HIP events around '
+                      'the kernel), the median and the min-max of %d calls after %d warm-up calls; %d points per spectrum, %d lanes per fit; passes = '
+                      'the fits\' total sweeps, chi2 passes and omega passes; no counter pass was made and no ratio is asserted'
+                      % (LOSS_SIGMA, LAMBDA0, MAX_ITER, a.launches, a.warmup, n_points, lanes), measurements=[])
+    kw = dict(lambda_=LAMBDA0, max_iter=MAX_ITER, accth=0.9)
+    for name in ('gauss4', 'exp4'):
+        m = ROW_MODELS[name]
+        for nf in [int(s) for s in a.sizes.split(',')]:
+            xs, ys, ws = spectra_flat(name, nf, n_points)
+            hit = (7919 * np.arange(nf, dtype=np.int64)[:, None] + 104729 * np.arange(n_points, dtype=np.int64)[None, :]) % 100 == 0
+            ys[hit.reshape(-1)] += 12.0 * LOSS_SIGMA
+            ws[:] = 1.0 / LOSS_SIGMA
+            ctx = _lib.Context(0)
+            ctx.set_model(trace_model(m['model'], m['n_pars']))
+            ctx.set_batch_lanes(lanes)
+            ctx.set_batch_data(np.arange(nf + 1, dtype=np.int64) * n_points, xs, ys, ws)
+            del xs, ys, ws
+            start = np.tile(m['start'], (nf, 1))
+            dev = {k: dict(pass_=[], fit=[]) for k in LOSS_NAMES}
+            last = {}
+            for it in range(a.warmup + a.launches):
+                for loss, lname in enumerate(LOSS_NAMES):
+                    ctx.set_batch_loss(loss, 1.0)
+                    ctx.batch_pass(start, m['active'])
+                    sec_p = ctx.batch_pass_seconds()
+                    p, r, sec = ctx.fit_batch(start, m['active'], **kw)
+                    last[lname] = (p, r)
+                    if it >= a.warmup:
+                        dev[lname]['pass_'].append(sec_p); dev[lname]['fit'].append(sec)
+            ctx.close()
+            entry = dict(model=name, what=m['what'], n_active=len(m['active']), fits=nf, points=n_points, lanes=lanes, displaced_samples=int(hit.sum()))
+            for lname in LOSS_NAMES:
+                p, r = last[lname]
+                entry[lname] = dict(device_ms_pass=_spread(dev[lname]['pass_']), device_ms_fit=_spread(dev[lname]['fit']),
+                                    passes=dict(sweeps=int(r['n_sweeps'].sum()), chi2=int(r['n_chi2'].sum()), omega=int(r['n_omega'].sum())),
+                                    exits={str(k): int(np.sum(r['exit_reason'] == k)) for k in sorted(set(r['exit_reason'].tolist()))},
+                                    median_parameters=[float(v) for v in np.median(p, axis=0)])
+                e = entry[lname]
+                print('%-6s %7d fits %-6s: pass %.4f ms [%.4f, %.4f], fit %.3f ms [%.3f, %.3f], sweeps %d chi2 %d omega %d'
+                      % (name, nf, lname, e['device_ms_pass']['median'], e['device_ms_pass']['min'], e['device_ms_pass']['max'],
+                         e['device_ms_fit']['median'], e['device_ms_fit']['min'], e['device_ms_fit']['max'],
+                         e['passes']['sweeps'], e['passes']['chi2'], e['passes']['omega']), flush=True)
+            rec['measurements'].append(entry)
             with open(a.out, 'w') as fh:
                 json.dump(rec, fh, indent=1, sort_keys=True)
                 fh.write('\n')
@@ -845,6 +933,7 @@ def main():
     ap.add_argument('--frames', action='store_true', help='a stack of frames against the host transpose and the upload alone, into profiles/batch_frames.json')
     ap.add_argument('--cov', action='store_true', help='fit_batch_errors against fit_batch alone and against the host route, into profiles/batch_cov.json')
     ap.add_argument('--bounds', action='store_true', help='fit_batch_bounded under infinite bounds and under a binding box against fit_batch, into profiles/batch_bounds.json')
+    ap.add_argument('--loss', action='store_true', help='the Cauchy and Huber units of the batch kernels against the linear unit, into profiles/batch_loss.json')
     ap.add_argument('--eval', action='store_true', help='batch_eval against batch_pass and against the bytes it moves, into profiles/batch_eval.json')
     ap.add_argument('--cells', default=None, help='with --cube and --eval: model:lanes:fits:points, ...; with --frames: sample type:error type:lanes:fits:points, ...')
     ap.add_argument('--models', default='gauss4,exp4', help='with --workgroup: the models measured by this call (the record keeps the others)')
@@ -860,9 +949,17 @@ def main():
                                                                  'nothing is timed, no GPU is needed')
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'batch_bounds.json' if a.bounds else 'batch_eval.json' if a.eval else 'batch_cov.json' if a.cov else 'batch_frames.json' if a.frames else 'batch_cube.json' if a.cube else 'batch_workgroup.json' if a.workgroup else 'batch_rows.json' if a.rows else 'batch_fits.json')
+        a.out = os.path.join(ROOT, 'profiles', 'batch_loss.json' if a.loss else 'batch_bounds.json' if a.bounds else 'batch_eval.json' if a.eval else 'batch_cov.json' if a.cov else 'batch_frames.json' if a.frames else 'batch_cube.json' if a.cube else 'batch_workgroup.json' if a.workgroup else 'batch_rows.json' if a.rows else 'batch_fits.json')
     if a.cells is None:
         a.cells = FRAMES_CELLS if a.frames else EVAL_CELLS if a.eval else CUBE_CELLS
+    if a.loss and a.registers:
+        rec = json.load(open(a.out)) if os.path.exists(a.out) else {}
+        rec['registers'] = loss_registers_record()
+        with open(a.out, 'w') as fh:
+            json.dump(rec, fh, indent=1, sort_keys=True)
+            fh.write('\n')
+        print('wrote', a.out)
+        return
     if a.eval and (a.registers or a.observed):
         rec = json.load(open(a.out)) if os.path.exists(a.out) else {}
         if a.registers:
@@ -905,6 +1002,10 @@ def main():
         if a.sizes == '1024,16384,131072':
             a.sizes = '16384'
         return bounds_main(a)
+    if a.loss:
+        if a.sizes == '1024,16384,131072':
+            a.sizes = '16384'
+        return loss_main(a)
     if a.cov:
         if a.sizes == '1024,16384,131072':
             a.sizes = '16384,131072'
