@@ -24,6 +24,7 @@ def lib():
             build()
         _LIB = C.CDLL(so)
         _LIB.orc_last_error.restype = C.c_char_p
+        _LIB.orc_report_exit_margin(1)          # FitResult below has min_exit_margin (gadfit_oracle.h)
     return _LIB
 
 
@@ -56,7 +57,7 @@ class FitResult(C.Structure):
                 ('dof', C.c_int), ('exit_reason', C.c_int), ('n_sweeps', C.c_int), ('n_chi2', C.c_int),
                 ('n_omega', C.c_int), ('JTJ0', C.POINTER(C.c_double)), ('JTres0', C.POINTER(C.c_double)),
                 ('delta1_0', C.POINTER(C.c_double)), ('delta2_0', C.POINTER(C.c_double)), ('chi2_0', C.c_double),
-                ('min_margin', C.c_double)]
+                ('min_margin', C.c_double), ('min_exit_margin', C.c_double)]
 
 
 def _dp(a):

@@ -1051,6 +1051,11 @@ static double dtd_dot(int dim, const double* DTD, const double* a, const double*
   double s = 0; for (int i = 0; i < dim; i++) s += a[i] * (DTD[i] * b[i]); return s;
 }
 
+/* orc_fit_result grew by min_exit_margin: a caller that holds the shorter result must not be written past its end, so the field is
+ * written only for callers that say they have it */
+static int report_exit_margin = 0;
+void orc_report_exit_margin(int on) { report_exit_margin = on != 0; }
+
 int orc_fit(orc_problem* p, orc_fit_options* o, orc_fit_result* r) {
   int nd = p->n_datasets, na = p->n_active, np = p->n_pars;
   if (na == 0) FAIL("There are no active parameters.");
@@ -1070,6 +1075,7 @@ int orc_fit(orc_problem* p, orc_fit_options* o, orc_fit_result* r) {
          *old_pars = (double*)malloc(sizeof(double) * na * nd), *res = (double*)malloc(sizeof(double) * N),
          *JT = (double*)malloc(sizeof(double) * (size_t)N * dim);
   int rc = -1, iterations = 0;
+  double exit_margin = INFINITY;                                          /* orc_fit_result.min_exit_margin */
   if (o->DTD_min) for (int i = 0; i < dim; i++) DTD[i] = o->DTD_min[i];   /* GF:641-646 */
   int dof = (int)(N - dim);                                               /* GF:648-657 */
   if (dof < 0) { snprintf(g_err, sizeof g_err, "More independent fitting parameters than data points."); goto done; }
@@ -1079,6 +1085,8 @@ int orc_fit(orc_problem* p, orc_fit_options* o, orc_fit_result* r) {
   if (r) { r->n_sweeps = r->n_chi2 = r->n_omega = 0; r->dim = dim; r->dof = dof; r->exit_reason = -1; r->min_margin = INFINITY; }
   if (orc_chi2(p, P, &old_chi2, res)) goto done;                          /* GF:670 */
   if (r) r->n_chi2++;
+  /* the report orc_fit_result.min_exit_margin: |value - threshold| / |threshold| of a data-dependent comparison; nothing reads it */
+#define EXIT_MARGIN(value, threshold) do { double m_ = fabs((value) - (threshold)) / fabs(threshold); if (!(m_ >= exit_margin)) exit_margin = m_; } while (0)
 #define SOLVE(rhs_src, out) do { for (int q = 0; q < dim; q++) out[q] = rhs_src[q]; \
     for (int c = 0; c < dim; c++) for (int rr = 0; rr < dim; rr++) lin[(size_t)c * dim + rr] = JTJ[(size_t)c * dim + rr] + (rr == c ? lambda * DTD[c] : lambda * 0.0); \
     if (orc_potr(dim, lin, out)) goto done; } while (0)
@@ -1095,6 +1103,7 @@ int orc_fit(orc_problem* p, orc_fit_options* o, orc_fit_result* r) {
       if (r) r->n_omega++;
       SOLVE(JTomega, delta2);
       acc_ratio = sqrt(dtd_dot(dim, DTD, delta2, delta2) / dtd_dot(dim, DTD, delta1, delta1));
+      EXIT_MARGIN(acc_ratio, o->accth);
       if (acc_ratio > o->accth) for (int q = 0; q < dim; q++) delta2[q] = 0.0;
     }
     if (r && iterations == 0) {
@@ -1113,6 +1122,9 @@ int orc_fit(orc_problem* p, orc_fit_options* o, orc_fit_result* r) {
       if (r) { double m_ = fabs(new_chi2 - old_chi2) / old_chi2; if (!(m_ >= r->min_margin)) r->min_margin = m_; }
       if (iterations == 0) beta = 0.0;
       else beta = dtd_dot(dim, DTD, delta1, old_delta1) / sqrt(dtd_dot(dim, DTD, delta1, delta1)) / sqrt(dtd_dot(dim, DTD, old_delta1, old_delta1));
+      if (uphill != 0) EXIT_MARGIN(powi(1.0 - beta, uphill) * new_chi2, old_chi2);
+      /* both Umrigar-Nightingale branches switch on the sign of beta: its distance from zero, absolute */
+      if (o->has_umnigh && o->umnigh && iterations > 0 && !(fabs(beta) >= exit_margin)) exit_margin = fabs(beta);
       if (powi(1.0 - beta, uphill) * new_chi2 < old_chi2) {               /* GF:761 */
         if (o->has_nielsen && o->nielsen) {                               /* GF:762-767 */
           double q = 0;
@@ -1159,27 +1171,36 @@ int orc_fit(orc_problem* p, orc_fit_options* o, orc_fit_result* r) {
     old_chi2 = old_chi2 < new_chi2 ? old_chi2 : new_chi2;
     iterations++;
     /* STEP 5, GF:835-915 */
+    if (o->has_chi2_abs) EXIT_MARGIN(old_chi2 / dof, o->chi2_abs);
     if (o->has_chi2_abs && old_chi2 / dof < o->chi2_abs) { if (r) r->exit_reason = 1; break; }
+    if (o->has_chi2_rel) EXIT_MARGIN((old_old_chi2 - old_chi2) / old_chi2, o->chi2_rel);
     if (o->has_chi2_rel && (old_old_chi2 - old_chi2) / old_chi2 < o->chi2_rel) { if (r) r->exit_reason = 2; break; }
     if (o->has_grad_chi2) {                                               /* GF:848-860: res from last chi2(), old JT */
       double s = 0;
       for (int c = 0; c < dim; c++) { double g = 0; for (int64_t i = 0; i < N; i++) g += JT[(size_t)i * dim + c] * res[i]; JTres[c] = g; s += g * g; }
+      EXIT_MARGIN(2 * sqrt(s), o->grad_chi2);
       if (2 * sqrt(s) < o->grad_chi2) { if (r) r->exit_reason = 3; break; }
     }
     if (o->has_cos_phi) {                                                 /* GF:861-884 */
       double rj = 0, rr = 0, jj = 0;
       for (int64_t i = 0; i < N; i++) { double jd = 0; for (int c = 0; c < dim; c++) jd += JT[(size_t)i * dim + c] * delta1[c]; rj += res[i] * jd; rr += res[i] * res[i]; jj += jd * jd; }
+      EXIT_MARGIN(fabs(rj) / sqrt(rr) / sqrt(jj), o->cos_phi);
       if (fabs(rj) / sqrt(rr) / sqrt(jj) < o->cos_phi) { if (r) r->exit_reason = 4; break; }
     }
     if (o->has_rel_error) {                                               /* GF:885-898 */
       int all = 1;
-      for (int a = 0; a < nd && all; a++) for (int j = 0; j < na; j++)
+      for (int a = 0; a < nd && all; a++) for (int j = 0; j < na; j++) {
+        EXIT_MARGIN(fabs(delta1[jac[a * na + j]] / p->pars[a * np + p->active_pars[j]]), o->rel_error);
         if (fabs(delta1[jac[a * na + j]] / p->pars[a * np + p->active_pars[j]]) > o->rel_error) { all = 0; break; }
+      }
       if (all) { if (r) r->exit_reason = 5; break; }
     }
     if (o->has_rel_error_global) {                                        /* GF:899-910 */
       int any = 0;
-      for (int j = 0; j < na; j++) if (p->is_global[p->active_pars[j]] && fabs(delta1[jac[j]] / p->pars[p->active_pars[j]]) > o->rel_error_global) any = 1;
+      for (int j = 0; j < na; j++) if (p->is_global[p->active_pars[j]]) {
+        EXIT_MARGIN(fabs(delta1[jac[j]] / p->pars[p->active_pars[j]]), o->rel_error_global);
+        if (fabs(delta1[jac[j]] / p->pars[p->active_pars[j]]) > o->rel_error_global) any = 1;
+      }
       if (!any) { if (r) r->exit_reason = 6; break; }
     }
     if (o->has_max_iter && iterations >= o->max_iter) { if (r) r->exit_reason = 0; break; }  /* GF:911-915 */
@@ -1187,6 +1208,7 @@ int orc_fit(orc_problem* p, orc_fit_options* o, orc_fit_result* r) {
   rc = 0;
 done:
   if (r) { r->iterations = iterations; r->lambda = lambda; r->chi2 = old_chi2; }
+  if (r && report_exit_margin) r->min_exit_margin = exit_margin;
   free(jac); free(JTJ); free(JTres); free(DTD); free(delta1); free(delta2); free(old_delta1); free(lin);
   free(JTomega); free(old_pars); free(res); free(JT);
   return rc;

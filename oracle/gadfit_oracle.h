@@ -84,6 +84,13 @@ typedef struct orc_fit_result {
   /* the closest of the loop's decisions: min |new_chi2 - old_chi2| / old_chi2 over every STEP 4 comparison, accepted or rejected
      (inf if there was none); a report only, nothing in the loop reads it */
   double min_margin;
+  /* the closest of the loop's OTHER data-dependent comparisons, |value - threshold| / |threshold|: every STEP 5 test that was evaluated,
+     fired or not (rel_error, rel_error_global: every coordinate looked at); acc_ratio against accth; under uphill /= 0,
+     (1 - beta)**uphill * new_chi2 against old_chi2; under umnigh after the first iteration |beta| itself (absolute: both
+     Umrigar-Nightingale branches switch on its sign).  inf where nothing was compared; a report only, nothing in the loop reads it.
+     Written only after orc_report_exit_margin(1): the result was 8 bytes shorter before this field, and a caller that still holds
+     the shorter one is not written past its end */
+  double min_exit_margin;
 } orc_fit_result;
 
 const char* orc_last_error(void);
@@ -109,6 +116,9 @@ int orc_chi2(const orc_problem* p, int n_images, double* chi2, double* res_out);
 /* STEP 3 omega vector and J^T omega (gadfit.F90:715-735); delta1 length dim; JT (dim x N) from orc_sweep */
 int orc_omega(const orc_problem* p, const double* delta1, const double* JT, double* omega_out,
               double* JTomega);
+
+/* on != 0: the caller's orc_fit_result has min_exit_margin, and orc_fit fills it in (default 0: it leaves those bytes alone) */
+void orc_report_exit_margin(int on);
 
 /* The full gadf_fit (gadfit.F90:502-1035). */
 int orc_fit(orc_problem* p, orc_fit_options* o, orc_fit_result* r);
