@@ -175,6 +175,31 @@ class BatchCalls:
             held = self.batch_loss()          # (the library's own record: the one source of the setting)
             self.set_batch_loss(held[0] if loss is None else loss, held[1] if loss_scale is None else loss_scale)
 
+    # --- the estimator of a batch (gfh_set_batch_estimator) and what the last launch ran under
+    _ESTIMATORS = {'lsq': 0, 'poisson': 1}
+
+    def set_batch_estimator(self, estimator):
+        """what the batch calls minimise from here on (it stays set): 0 or 'lsq' the weighted sum of squares (the default), 1 or
+        'poisson' the Poisson deviance 2 sum [f - y + y ln(y / f)] over the points of non-zero weight, by Fisher scoring -- the
+        maximum-likelihood fit of counted data.  The deviance then stands wherever chi2 stood (the records, batch_pass's third output,
+        chi2_abs and chi2_rel, the factor of scale=True) and the covariance is the inverse Fisher matrix.  The data form's weight is a
+        mask there: a cube under this estimator wants error_type NONE -- any rule works as a mask, but SQRT_Y pays a sqrt and a
+        division per point for nothing.  Refused with a batch loss, with accth and for batch_eval's residuals -- gfh_set_batch_estimator"""
+        if isinstance(estimator, str):
+            if estimator not in self._ESTIMATORS:
+                raise GadfitHipError("set_batch_estimator: unknown estimator %r (0 or 'lsq': least squares, 1 or 'poisson')" % (estimator,))
+            estimator = self._ESTIMATORS[estimator]
+        self._chk(lib().gfh_set_batch_estimator(self._h, int(estimator)))
+
+    def batch_estimator(self):
+        """the estimator as set_batch_estimator left it; 0 until it is called -- gfh_get_batch_estimator"""
+        return int(lib().gfh_get_batch_estimator(self._h))
+
+    def batch_estimator_used(self):
+        """the estimator of the last batch launch that sweeps, None: none yet -- gfh_debug_batch_estimator"""
+        e = int(lib().gfh_debug_batch_estimator(self._h))
+        return None if e < 0 else e
+
     def batch_form_used(self):
         """the data form of the last batch launch: None (none yet), 'ragged', or ('cube', y_type, error_type) -- gfh_debug_batch_form"""
         f = int(lib().gfh_debug_batch_form(self._h))
@@ -202,7 +227,7 @@ class BatchCalls:
         if lanes_per_fit is not None:
             self.set_batch_lanes(lanes_per_fit)
 
-    def _batch_args(self, who, pars, active, lanes_per_fit, loss=None, loss_scale=None):
+    def _batch_args(self, who, pars, active, lanes_per_fit, loss=None, loss_scale=None, estimator=None):
         """a copy of pars as [n_fits][n_pars], the active set and n_fits of a call on every fit of the batch held"""
         n = self._n_held(who)
         p = np.ascontiguousarray(pars, dtype=np.float64).copy()
@@ -210,6 +235,8 @@ class BatchCalls:
         a = self._active(who, active)
         self._lanes(lanes_per_fit)
         self._loss(loss, loss_scale)
+        if estimator is not None:
+            self.set_batch_estimator(estimator)
         return p.reshape(n, self.n_pars), a, n
 
     def _batch_options(self, who, a, DTD_min, kw):
@@ -232,16 +259,17 @@ class BatchCalls:
             o.DTD_min = dp(dm)
         return o, dm
 
-    def fit_batch(self, pars, active, DTD_min=None, lanes_per_fit=None, loss=None, loss_scale=None, **kw):
+    def fit_batch(self, pars, active, DTD_min=None, lanes_per_fit=None, loss=None, loss_scale=None, estimator=None, **kw):
         """every spectrum of the batch fitted in one launch.  pars [n_fits][n_pars]; keyword arguments as fit(); lanes_per_fit: as
         set_batch_lanes (it stays set), None leaves the context's setting; loss, loss_scale: as set_batch_loss (they stay set), None
-        leaves the setting.  Returns the fitted parameters, a numpy record array of
+        leaves the setting; estimator: as set_batch_estimator (0 / 'lsq', 1 / 'poisson'; it stays set), None leaves the setting -- under
+        'poisson' a cube wants error_type NONE and the records' chi2 is the deviance.  Returns the fitted parameters, a numpy record array of
         BatchResult [n_fits] and the device time of the launch in seconds."""
-        return self._fit('fit_batch', pars, active, None, DTD_min, lanes_per_fit, kw, loss, loss_scale)
+        return self._fit('fit_batch', pars, active, None, DTD_min, lanes_per_fit, kw, loss, loss_scale, estimator)
 
-    def _fit(self, who, pars, active, scale, DTD_min, lanes_per_fit, kw, loss=None, loss_scale=None):
+    def _fit(self, who, pars, active, scale, DTD_min, lanes_per_fit, kw, loss=None, loss_scale=None, estimator=None):
         """fit_batch or fit_batch_errors (who): the same arguments, the second with scale and the error outputs behind them"""
-        p, a, n = self._batch_args(who, pars, active, lanes_per_fit, loss, loss_scale)
+        p, a, n = self._batch_args(who, pars, active, lanes_per_fit, loss, loss_scale, estimator)
         o, _keep = self._batch_options(who, a, DTD_min, kw)
         res = np.zeros(n, dtype=BATCH_RESULT_DTYPE)
         sec = C.c_double()
@@ -253,14 +281,15 @@ class BatchCalls:
         self._chk(lib().gfh_fit_batch_errors(*args, int(scale), dp(cov), dp(sigma), ip(info), C.cast(C.byref(sec), _dp)))
         return p, res.view(np.recarray), (cov, sigma, info), sec.value
 
-    def fit_batch_bounded(self, pars, active, lower, upper, DTD_min=None, lanes_per_fit=None, loss=None, loss_scale=None, **kw):
+    def fit_batch_bounded(self, pars, active, lower, upper, DTD_min=None, lanes_per_fit=None, loss=None, loss_scale=None, estimator=None, **kw):
         """fit_batch inside one box per batch: lower and upper hold one value per active parameter, in the order of `active`, -inf /
         +inf for no bound on that side.  Returns the fitted parameters, the records, at_bound [n_fits] (int32: bit j where the
         returned active parameter j equals lower[j], bit 8 + j where it equals upper[j]) and the device time of the launch in seconds.
         With no finite bound the parameters and records are fit_batch's bits; loss, loss_scale as fit_batch (under a loss a parameter
-        is pinned on the sign of the loss-scaled J^T r) -- gfh_fit_batch_bounded"""
+        is pinned on the sign of the loss-scaled J^T r); estimator as fit_batch (under 'poisson' the sign is that of sum g (y - f) / f; a
+        cube wants error_type NONE) -- gfh_fit_batch_bounded"""
         who = 'fit_batch_bounded'
-        p, a, n = self._batch_args(who, pars, active, lanes_per_fit, loss, loss_scale)
+        p, a, n = self._batch_args(who, pars, active, lanes_per_fit, loss, loss_scale, estimator)
         lo = np.ascontiguousarray(lower, dtype=np.float64); hi = np.ascontiguousarray(upper, dtype=np.float64)
         for name, v in (('lower', lo), ('upper', hi)):
             if v.ndim != 1 or v.size != a.size:
@@ -273,28 +302,32 @@ class BatchCalls:
                                               ip(at), C.cast(C.byref(sec), _dp)))
         return p, res.view(np.recarray), at, sec.value
 
-    def fit_batch_errors(self, pars, active, scale=False, DTD_min=None, lanes_per_fit=None, loss=None, loss_scale=None, **kw):
+    def fit_batch_errors(self, pars, active, scale=False, DTD_min=None, lanes_per_fit=None, loss=None, loss_scale=None, estimator=None, **kw):
         """fit_batch and, behind it on the device, each fit's parameter covariance at the fitted parameters: returns the fitted
         parameters, the records, (cov [n_fits][na][na], sigma [n_fits][na], info [n_fits]) as batch_covariance returns them and the
-        device time of the two launches in seconds.  The parameters and records are fit_batch's bits; loss, loss_scale as fit_batch
+        device time of the two launches in seconds.  The parameters and records are fit_batch's bits; loss, loss_scale and estimator as
+        fit_batch (under 'poisson' cov is the inverse Fisher matrix, under scale=True times deviance / dof; a cube wants error_type NONE)
         -- gfh_fit_batch_errors"""
-        return self._fit('fit_batch_errors', pars, active, scale, DTD_min, lanes_per_fit, kw, loss, loss_scale)
+        return self._fit('fit_batch_errors', pars, active, scale, DTD_min, lanes_per_fit, kw, loss, loss_scale, estimator)
 
-    def batch_covariance(self, pars, active, scale=False, lanes_per_fit=None, loss=None, loss_scale=None):
+    def batch_covariance(self, pars, active, scale=False, lanes_per_fit=None, loss=None, loss_scale=None, estimator=None):
         """(cov [n_fits][na][na], sigma [n_fits][na], info [n_fits]) of every spectrum at pars [n_fits][n_pars]: cov = (J^T J)^-1
         (the reference's LMsolver::getInvJTJ), under scale=True times the fit's chi2 / dof; sigma = sqrt of its diagonal; info 0, or
         j + 1 where pivot j of the Cholesky factor failed (that fit's cov and sigma are NaN).  Rows and columns in the order of
         `active`; lanes_per_fit, loss and loss_scale as fit_batch: under a loss J is the loss-scaled Jacobian and the chi2 of
-        scale=True stays the plain one -- gfh_batch_covariance"""
-        p, a, n = self._batch_args('batch_covariance', pars, active, lanes_per_fit, loss, loss_scale)
+        scale=True stays the plain one; estimator as fit_batch: under 'poisson' J^T J is the Fisher matrix sum g g^T / f and scale=True
+        multiplies by deviance / dof (a cube wants error_type NONE) -- gfh_batch_covariance"""
+        p, a, n = self._batch_args('batch_covariance', pars, active, lanes_per_fit, loss, loss_scale, estimator)
         cov, sigma, info = _error_outputs(n, a.size)
         self._chk(lib().gfh_batch_covariance(self._h, dp(p), a.size, ip(a), int(scale), dp(cov), dp(sigma), ip(info)))
         return cov, sigma, info
 
-    def batch_pass(self, pars, active, lanes_per_fit=None, loss=None, loss_scale=None):
+    def batch_pass(self, pars, active, lanes_per_fit=None, loss=None, loss_scale=None, estimator=None):
         """(JTJ [n_fits][na][na], JTres [n_fits][na], chi2 [n_fits]) of every spectrum at pars [n_fits][n_pars] -- gfh_batch_pass;
-        lanes_per_fit, loss and loss_scale as fit_batch (under a loss JTJ and JTres are the loss-scaled sums, chi2 the plain one)"""
-        p, a, n = self._batch_args('batch_pass', pars, active, lanes_per_fit, loss, loss_scale)
+        lanes_per_fit, loss and loss_scale as fit_batch (under a loss JTJ and JTres are the loss-scaled sums, chi2 the plain one);
+        estimator as fit_batch: under 'poisson' JTJ = sum g g^T / f, JTres = sum g (y - f) / f and the third output is the deviance (a
+        cube wants error_type NONE)"""
+        p, a, n = self._batch_args('batch_pass', pars, active, lanes_per_fit, loss, loss_scale, estimator)
         JTJ = np.zeros((n, a.size, a.size)); JTr = np.zeros((n, a.size)); chi2 = np.zeros(n)
         self._chk(lib().gfh_batch_pass(self._h, dp(p), a.size, ip(a), dp(JTJ), dp(JTr), dp(chi2)))
         return JTJ, JTr, chi2

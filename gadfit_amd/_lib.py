@@ -125,6 +125,9 @@ SYMBOLS = {
     'gfh_set_batch_loss': (_i, [_vp, _i, C.c_double]),
     'gfh_debug_batch_loss': (_i, [_vp, _dp]),
     'gfh_get_batch_loss': (_i, [_vp, _dp]),
+    'gfh_set_batch_estimator': (_i, [_vp, _i]),
+    'gfh_get_batch_estimator': (_i, [_vp]),
+    'gfh_debug_batch_estimator': (_i, [_vp]),
     'gfh_set_batch_cube': (_i, [_vp, _i64, _i64, _dp, _vp, _i, _i, _dp]),
     'gfh_debug_batch_form': (_i, [_vp]),
     'gfh_batch_frames_begin': (_i, [_vp, _i64, _i64, _dp, _i, _i]),

@@ -53,6 +53,8 @@ int check_batchable(gfh_ctx* c, const char* who, int na, const int32_t* active) 
   if (c->pars_fn) return fail(c, w + ": a pars hook (gfh_set_pars_hook) cannot run inside a device-resident loop");
   if (c->gen.loss != 0) return fail(c, w + ": a robust loss (gfh_set_loss) is not carried by the batch kernels: a batch takes its loss and residual scale from gfh_set_batch_loss");
   if (c->gen.finite_diff) return fail(c, w + ": use_ad = 0 (finite differences) is not carried by the batch kernels");
+  if (c->batch.estimator != 0 && c->batch.loss != 0)
+    return fail(c, w + ": the poisson estimator (gfh_set_batch_estimator) together with a batch loss (gfh_set_batch_loss) is not carried: the robust costs are costs of a weighted residual, which the deviance has none of");
   if (na < 1) return fail(c, "There are no active parameters.");                                       // gadfit.F90:602-603
   if (na > kValuGramMax) return fail(c, w + ": more than " + std::to_string(kValuGramMax) + " active parameters per fit");
   if (!active) return fail(c, w + ": null argument");
@@ -86,6 +88,7 @@ GenConfig batch_config(const gfh_ctx* c, int lanes, bool bounded) {
   cfg.batch_bounded = bounded;      // gfh_k_fit_batch_bounded in place of the four kernels: a unit of its own
   cfg.batch_loss = c->batch.loss;   // gfh_set_batch_loss: the batch's own setting (cfg.loss, the plain units' GFH_LOSS, stays 0); the scale is a kernel argument
   cfg.batch_cube = c->batch.cube;   // the data form held: a cube's sample type and weight rule are part of the text (batch_cube.hip)
+  cfg.batch_estimator = c->batch.estimator;      // gfh_set_batch_estimator: likewise part of the text
   if (c->batch.cube) { cfg.batch_y_type = c->batch.y_type; cfg.batch_error_type = c->batch.error_type; }
   return cfg;
 }
@@ -100,6 +103,7 @@ int batch_kernels(gfh_ctx* c, const std::vector<int32_t>& active, int lanes, boo
   key.push_back(lanes);             // both forms of one active set can be resident
   if (c->batch.cube) key.push_back(data_form(c));      // ... and so can its cube forms beside the ragged one (whose key stays what it was)
   if (c->batch.loss) key.push_back(-(1 << 29) - c->batch.loss);      // ... and its loss units beside the linear one (no lane count and no data form is negative)
+  if (c->batch.estimator) key.push_back(-(1 << 28) - c->batch.estimator);      // ... and its Poisson units beside the least-squares ones
   auto it = c->kernel_cache.find(key);
   if (it != c->kernel_cache.end()) { if (out) *out = &it->second; return 0; }
   std::string src, err;
@@ -143,7 +147,7 @@ int launch_batch(gfh_ctx* c, hipFunction_t kernel, int lanes, int64_t n, std::in
   const int per_wg = 256 / lanes;
   HIPCHK(c, hipModuleLaunchKernel(kernel, (unsigned)((n + per_wg - 1) / per_wg), 1, 1, 256, 1, 1, 0, c->stream, args.data(), nullptr));
   c->batch.last_lanes = lanes; c->batch.last_form = data_form(c);
-  if (sweeps) { c->batch.last_loss = c->batch.loss; c->batch.last_loss_scale = c->batch.loss_scale; }
+  if (sweeps) { c->batch.last_loss = c->batch.loss; c->batch.last_loss_scale = c->batch.loss_scale; c->batch.last_estimator = c->batch.estimator; }
   return 0;
 }
 
@@ -187,6 +191,8 @@ int batch_options(gfh_ctx* c, const std::string& who, const gfh_fit_options* o, 
   LmOptions lo;
   if (const char* refusal = resolve_lm_options(*o, &lo)) return fail(c, refusal);                        // gadfit.F90:575-578
   if (!o->has_max_iter || o->max_iter < 0) return fail(c, who + ": max_iter is required (a loop that runs on the device must be bounded)");
+  if (c->batch.estimator != 0 && lo.use_accth)
+    return fail(c, who + ": accth (geodesic acceleration) is not carried under the poisson estimator (gfh_set_batch_estimator): STEP 3's second derivative is that of the least-squares cost");
   BatchOpts bo; memset(&bo, 0, sizeof bo);
   bo.lambda = lo.lambda; bo.lam_up = lo.lam_up; bo.lam_down = lo.lam_down; bo.lam_incs = lo.lam_incs;      // gadfit.F90:568-584 (lm_options.h)
   bo.use_accth = lo.use_accth; bo.accth = o->accth;
@@ -391,6 +397,8 @@ int gfh_batch_eval(gfh_ctx* c, const double* pars, int na, const int32_t* active
   if (!pars) return fail(c, "gfh_batch_eval: null argument (pars is required)");
   if (!model && !residual && !band) return fail(c, "gfh_batch_eval: no output requested (model, residual and band are all NULL)");
   if (band && !cov) return fail(c, "gfh_batch_eval: a band needs the fits' covariances (cov is NULL)");
+  if (residual && c->batch.estimator != 0)
+    return fail(c, "gfh_batch_eval: the weighted residual has no meaning under the poisson estimator (gfh_set_batch_estimator): the data form's weight is a mask there; model and band are given");
   if (residual && x_eval) return fail(c, "gfh_batch_eval: a residual on a caller's grid has no meaning (residual is given on the fits' own points alone)");
   if (x_eval && n_eval < 1) return fail(c, "gfh_batch_eval: a grid holds at least one point (x_eval given with n_eval = " + std::to_string((long long)n_eval) + ")");
   if (!x_eval && n_eval != 0) return fail(c, "gfh_batch_eval: n_eval = " + std::to_string((long long)n_eval) + " without x_eval (NULL, 0: the fits' own points)");
@@ -492,6 +500,21 @@ int gfh_debug_batch_loss(gfh_ctx* c, double* scale) {
   if (scale) *scale = c->batch.last_loss_scale;
   return c->batch.last_loss;
 }
+
+// What the batch kernels minimise from here on (it stays set, as gfh_set_batch_loss): 0 the weighted sum of squares (the default, and
+// what a batch was before this setting), 1 the Poisson deviance 2 sum [f - y + y ln(y / f)] over the points of non-zero weight, by
+// Fisher scoring (device/batch_fit.hip, GFH_BMLE).  Part of the batch unit's text.  A setting, not a launch: needs no GPU and no model.
+int gfh_set_batch_estimator(gfh_ctx* c, int estimator) try {
+  if (check_context(c, "gfh_set_batch_estimator")) return 1;
+  if (estimator != GFH_ESTIMATOR_LSQ && estimator != GFH_ESTIMATOR_POISSON)
+    return fail(c, "gfh_set_batch_estimator: unknown estimator " + std::to_string(estimator) + " (0: least squares, 1: poisson)");
+  c->batch.estimator = estimator;
+  return 0;
+} catch (const std::exception& e) { return fail(c, std::string("gfh_set_batch_estimator: ") + e.what()); }
+// The setting itself (-1: no context)
+int gfh_get_batch_estimator(gfh_ctx* c) { return c ? c->batch.estimator : -1; }
+// The estimator that the last sweeping batch launch of this context ran under (-1: none yet)
+int gfh_debug_batch_estimator(gfh_ctx* c) { return c ? c->batch.last_estimator : -1; }
 
 // The form of the last batch launch of this context (64, 16 or 256; 0: none yet), so that a test asserts the dispatch.
 int gfh_debug_batch_lanes(gfh_ctx* c) { return c ? c->batch.last_lanes : 0; }

@@ -65,17 +65,20 @@ static std::string coop_defines(int NA) {
 // A file of the batch text with its `#if GFH_BLOSS` / `#else  // GFH_BLOSS` / `#endif  // GFH_BLOSS` lines resolved HERE, not by the
 // preprocessor: the three directives (whole lines, exactly these) and the arm not taken are left out, so a linear unit is the text it
 // was before a batch had a loss and a loss unit reads as straight as that one.  The regions do not nest; any other directive passes through.
-static std::string resolve_batch_loss(const char* text, bool loss) {
+// The estimator's regions (`macro` GFH_BMLE, GenConfig::batch_estimator) are resolved by a second walk over the result of the first: they
+// stand outside the loss's regions or inside their linear arms, which a loss unit has dropped by then, directives and all.
+static std::string resolve_batch_loss(const char* text, bool loss, const char* macro = "GFH_BLOSS") {
   std::string out; out.reserve(strlen(text));
+  const std::string m_if = std::string("#if ") + macro + "\n", m_else = std::string("#else  // ") + macro + "\n", m_endif = std::string("#endif  // ") + macro + "\n";
   int arm = 0;                      // 0 outside a region, 1 in its loss arm, 2 in its linear arm
   for (const char* p = text; *p;) {
     const char* e = strchr(p, '\n');
     const size_t n = e ? (size_t)(e - p) + 1 : strlen(p);
     const std::string line(p, n);
     p += n;
-    if (line == "#if GFH_BLOSS\n") { arm = 1; continue; }
-    if (arm && line == "#else  // GFH_BLOSS\n") { arm = 2; continue; }
-    if (arm && line == "#endif  // GFH_BLOSS\n") { arm = 0; continue; }
+    if (line == m_if) { arm = 1; continue; }
+    if (arm && line == m_else) { arm = 2; continue; }
+    if (arm && line == m_endif) { arm = 0; continue; }
     if (arm == 0 || (arm == 1) == loss) out += line;
   }
   return out;
@@ -93,18 +96,23 @@ static bool emit_batch_kernels(const Model& m, const std::vector<int32_t>& activ
   if (cfg.batch_loss < 0 || cfg.batch_loss > 2) { *err = "batch kernels: batch_loss is 0 (linear), 1 (cauchy) or 2 (huber)"; return false; }
   const bool loss = cfg.batch_loss != 0;
   if (loss) s << "#define GFH_BLOSS " << cfg.batch_loss << "\n";      // in the text of the loss units alone
+  if (cfg.batch_estimator < 0 || cfg.batch_estimator > 1) { *err = "batch kernels: batch_estimator is 0 (least squares) or 1 (poisson)"; return false; }
+  const bool mle = cfg.batch_estimator != 0;
+  if (mle && loss) { *err = "batch kernels: the poisson estimator is not carried under a loss"; return false; }
+  if (mle) s << "#define GFH_BMLE " << cfg.batch_estimator << "\n";   // in the text of the Poisson units alone
+  const auto resolve = [&](const char* text) { return resolve_batch_loss(resolve_batch_loss(text, loss).c_str(), mle, "GFH_BMLE"); };
   if (cfg.batch_cube) {             // batch_cube.hip: the data form and the load of a cube, in the text of the cube forms alone
     if (cfg.batch_y_type < 0 || cfg.batch_y_type > 2 || cfg.batch_error_type < 0 || cfg.batch_error_type > 4) { *err = "batch kernels: a cube's y_type is 0 ... 2, its error_type 0 ... 4"; return false; }
     s << "#define GFH_BCUBE 1\n#define GFH_BYTYPE " << cfg.batch_y_type << "\n#define GFH_BERR " << cfg.batch_error_type << "\n" << kBatchCube;
   }
   if (cfg.batch_lanes == 256) s << kBatchWgSum;          // batch_wg_sum.hip: LDS and a barrier, in the text of the workgroup form alone
-  s << resolve_batch_loss(kBatchFit, loss);                   // batch_fit.hip: the passes and the solve of a fit, written once against GFH_BLANES
+  s << resolve(kBatchFit);                               // batch_fit.hip: the passes and the solve of a fit, written once against GFH_BLANES
   if (cfg.batch_bounded) {          // the bounded unit: gfh_k_fit_batch_bounded alone behind them (batch_fit_bounded.hip)
-    s << resolve_batch_loss(kBatchFitBounded, loss);
+    s << resolve(kBatchFitBounded);
     return true;
   }
-  s << resolve_batch_loss(kBatchFitKernels, loss);            // batch_fit_kernels.hip: gfh_k_fit_batch, gfh_k_batch_pass
-  s << resolve_batch_loss(kBatchCov, loss);                   // batch_cov.hip: gfh_k_batch_cov, behind them in every form
+  s << resolve(kBatchFitKernels);                 // batch_fit_kernels.hip: gfh_k_fit_batch, gfh_k_batch_pass
+  s << resolve(kBatchCov);                               // batch_cov.hip: gfh_k_batch_cov, behind them in every form
   s << kBatchEval;                  // batch_eval.hip: gfh_k_batch_eval, behind that
   return true;
 }

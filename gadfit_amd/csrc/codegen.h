@@ -40,6 +40,9 @@ struct GenConfig {
   int batch_loss = 0;     // ... the loss of a batch (gfh_set_batch_loss): 0 linear, 1 cauchy, 2 huber.  Non-zero: `#define GFH_BLOSS <n>` in front of the
                           // batch text, whose kernels then take inv_c = 1 / scale as one more argument; the scale is no part of the text.  The
                           // text of a linear unit does not change by a byte.  `loss` above (GFH_LOSS of the plain units) stays 0 in a batch unit
+  int batch_estimator = 0; // ... what a batch minimises (gfh_set_batch_estimator): 0 the weighted sum of squares, 1 the Poisson deviance by Fisher
+                          // scoring.  Non-zero: `#define GFH_BMLE 1` in front of the batch text and the GFH_BMLE arms of batch_fit.hip, chosen by the
+                          // generator as the loss's are; refused together with batch_loss.  The text of a least-squares unit does not change by a byte
   bool eval = false;      // the curves of a plain fit (eval.cpp): behind the point functions stand gfh_k_eval / gfh_k_eval_band and, for models a
                           // grid carries, gfh_k_eval_grid / gfh_k_eval_grid_band (eval.hip) INSTEAD of the kernels of a fit.  A translation
                           // unit of its own once more: the default one does not change by a byte

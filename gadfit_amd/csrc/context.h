@@ -197,6 +197,8 @@ struct gfh_ctx {
     double loss_scale = 1.0;        // ... and the residual scale c of it (the loss switches at |r| = c); the kernels take 1 / c as an argument
     int last_loss = -1;             // the loss and scale of the last batch launch that carries one (gfh_debug_batch_loss); -1: none yet
     double last_loss_scale = 0.0;
+    int estimator = 0;              // gfh_set_batch_estimator: 0 least squares, 1 the Poisson deviance by Fisher scoring -- part of the unit's text, as the loss
+    int last_estimator = -1;        // ... of the last batch launch that sweeps (gfh_debug_batch_estimator); -1: none yet
     // gfh_set_batch_cube: every spectrum on one grid.  x holds the grid [n_points], y the samples [n_fits][n_points] in y_type
     // (0 double, 1 float, 2 uint16_t), w the weights under error_type 4 (USER) alone, off stays empty (min_points = max_points = n_points)
     bool cube = false;

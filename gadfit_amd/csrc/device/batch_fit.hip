@@ -103,6 +103,22 @@ static __device__ __forceinline__ double gfh_b_ls(const double r, const double i
 #endif
 }
 #endif  // GFH_BLOSS
+#if GFH_BMLE
+// The estimator of a batch (GenConfig::batch_estimator, gfh_set_batch_estimator; DESIGN section 3a, Estimator of a batch).  The lines
+// between `#if GFH_BMLE`, `#else  // GFH_BMLE` and `#endif  // GFH_BMLE` are chosen by the GENERATOR as the loss's are (codegen.cpp,
+// resolve_batch_loss), not by the preprocessor: a least-squares unit holds the #else arms alone and none of these lines.
+// GFH_BMLE 1: the Poisson maximum-likelihood fit.  What the loop minimises is the deviance D = 2 sum [f - y + y ln(y / f)] over the
+// points with w != 0 (the data form's weight is a mask here and nothing more), by Fisher scoring: the sweep's weight is
+// m / sqrt(f(P)), m = (w != 0), so J^T J = sum g g^T / f and J^T r = sum g (y - f) / f, and the sweep's last sum and gfh_b_chi2 are D.
+// One term of D: 2 f at y = 0; NaN where f <= 0, y < 0 or an operand is not finite (a NaN deviance is a rejected trial, and a fit that
+// starts with one ends with reason 8); an exact +0.0 at a masked point and in the padding lanes, which re-read the last point with w = 0.
+static __device__ __forceinline__ double gfh_b_dev(const double y, const double f, const double w) {
+#pragma clang fp contract(off)
+  const bool ok = f > 0.0 && f < __builtin_inf() && y >= 0.0 && y < __builtin_inf();
+  const double t = y == 0.0 ? 2.0 * f : 2.0 * ((f - y) + y * log(y / f));
+  return w != 0.0 ? (ok ? t : __builtin_nan("")) : 0.0;
+}
+#endif  // GFH_BMLE
 
 #if GFH_BLOSS
 // STEP 1 + 2 (gadfit.F90:675-699) of one fit under a loss: S = [J^T J upper triangle, packed | J^T r | sum r^2], J and the r of J^T r
@@ -132,13 +148,26 @@ static __device__ __forceinline__ void gfh_b_sweep(const gfh_bdata& d, const dou
       R = r * ls; Wl = Wc * ls;
     }
 #else  // GFH_BLOSS
+#if GFH_BMLE
+    double R, Wf;                                              // Fisher scoring: the pass at weights m / sqrt(f(P))
+    {
+#pragma clang fp contract(off)
+      Wf = (Wc != 0.0 ? 1.0 : 0.0) / __builtin_sqrt(F);        // (a per-lane select and factor inside the point loop: no barrier here)
+      R = (Yc - F) * Wf;                                       // gadfit.F90:682-683
+    }
+#else  // GFH_BMLE
     const double R = (Yc - F) * Wc;                            // gadfit.F90:682-683
+#endif  // GFH_BMLE
 #endif  // GFH_BLOSS
 #pragma unroll
 #if GFH_BLOSS
     for (int a = 0; a < GFH_NA; a++) G[a] = G[a] * Wl;         // gadfit.F90:689-690, lm_solver.cpp:303-317
 #else  // GFH_BLOSS
+#if GFH_BMLE
+    for (int a = 0; a < GFH_NA; a++) G[a] = G[a] * Wf;         // gadfit.F90:689-690
+#else  // GFH_BMLE
     for (int a = 0; a < GFH_NA; a++) G[a] = G[a] * Wc;         // gadfit.F90:689-690
+#endif  // GFH_BMLE
 #endif  // GFH_BLOSS
     int p = 0;
 #pragma unroll
@@ -150,7 +179,11 @@ static __device__ __forceinline__ void gfh_b_sweep(const gfh_bdata& d, const dou
 #if GFH_BLOSS
     av[GFH_BNP + GFH_NA] += r * r;
 #else  // GFH_BLOSS
+#if GFH_BMLE
+    av[GFH_BNP + GFH_NA] += gfh_b_dev(Yc, F, Wc);              // the deviance in the place of sum r^2
+#else  // GFH_BMLE
     av[GFH_BNP + GFH_NA] += R * R;
+#endif  // GFH_BMLE
 #endif  // GFH_BLOSS
     Xc = Xn; Yc = Yn; Wc = Wn;
   }
@@ -168,8 +201,12 @@ static __device__ __forceinline__ double gfh_b_chi2(const gfh_bdata& d, const do
   for (i64 i0 = d.b; i0 < d.e; i0 += GFH_BLANES) {
     double Xn, Yn, Wn;
     GFH_BLOAD(Xn, Yn, Wn, i0 + GFH_BLANES < d.e ? i0 + GFH_BLANES : i0)
+#if GFH_BMLE
+    acc += gfh_b_dev(Yc, gfh_point_value(Xc, P, status, (const double*)nullptr, 0 GFH_MESH_NONE GFH_SLOT(i0 + d.lane)), Wc);   // the deviance in the place of chi2
+#else  // GFH_BMLE
     const double r = (Yc - gfh_point_value(Xc, P, status, (const double*)nullptr, 0 GFH_MESH_NONE GFH_SLOT(i0 + d.lane))) * Wc;   // gadfit.F90:1024-1026
     acc += r * r;
+#endif  // GFH_BMLE
     Xc = Xn; Yc = Yn; Wc = Wn;
   }
 #if GFH_BLANES == 256

@@ -74,6 +74,10 @@ static __device__ __forceinline__ bool gfh_b_solve_pinned(const double (&S)[GFH_
 // holds no barrier, and its ok is (S) as gfh_b_solve's; gfh_b_clamp selects among P + delta (S) and box (K), so the trial points
 // that gfh_b_chi2 is called at, and new_chi2 < old_chi2 behind it, stay (S); the rel_error exit tests P (S) against box (K);
 // at_bound is written behind the loop under d.lane == 0, which encloses no barrier.  No per-lane value enters any of them.
+#if GFH_BMLE
+// Under the Poisson estimator (GFH_BMLE) rule 1 pins on the sign of the sweep's J^T r = sum g (y - f) / f, minus half the gradient of
+// the deviance, and everything else is the rule unchanged; the start with a NaN deviance ends with reason 8 as in gfh_k_fit_batch.
+#endif  // GFH_BMLE
 #if GFH_BLOSS
 // Under a loss (GFH_BLOSS) rule 1 pins on the sign of the sweep's loss-scaled J^T r -- the gradient of the cost the step descends --
 // and everything else is the rule unchanged.  inv_c (K) reaches only the point loops of gfh_b_sweep and gfh_b_omega, which hold no barrier.
@@ -102,6 +106,10 @@ void gfh_k_fit_batch_bounded(GFH_BARGS, double* __restrict__ pars, const gfh_bat
   GFH_BIMG_INIT
   double old_chi2 = gfh_b_chi2(d, P, status GFH_BIMG), new_chi2 = 0.0, old_old_chi2 = 0.0;             // gadfit.F90:670
   n_chi2++;
+#if GFH_BMLE
+  if (!(old_chi2 == old_chi2)) exit_reason = 8;      // the first deviance is NaN: as gfh_k_fit_batch
+  else
+#endif  // GFH_BMLE
   for (;;) {
 #if GFH_BLOSS
     gfh_b_sweep(d, P, status, S, inv_c GFH_BIMG);                                              // STEP 1 + 2, gadfit.F90:675-701

@@ -20,6 +20,13 @@
 // and on the lane inside gfh_b_sum_n enclose no barrier.  Lane 0 of wave 0 writes the parameters and the record.
 // The cube's load (batch_cube.hip) adds only per-lane values -- the sample converted to double and the weight formed from it -- and
 // none of them enters a branch that encloses a barrier: its selects (the threshold of SQRT_Y / PROPTO_Y, the clamp) sit inside GFH_BLOAD.
+#if GFH_BMLE
+// Under the Poisson estimator (GFH_BMLE; batch_fit.hip, gfh_b_dev) the arm adds only per-lane selects (w != 0, y == 0, the NaN of a
+// term that has no value) and per-lane factors (1 / sqrt(f), the log) inside the point loops of gfh_b_sweep and gfh_b_chi2, which hold
+// no barrier; what leaves those loops still goes through gfh_b_sum_n, so S and the deviance stay (S) and no per-lane value enters a
+// branch that encloses a barrier.  The one new branch, a fit that STARTS with a NaN deviance ends with reason 8 in front of the loop,
+// tests old_chi2 (S): the four waves skip the loop together.
+#endif  // GFH_BMLE
 #if GFH_BLOSS
 // Under a loss (GFH_BLOSS; batch_fit.hip, gfh_b_ls) the kernels take inv_c = 1 / scale (K) behind their own arguments.  The loss adds
 // per-lane selects (Huber's u^2 > 1) and per-lane factors inside the point loops of gfh_b_sweep and gfh_b_omega, which hold no barrier;
@@ -50,6 +57,10 @@ void gfh_k_fit_batch(GFH_BARGS, double* __restrict__ pars, const gfh_batch_opts 
   GFH_BIMG_INIT
   double old_chi2 = gfh_b_chi2(d, P, status GFH_BIMG), new_chi2 = 0.0, old_old_chi2 = 0.0;             // gadfit.F90:670
   n_chi2++;
+#if GFH_BMLE
+  if (!(old_chi2 == old_chi2)) exit_reason = 8;      // the first deviance is NaN (f <= 0, y < 0 or not finite): nothing to descend from
+  else
+#endif  // GFH_BMLE
   for (;;) {
 #if GFH_BLOSS
     gfh_b_sweep(d, P, status, S, inv_c GFH_BIMG);                                              // STEP 1 + 2, gadfit.F90:675-701

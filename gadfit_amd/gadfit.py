@@ -343,6 +343,16 @@ def _batch_loss(who, loss, loss_scale):
     return int(loss), float(scale)
 
 
+def _batch_estimator(who, estimator):
+    """the ``estimator`` argument of the batch calls as set_batch_estimator takes it: None is least squares, so that every call sets
+    the estimator itself and nothing stays behind from an earlier one"""
+    if estimator is None:
+        return 0
+    if isinstance(estimator, bool) or estimator not in (0, 1, 'lsq', 'poisson'):
+        raise GadfitError("%s: estimator must be None, 0 or 'lsq' (least squares), 1 or 'poisson', got %r" % (who, estimator))
+    return {'lsq': 0, 'poisson': 1}.get(estimator, estimator) if isinstance(estimator, str) else int(estimator)
+
+
 def _batch_fit(pars, active, scale, bounds, **kw):
     """fit_batch, fit_batch_errors under errors= or fit_batch_bounded under bounds=: what the batch calls return"""
     if bounds is not None:
@@ -357,7 +367,7 @@ def _batch_fit(pars, active, scale, bounds, **kw):
 
 def gadf_fit_batch(xs, ys, ws, pars, lambda_=None, lam_up=None, lam_down=None, accth=None, rel_error=None, chi2_rel=None,
                    chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, lanes_per_fit=None, errors=None, bounds=None,
-                   loss=None, loss_scale=None, **kw):
+                   loss=None, loss_scale=None, estimator=None, **kw):
     """Many independent fits of the session's model in one kernel launch (gfh_fit_batch): gadf_fit's loop (gadfit.F90:670-915) per
     spectrum, each with its own data, start parameters, lambda history and exit.  On a session initialised with one dataset slot
     (``gadf_init(f)``); the active set is the one ``gadf_set`` left.  ``xs, ys, ws``: one array per spectrum (``ws``: the weights as
@@ -374,8 +384,13 @@ def gadf_fit_batch(xs, ys, ws, pars, lambda_=None, lam_up=None, lam_down=None, a
     [n_fits] (bit j: the returned active parameter j equals lower[j], bit 8 + j: upper[j]).  ``bounds`` with ``errors`` is refused.
     ``loss``: None or LOSS_LINEAR, LOSS_CAUCHY, LOSS_HUBER -- the batch's own robust cost (gfh_set_batch_loss), set by this call for this
     call -- and ``loss_scale`` the weighted residual |(y - f) w| at which it switches (None: 1, the reference's costs); the steps are
-    accepted on the plain chi2, which is also the records'.  The session's ``gadf_set_loss`` is the plain fit's and stays refused here."""
+    accepted on the plain chi2, which is also the records'.  The session's ``gadf_set_loss`` is the plain fit's and stays refused here.
+    ``estimator``: None, 0 or 'lsq' for least squares, 1 or 'poisson' for the Poisson maximum-likelihood fit of counted data
+    (gfh_set_batch_estimator), set by this call for this call: the loop minimises the deviance 2 sum [f - y + y ln(y / f)] over the points
+    of non-zero weight by Fisher scoring, ``ws`` is a mask and nothing more, the records' chi2 is the deviance, ``errors`` gives the
+    inverse Fisher matrix ('scaled': times deviance / dof).  Refused with ``loss`` and with ``accth``."""
     _need_init()
+    batch_estimator = _batch_estimator('gadf_fit_batch', estimator)
     batch_loss = _batch_loss('gadf_fit_batch', loss, loss_scale)
     scale = _batch_errors('gadf_fit_batch', errors)
     bounds = _batch_bounds('gadf_fit_batch', bounds, errors)
@@ -400,7 +415,7 @@ def gadf_fit_batch(xs, ys, ws, pars, lambda_=None, lam_up=None, lam_down=None, a
     np.cumsum([v.size for v in xs], out=off[1:])
     try:
         _S.ctx.set_batch_data(off, np.concatenate(xs), np.concatenate(ys), np.concatenate(ws))
-        return _batch_fit(pars, active, scale, bounds, DTD_min=DTD_min, lanes_per_fit=lanes_per_fit, loss=batch_loss[0], loss_scale=batch_loss[1], lambda_=_f32(lambda_), lam_up=_f32(lam_up), lam_down=_f32(lam_down),
+        return _batch_fit(pars, active, scale, bounds, DTD_min=DTD_min, lanes_per_fit=lanes_per_fit, loss=batch_loss[0], loss_scale=batch_loss[1], estimator=batch_estimator, lambda_=_f32(lambda_), lam_up=_f32(lam_up), lam_down=_f32(lam_down),
                           accth=_f32(accth), rel_error=_f32(rel_error), chi2_rel=_f32(chi2_rel), chi2_abs=_f32(chi2_abs),
                           lam_incs=lam_incs, max_iter=max_iter, damp_max=None if damp_max is None else int(damp_max),
                           **{k: v for k, v in kw.items() if v is not None})
@@ -408,9 +423,10 @@ def gadf_fit_batch(xs, ys, ws, pars, lambda_=None, lam_up=None, lam_down=None, a
         raise GadfitError(str(e))
 
 
-def _fit_cube(who, frames, x, Y, pars, sigma, DTD_min, lanes_per_fit, frames_per_put, errors, bounds, loss, loss_scale, kw):
+def _fit_cube(who, frames, x, Y, pars, sigma, DTD_min, lanes_per_fit, frames_per_put, errors, bounds, loss, loss_scale, estimator, kw):
     """gadf_fit_cube and gadf_fit_frames: one body, the data spectrum-major (Y [n_fits][n_points]) or frame-major (F [n_points][n_fits])"""
     _need_init()
+    batch_estimator = _batch_estimator(who, estimator)
     batch_loss = _batch_loss(who, loss, loss_scale)
     scale = _batch_errors(who, errors)
     bounds = _batch_bounds(who, bounds, errors)
@@ -444,7 +460,7 @@ def _fit_cube(who, frames, x, Y, pars, sigma, DTD_min, lanes_per_fit, frames_per
             _S.ctx.set_batch_frames(x, Y, _S.error_type, None if sigma is None else 1.0 / sigma, frames_per_put)
         else:
             _S.ctx.set_batch_cube(x, Y, _S.error_type, None if sigma is None else 1.0 / sigma)
-        return _batch_fit(pars, active, scale, bounds, DTD_min=DTD_min, lanes_per_fit=lanes_per_fit, loss=batch_loss[0], loss_scale=batch_loss[1], **kw)
+        return _batch_fit(pars, active, scale, bounds, DTD_min=DTD_min, lanes_per_fit=lanes_per_fit, loss=batch_loss[0], loss_scale=batch_loss[1], estimator=batch_estimator, **kw)
     except _lib.GadfitHipError as e:
         raise GadfitError(str(e))
 
@@ -459,26 +475,29 @@ def _cube_fit_args(lambda_, lam_up, lam_down, accth, rel_error, chi2_rel, chi2_a
 
 def gadf_fit_cube(x, Y, pars, sigma=None, lambda_=None, lam_up=None, lam_down=None, accth=None, rel_error=None, chi2_rel=None,
                   chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, lanes_per_fit=None, errors=None, bounds=None,
-                  loss=None, loss_scale=None, **kw):
+                  loss=None, loss_scale=None, estimator=None, **kw):
     """gadf_fit_batch over a data cube (gfh_set_batch_cube): every spectrum on the one grid ``x`` [n_points], ``Y`` [n_fits][n_points] a
     C-contiguous numpy array of float64, float32 or uint16 that is uploaded as it is.  The weights follow from ``Y`` on the device by
     the session's ``gadf_set_errors`` type (NONE, SQRT_Y, PROPTO_Y, INVERSE_Y: no weight array exists anywhere; gadf_fit_batch ignores
     that type, this call takes it); under USER ``sigma`` [n_fits][n_points] is required and 1 / sigma is passed.  ``pars``, the fit
     arguments, ``lanes_per_fit``, ``errors``, ``bounds``, ``loss``, ``loss_scale`` and what is returned are gadf_fit_batch's; the weights
-    are formed on the device, so ``loss_scale`` is the one way to move a loss's threshold here."""
-    return _fit_cube('gadf_fit_cube', False, x, Y, pars, sigma, DTD_min, lanes_per_fit, 0, errors, bounds, loss, loss_scale,
+    are formed on the device, so ``loss_scale`` is the one way to move a loss's threshold here.  ``estimator`` is gadf_fit_batch's: a
+    cube of counts under 'poisson' wants ``gadf_set_errors(NONE)`` -- any rule works as a mask, but SQRT_Y pays a sqrt and a division
+    per point for nothing."""
+    return _fit_cube('gadf_fit_cube', False, x, Y, pars, sigma, DTD_min, lanes_per_fit, 0, errors, bounds, loss, loss_scale, estimator,
                      _cube_fit_args(lambda_, lam_up, lam_down, accth, rel_error, chi2_rel, chi2_abs, lam_incs, max_iter, damp_max, kw))
 
 
 def gadf_fit_frames(x, F, pars, sigma=None, lambda_=None, lam_up=None, lam_down=None, accth=None, rel_error=None, chi2_rel=None,
                     chi2_abs=None, DTD_min=None, lam_incs=None, max_iter=None, damp_max=None, lanes_per_fit=None, frames_per_put=0, errors=None,
-                    bounds=None, loss=None, loss_scale=None, **kw):
+                    bounds=None, loss=None, loss_scale=None, estimator=None, **kw):
     """gadf_fit_cube for a stack of frames (gfh_set_batch_frames): ``F`` [n_points][n_fits], one image per abscissa of ``x`` with the
     fit (pixel) index fastest, as instruments deliver it -- C-contiguous in float64, float32 or uint16, uploaded as it is and
     transposed into the cube on the device, so no ``np.ascontiguousarray(F.T)`` runs on the host.  ``sigma`` (under USER) is
     frame-major as ``F``; ``frames_per_put``: frames per upload, 0 the library's rule.  Everything else, and what is returned (the
-    bits included), is gadf_fit_cube's on the transposed arrays."""
-    return _fit_cube('gadf_fit_frames', True, x, F, pars, sigma, DTD_min, lanes_per_fit, frames_per_put, errors, bounds, loss, loss_scale,
+    bits included), is gadf_fit_cube's on the transposed arrays -- ``estimator`` too: a stack of counts under 'poisson' wants
+    ``gadf_set_errors(NONE)``."""
+    return _fit_cube('gadf_fit_frames', True, x, F, pars, sigma, DTD_min, lanes_per_fit, frames_per_put, errors, bounds, loss, loss_scale, estimator,
                      _cube_fit_args(lambda_, lam_up, lam_down, accth, rel_error, chi2_rel, chi2_abs, lam_incs, max_iter, damp_max, kw))
 
 

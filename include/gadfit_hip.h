@@ -577,6 +577,28 @@ int  gfh_set_batch_loss(gfh_ctx* ctx, int loss, double scale);
 int  gfh_get_batch_loss(gfh_ctx* ctx, double* scale);
 /* The loss (return value; -1: none yet) and *scale (may be NULL) of the last batch launch of this context that sweeps. */
 int  gfh_debug_batch_loss(gfh_ctx* ctx, double* scale);
+/* What every batch call minimises from here on (it stays set, as gfh_set_batch_loss; no GPU and no model needed):
+ * GFH_ESTIMATOR_LSQ (0, the default, and what a batch was before this setting) the weighted sum of squares chi2 = sum ((y - f) w)^2, or
+ * GFH_ESTIMATOR_POISSON (1) the Poisson deviance D = 2 sum [f - y + y ln(y / f)] over the points whose weight is not 0 -- the
+ * maximum-likelihood fit of counted data, where 1 / sqrt(y) weights bias the amplitudes low and a bin with y = 0 has no weight.  The
+ * term of a point with y = 0 is 2 f; a term with f <= 0, y < 0 or an operand that is not finite is NaN.  The data form's weight is a mask
+ * there and nothing more: give a cube error_type NONE (any rule works, but SQRT_Y then pays a sqrt and a division per point for nothing).
+ * The loop runs by Fisher scoring: STEP 1+2 form J^T J = sum g g^T / f and J^T r = sum g (y - f) / f, the least-squares pass at the
+ * weights 1 / sqrt(f(P)), so J^T J is positive semidefinite for every y >= 0, empty bins carry curvature, and its inverse, which
+ * gfh_batch_covariance / gfh_fit_batch_errors return unchanged, is the Cramer-Rao covariance; under scale 1 it is multiplied by D / dof
+ * (the quasi-Poisson factor).  D stands wherever chi2 stood: the first value, the acceptance test new < old (a NaN deviance is a
+ * rejected trial), chi2_abs and chi2_rel, the record's chi2 and gfh_batch_pass's third output.  A fit that starts with a NaN deviance or
+ * whose J^T J is not positive definite ends with exit reason 8; its neighbours go on.  gfh_fit_batch_bounded pins on the sign of
+ * J^T r.  Refused by the launching calls, before the device is asked for: estimator 1 together with a batch loss != 0, with accth
+ * (STEP 3's second derivative is that of the least-squares cost), and a residual from gfh_batch_eval (model and band are given).
+ * Refused here: an unknown estimator.  One estimator per batch; it is part of the unit's text, and the text of a least-squares unit is
+ * what it was.  Not built: other likelihoods, an estimator per fit, geodesic acceleration under it, a Fortran entry. */
+enum { GFH_ESTIMATOR_LSQ = 0, GFH_ESTIMATOR_POISSON = 1 };
+int  gfh_set_batch_estimator(gfh_ctx* ctx, int estimator);
+/* The setting as it stands (-1: ctx is NULL); 0 until it is set. */
+int  gfh_get_batch_estimator(gfh_ctx* ctx);
+/* The estimator of the last batch launch of this context that sweeps (-1: none yet). */
+int  gfh_debug_batch_estimator(gfh_ctx* ctx);
 /* Device time of the kernel of this context's last gfh_batch_pass in seconds (HIP events around the launch; 0: none yet): the
  * yardstick tools/bench_batch.py --eval holds gfh_batch_eval's kernel against. */
 double gfh_debug_batch_pass_seconds(gfh_ctx* ctx);

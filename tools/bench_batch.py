@@ -12,6 +12,7 @@ profiles/r05_small_fits.txt: 1000 points, a Gaussian on a background, 4 paramete
     python tools/bench_batch.py --cov [--sizes 16384,131072] [--points 1000] [--lanes 64] [--out profiles/batch_cov.json]
     python tools/bench_batch.py --bounds [--sizes 16384] [--points 1000] [--lanes 64] [--out profiles/batch_bounds.json]
     python tools/bench_batch.py --loss [--registers] [--sizes 16384] [--points 1000] [--lanes 64] [--out profiles/batch_loss.json]
+    python tools/bench_batch.py --estimator [--registers] [--cells gauss4:64:16384:1000,...] [--out profiles/batch_mle.json]
     python tools/bench_batch.py --eval [--cells gauss4:64:16384:1000,...] [--registers] [--observed FILE] [--out profiles/batch_eval.json]
 
 Per batch size: warm-up launches, then the median of the timed launches -- device time from the HIP events around the kernel
@@ -75,6 +76,14 @@ batch_pass (the per-pass cost, free of the iteration counts; HIP events around i
 with the fits' total sweeps, chi2 passes and omega passes beside it, under accth so that the omega pass is in it); median and min-max.
 No ratio is asserted.  --registers: only the compiler's figures of the linear and the loss units of model_exp2 (4 active) and
 model_exp4 (8 active) at the three lane forms, the bounded unit included; no GPU is needed.
+--estimator: the Poisson unit of the batch kernels (gfh_set_batch_estimator(1): the deviance by Fisher scoring) against the least-squares
+unit -- the parent commit's kernels, whose text did not change -- at shapes of the tables above (model:lanes:fits:points).  The spectra
+are counts (the models scaled by 1000 and rounded, as --cube's) in the ragged form with the weights 1 / sqrt(y), which the least-squares
+unit uses and the Poisson unit reads as a mask: both load the same arrays.  The two alternate call by call on one context; per
+estimator batch_pass (HIP events around its kernel) and fit_batch (events around its kernel; the fits' total sweeps and chi2 passes
+beside it, and the device time per pass = fit time / (sweeps + chi2 passes)); median and min-max.  No ratio is asserted.  --registers:
+only the compiler's figures of the two units of model_exp2 (4 active) and model_exp4 (8 active) at the three lane forms, the bounded
+unit included; no GPU is needed.
 
 --eval: the curves of a batch (gfh_batch_eval: the kernel gfh_k_batch_eval) at the cells of the cube table, on the ragged form and on
 the uint16 cube under SQRT_Y of the same counts, at the start parameters with the device's own covariance.  Per cell and form three
@@ -549,6 +558,94 @@ def loss_main(a):
     print('wrote', a.out)
 
 
+# --estimator
+ESTIMATOR_NAMES = ('lsq', 'poisson')
+ESTIMATOR_CELLS = 'gauss4:64:16384:1000,exp4:64:16384:1000,gauss4:16:131072:64,gauss4:256:256:65536'
+
+
+def estimator_registers_record():
+    """{model_lanesN_<estimator>: the compiler's figures of the unit's kernels, gfh_k_fit_batch_bounded (a unit of its own) among them}"""
+    from tests import models as M
+    rec = {}
+    c = _lib.Context(-1)
+    for name, fn, n_pars in (('exp2', M.model_exp2, 4), ('exp4', M.model_exp4, 8)):
+        c.set_model(trace_model(fn, n_pars))
+        for lanes in (64, 16, 256):
+            c.set_batch_lanes(lanes)
+            for est, ename in enumerate(ESTIMATOR_NAMES):
+                c.set_batch_estimator(est)
+                r = kernel_registers(c.batch_source(list(range(n_pars))))
+                r.update(kernel_registers(c.batch_source(list(range(n_pars)), bounded=True)))
+                r.pop('gfh_k_batch_eval', None)
+                rec['%s_lanes%d_%s' % (name, lanes, ename)] = r
+                print('%s %3d lanes %-7s: %s' % (name, lanes, ename, {k: (v['vgprs'], v['scratch_bytes_per_lane'], v['waves_per_simd']) for k, v in sorted(r.items())}), flush=True)
+    c.close()
+    return rec
+
+
+def estimator_main(a):
+    """the least-squares and the Poisson unit against each other (see the module's text)"""
+    rec = json.load(open(a.out)) if os.path.exists(a.out) else {}
+    rec.update(method='per cell the two estimators alternating call by call on one context of one card in one run: lsq = the unit of the parent '
+                      'commit, whose text did not change; poisson = set_batch_estimator(1).  counts = round(%g x the model\'s spectrum), ragged form, '
+                      'weights 1 / sqrt(y) (the Poisson unit reads them as a mask).  pass = batch_pass at the start parameters, fit = fit_batch with '
+                      'lambda0 = %g, max_iter = %d; device time (HIP events around the kernel), the median and the min-max of %d calls after %d '
+                      'warm-up calls; per_pass_in_fit = fit time / (sweeps + chi2 passes of all fits) x fits: the time of one pass over the batch '
+                      'made inside a fit; no counter pass was made and no ratio is asserted' % (CUBE_SCALE, LAMBDA0, MAX_ITER, a.launches, a.warmup),
+               measurements=[])
+    kw = dict(lambda_=LAMBDA0, max_iter=MAX_ITER)
+    for cell in a.cells.split(','):
+        name, lanes, nf, n_points = cell.split(':')
+        lanes, nf, n_points = int(lanes), int(nf), int(n_points)
+        m = ROW_MODELS[name]
+        xs, ys, ws = spectra_flat(name, nf, n_points)
+        np.rint(CUBE_SCALE * ys, out=ys)
+        np.divide(1.0, np.sqrt(ys), out=ws, where=ys > 0.0)
+        ws[ys <= 0.0] = 0.0
+        scale = np.where(np.arange(m['n_pars']) % 2 == 0, CUBE_SCALE, 1.0) if name == 'exp4' else np.array([CUBE_SCALE, 1.0, 1.0, CUBE_SCALE])
+        ctx = _lib.Context(0)
+        ctx.set_model(trace_model(m['model'], m['n_pars']))
+        ctx.set_batch_lanes(lanes)
+        ctx.set_batch_data(np.arange(nf + 1, dtype=np.int64) * n_points, xs, ys, ws)
+        del xs, ys, ws
+        start = np.tile(m['start'] * scale, (nf, 1))
+        dev = {k: dict(pass_=[], fit=[]) for k in ESTIMATOR_NAMES}
+        last = {}
+        for it in range(a.warmup + a.launches):
+            for est, ename in enumerate(ESTIMATOR_NAMES):
+                ctx.set_batch_estimator(est)
+                ctx.batch_pass(start, m['active'])
+                sec_p = ctx.batch_pass_seconds()
+                p, r, sec = ctx.fit_batch(start, m['active'], **kw)
+                if ctx.batch_estimator_used() != est or ctx.batch_lanes_used() != lanes:
+                    sys.exit('the launch did not run the unit asked for')
+                last[ename] = (p, r)
+                if it >= a.warmup:
+                    dev[ename]['pass_'].append(sec_p); dev[ename]['fit'].append(sec)
+        ctx.close()
+        entry = dict(model=name, what=m['what'], n_active=len(m['active']), fits=nf, points=n_points, lanes=lanes)
+        for ename in ESTIMATOR_NAMES:
+            p, r = last[ename]
+            passes = int(r['n_sweeps'].sum()) + int(r['n_chi2'].sum())
+            entry[ename] = e = dict(device_ms_pass=_spread(dev[ename]['pass_']), device_ms_fit=_spread(dev[ename]['fit']),
+                                    device_ms_per_pass_in_fit=_spread([v * nf / passes for v in dev[ename]['fit']]),
+                                    passes=dict(sweeps=int(r['n_sweeps'].sum()), chi2=int(r['n_chi2'].sum())),
+                                    exits={str(k): int(np.sum(r['exit_reason'] == k)) for k in sorted(set(r['exit_reason'].tolist()))},
+                                    median_parameters=[float(v) for v in np.median(p, axis=0)])
+            print('%-6s %3d lanes %7d x %5d %-7s: pass %.4f ms [%.4f, %.4f], fit %.3f ms [%.3f, %.3f], per pass in fit %.4f ms, sweeps %d chi2 %d'
+                  % (name, lanes, nf, n_points, ename, e['device_ms_pass']['median'], e['device_ms_pass']['min'], e['device_ms_pass']['max'],
+                     e['device_ms_fit']['median'], e['device_ms_fit']['min'], e['device_ms_fit']['max'], e['device_ms_per_pass_in_fit']['median'],
+                     e['passes']['sweeps'], e['passes']['chi2']), flush=True)
+        entry['poisson_over_lsq'] = dict(pass_=entry['poisson']['device_ms_pass']['median'] / entry['lsq']['device_ms_pass']['median'],
+                                         per_pass_in_fit=entry['poisson']['device_ms_per_pass_in_fit']['median'] / entry['lsq']['device_ms_per_pass_in_fit']['median'])
+        print('  poisson / lsq: pass %.3f, per pass in fit %.3f' % (entry['poisson_over_lsq']['pass_'], entry['poisson_over_lsq']['per_pass_in_fit']), flush=True)
+        rec['measurements'].append(entry)
+        with open(a.out, 'w') as fh:
+            json.dump(rec, fh, indent=1, sort_keys=True)
+            fh.write('\n')
+    print('wrote', a.out)
+
+
 EVAL_CELLS = 'gauss4:64:16384:1000,gauss4:64:131072:1000,gauss4:16:131072:64,gauss4:256:256:65536'
 
 
@@ -934,6 +1031,7 @@ def main():
     ap.add_argument('--cov', action='store_true', help='fit_batch_errors against fit_batch alone and against the host route, into profiles/batch_cov.json')
     ap.add_argument('--bounds', action='store_true', help='fit_batch_bounded under infinite bounds and under a binding box against fit_batch, into profiles/batch_bounds.json')
     ap.add_argument('--loss', action='store_true', help='the Cauchy and Huber units of the batch kernels against the linear unit, into profiles/batch_loss.json')
+    ap.add_argument('--estimator', action='store_true', help='the Poisson unit of the batch kernels against the least-squares unit, into profiles/batch_mle.json')
     ap.add_argument('--eval', action='store_true', help='batch_eval against batch_pass and against the bytes it moves, into profiles/batch_eval.json')
     ap.add_argument('--cells', default=None, help='with --cube and --eval: model:lanes:fits:points, ...; with --frames: sample type:error type:lanes:fits:points, ...')
     ap.add_argument('--models', default='gauss4,exp4', help='with --workgroup: the models measured by this call (the record keeps the others)')
@@ -949,12 +1047,12 @@ def main():
                                                                  'nothing is timed, no GPU is needed')
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'batch_loss.json' if a.loss else 'batch_bounds.json' if a.bounds else 'batch_eval.json' if a.eval else 'batch_cov.json' if a.cov else 'batch_frames.json' if a.frames else 'batch_cube.json' if a.cube else 'batch_workgroup.json' if a.workgroup else 'batch_rows.json' if a.rows else 'batch_fits.json')
+        a.out = os.path.join(ROOT, 'profiles', 'batch_mle.json' if a.estimator else 'batch_loss.json' if a.loss else 'batch_bounds.json' if a.bounds else 'batch_eval.json' if a.eval else 'batch_cov.json' if a.cov else 'batch_frames.json' if a.frames else 'batch_cube.json' if a.cube else 'batch_workgroup.json' if a.workgroup else 'batch_rows.json' if a.rows else 'batch_fits.json')
     if a.cells is None:
-        a.cells = FRAMES_CELLS if a.frames else EVAL_CELLS if a.eval else CUBE_CELLS
-    if a.loss and a.registers:
+        a.cells = ESTIMATOR_CELLS if a.estimator else FRAMES_CELLS if a.frames else EVAL_CELLS if a.eval else CUBE_CELLS
+    if (a.loss or a.estimator) and a.registers:
         rec = json.load(open(a.out)) if os.path.exists(a.out) else {}
-        rec['registers'] = loss_registers_record()
+        rec['registers'] = estimator_registers_record() if a.estimator else loss_registers_record()
         with open(a.out, 'w') as fh:
             json.dump(rec, fh, indent=1, sort_keys=True)
             fh.write('\n')
@@ -998,6 +1096,8 @@ def main():
         sys.exit('at least 5 timed launches')
     if a.eval:
         return eval_main(a)
+    if a.estimator:
+        return estimator_main(a)
     if a.bounds:
         if a.sizes == '1024,16384,131072':
             a.sizes = '16384'
